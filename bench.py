@@ -12,9 +12,15 @@ shard over ranks, weak scaling) and the finished RGB images are gathered to rank
 directly (no launcher) starts the N ranks itself.
 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" for the dominant kernel k_geo_rows (fp32
-MFMA bound; duration measured live with HIP events on the launch stream, see kpn_profile_*), and
-"cpu_baseline": the CPU oracle ("port") timed on this host's cores on a bounded sample of the same
-workload (a strided sub-lattice of the same frame sized for ~15 s of CPU work).
+MFMA bound; duration measured live with HIP events on the launch stream, see kpn_profile_*).  A plain run
+does only that: set-up, warm-up, the timed steps, the line.  With --full it also measures what takes runs of
+its own: "cpu_baseline", the CPU oracle ("port") timed on this host's cores on a bounded sample of the same
+workload (a strided sub-lattice of the same frame sized for ~15 s of CPU work), "parity" of the timed frame
+against the oracle on those rays, and "secondary" (other masks, scenes, rows kernels, the training step,
+configs[4] at full size).
+
+--dump-outputs DIR writes what the timed path returned in its last step (the render_rays out dict of rank 0)
+as DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -96,7 +102,31 @@ def parse():
     ap.add_argument("--sync-gather", action="store_true", help="N > 1: gather each frame before the next one starts (default: the "
                     "gather of frame i overlaps the rendering of frame i + 1)")
     ap.add_argument("--no-configs4", action="store_true", help="skip secondary.configs4_full (4096^2 rays, 10 views, 128 flat samples: ~15 s + set-up)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: cpu_baseline, parity, "
+                    "secondary (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """The out dict of the last timed step as <dirname>/<name>.npy, float32.  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded
+    sample of pixels from every array (last two dimensions flattened), their flat indices in pixel_index.npy."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in sorted(out.items())}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        npix = next(iter(arrs.values())).shape[-2] * next(iter(arrs.values())).shape[-1]
+        n = (DUMP_LIMIT_BYTES - 128 * (len(arrs) + 1)) // (total // npix + 8)     # (128 B: the header of an .npy file)
+        idx = np.sort(np.random.default_rng(0).choice(npix, n, replace=False))
+        arrs = {k: a.reshape(*a.shape[:-2], npix)[..., idx] for k, a in arrs.items()}
+        arrs["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
 
 
 def frame_parity(frame, oracle, osc, wflat, cam_tar, bounds, pix, Sc, Sf, fine, ref, render_one=None):
@@ -471,8 +501,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     # the frame of the last timed step, for the comparison with the oracle further down (world 1: rank 0's own camera)
-    frame_np = {k: v[0].cpu().numpy() for k, v in out.items() if k in ("tex_fg", "alpha", "tex_fg_fine", "alpha_fine")} if (world == 1 and rank == 0 and not multi) else None
+    frame_np = {k: v[0].cpu().numpy() for k, v in out.items() if k in ("tex_fg", "alpha", "tex_fg_fine", "alpha_fine")} if (
+        args.full and not args.no_cpu_baseline and world == 1 and rank == 0 and not multi) else None
     gather_ms = None
     if multi:                             # the exchange alone (after the timed region): one synchronous round, averaged
         img = out["tex_fg_fine" if fine else "tex_fg"][0]
@@ -587,7 +620,7 @@ def main():
                          "clock_note": "shader cycles (s_memtime) of the rows kernel's first workgroup / the launches' HIP-event time; the peaks are quoted at 2.4 GHz, the chip clocks to its power budget",
                          "kernel_time_share": (ms.value * 1e-3) / dt},
         }
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             sec = {}
             # the other mask kind on the same cameras, and round 1's lighter framing (tar focal 600: 17 % valid)
             other = "dense" if args.mask == "ellipsoid" else "ellipsoid"
@@ -660,7 +693,7 @@ def main():
                                                                                             parity_ok=(c4.get("parity") or {}).get("ok"))
             line["roofline"]["workloads"] = {k: {kk: vv for kk, vv in v.items() if kk in ("frac", "achieved", "peak", "avg_launch_ms", "ms_per_frame", "rays_per_sec", "parity_ok")}
                                              for k, v in side.items()}
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             def make_render_one():   # the product's one-pixel render with its per-sample stages, for the rays the gate widens
                 from tests import parity_gate
                 sc1 = to_device(scene_cpu, dev)

@@ -560,6 +560,32 @@ def run_loss_case(name="case_r_loss", seed=23):
     print(f"{name}: loss={float(loss):.6f} keys={sorted(err.keys())} -> {path}")
 
 
+def run_loss_lambdas_case(name="case_u_loss_lambdas", seed=3):
+    """The reference's compute_error (src/utils.py:97-171) beyond the shipped lambdas: l2 / lp / mask loss switched on, an ssim
+    weight and `*top*` keys present (both without effect in the reference), weights of 0 — its keys, values and total per lambda set."""
+    ref_shim.load_reference()
+    import src.utils as rutils
+    g = torch.Generator().manual_seed(seed)
+    out = {"tex_cal": torch.rand(1, 3, 8, 8, generator=g), "tex_cal_fine": torch.rand(1, 3, 8, 8, generator=g),
+           "alpha": torch.rand(1, 1, 8, 8, generator=g), "alpha_fine": torch.rand(1, 1, 8, 8, generator=g),
+           "tar_img": torch.rand(1, 3, 8, 8, generator=g), "tar_alpha": (torch.rand(1, 1, 8, 8, generator=g) > 0.5).float()}
+    sets = ({"lambda_l1": 10.0, "lambda_l1_c": 1.0, "lambda_vgg": 0.5},
+            {"lambda_l1": 2.0, "lambda_l1_c": 0.0, "lambda_l2": 3.0, "lambda_lp": 0.5, "lambda_ssim": 1.0, "lambda_mloss": 4.0,
+             "lambda_l1top30": 1.0, "lambda_l2top10": 0.0})
+    d = {"in." + k: _np(v) for k, v in out.items()}
+    d["n_sets"] = np.int32(len(sets))
+    for i, lambdas in enumerate(sets):
+        loss, err = rutils.compute_error(out, None, lambdas)
+        keys = sorted(err)
+        d[f"set{i}.lambdas_json"] = np.array(__import__("json").dumps(lambdas))
+        d[f"set{i}.keys"] = np.array(keys)
+        d[f"set{i}.values"] = np.array([float(err[k]) for k in keys], np.float64)
+        d[f"set{i}.loss"] = np.float64(float(loss))
+    path = os.path.join(GOLDEN_DIR, name + ".npz")
+    np.savez_compressed(path, **d)
+    print(f"{name}: {len(sets)} lambda sets -> {path}")
+
+
 def main():
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     net = ref_shim.build_reference_net(seed=0)
@@ -572,6 +598,9 @@ def main():
         return
     if "--only-loss" in sys.argv:
         run_loss_case()
+        return
+    if "--only-loss-lambdas" in sys.argv:
+        run_loss_lambdas_case()
         return
     if "--only-headline" in sys.argv:
         run_headline_cases(net)
@@ -604,6 +633,7 @@ def main():
     run_sigma_nofine_case(net)
     run_headline_cases(net)
     run_loss_case()
+    run_loss_lambdas_case()
     run_real_encoder_case(net)
 
 

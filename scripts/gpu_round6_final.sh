@@ -5,10 +5,11 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; TAG=${1:-r06_z}; QUICK=$2; export HSA_ENABLE_IPC_MODE_LEGACY=0
 (timeout 600 python __graft_entry__.py --smoke) > gpurun_out/smoke_$TAG.log 2>&1; echo "smoke rc=$?"; tail -1 gpurun_out/smoke_$TAG.log
 (timeout 1800 python -m pytest tests -m gpu -q) > gpurun_out/pytest_gpu_$TAG.log 2>&1; echo "pytest rc=$?"; tail -4 gpurun_out/pytest_gpu_$TAG.log | cut -c1-300
-(timeout 1500 python bench.py --steps 20 --warmup 5) > gpurun_out/bench_$TAG.json 2>gpurun_out/bench_$TAG.err; echo "bench rc=$?"
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"   # where the bench line and its log go
+(timeout 1500 python bench.py --full --steps 20 --warmup 5) > "$BENCH_OUT/bench_$TAG.json" 2> "$BENCH_OUT/bench_$TAG.err"; echo "bench rc=$?"
 python - <<PY
 import json
-d = json.loads(open("gpurun_out/bench_$TAG.json").read().strip().splitlines()[-1])
+d = json.loads(open("$BENCH_OUT/bench_$TAG.json").read().strip().splitlines()[-1])
 r = d["roofline"]
 print("ms_per_step", d["ms_per_step"], "value", d["value"], "frac", r["frac"], "avg_launch_ms", r["avg_launch_ms"], "clock", r.get("effective_clock_ghz"))
 print("workloads", json.dumps(r.get("workloads"), indent=0)[:1500])

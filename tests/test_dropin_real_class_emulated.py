@@ -17,7 +17,8 @@ import torch
 
 from oracle import ref_shim
 
-pytestmark = pytest.mark.skipif(not ref_shim.reference_available(), reason="needs /root/reference (build container)")
+# every test but the compute_error one drives the live reference class
+needs_reference = pytest.mark.skipif(not ref_shim.reference_available(), reason="needs the reference source tree (KPNERF_REFERENCE_ROOT)")
 
 _CPU_KERNELS = ("rgba2out", "rgba2out_backward", "importance_sample", "ray_bbox_intersection", "field_query", "render_rays",
                 "render_rays_train", "render_rays_train_backward", "pix_l1_loss")
@@ -50,6 +51,7 @@ def _close(got, ref, name, tol=1e-4, flips=0):
     assert int((d > tol).sum()) <= flips, (name, float(d.max()))
 
 
+@needs_reference
 @torch.no_grad()
 def test_render_pifu_nerf_of_the_live_class(emulated):
     """render_full_nerf_image's call (src/model.py:454-472), encoders included, reference vs installed."""
@@ -70,6 +72,7 @@ def test_render_pifu_nerf_of_the_live_class(emulated):
         assert torch.equal(got[k], again[k]), k
 
 
+@needs_reference
 def test_encoders_run_once_per_source_set_and_again_when_their_state_changes(emulated):
     """render_novel_views attaches the source set once (attach_im_feat, src/model.py:479) and render_pifu_nerf re-runs both
     encoders per camera (:913-914).  With the drop-in the attached maps are taken as long as the images AND the encoders' state
@@ -109,6 +112,7 @@ def test_encoders_run_once_per_source_set_and_again_when_their_state_changes(emu
         uninstall(net)
 
 
+@needs_reference
 @torch.no_grad()
 def test_attached_maps_are_not_served_after_the_module_replaced_them(emulated):
     """The reference overwrites net.feat_geo / net.feat_tex on EVERY attach_*_feat call, also with return_val=True
@@ -144,18 +148,18 @@ def test_attached_maps_are_not_served_after_the_module_replaced_them(emulated):
 def test_compute_error_matches_the_reference_for_its_other_lambdas(emulated):
     """losses.compute_error against the reference's compute_error (src/utils.py:97-171) beyond the shipped lambdas: l2 / lp /
     mask loss switched on, an ssim weight and `*top*` keys present (both without effect in the reference), weights of 0 —
-    same keys, same values, nothing refused."""
+    same keys, same values, nothing refused.  The reference's keys and values are recorded in golden case U
+    (oracle/make_golden.py::run_loss_lambdas_case)."""
+    import json
+    import os
     from keypointnerf_amd import losses
-    ref_shim.load_reference()
-    import src.utils as rutils
-    g = torch.Generator().manual_seed(3)
-    out = {"tex_cal": torch.rand(1, 3, 8, 8, generator=g), "tex_cal_fine": torch.rand(1, 3, 8, 8, generator=g),
-           "alpha": torch.rand(1, 1, 8, 8, generator=g), "alpha_fine": torch.rand(1, 1, 8, 8, generator=g),
-           "tar_img": torch.rand(1, 3, 8, 8, generator=g), "tar_alpha": (torch.rand(1, 1, 8, 8, generator=g) > 0.5).float()}
-    for lambdas in ({"lambda_l1": 10.0, "lambda_l1_c": 1.0, "lambda_vgg": 0.5},
-                    {"lambda_l1": 2.0, "lambda_l1_c": 0.0, "lambda_l2": 3.0, "lambda_lp": 0.5, "lambda_ssim": 1.0, "lambda_mloss": 4.0,
-                     "lambda_l1top30": 1.0, "lambda_l2top10": 0.0}):
-        want_loss, want = rutils.compute_error(out, None, lambdas)
+    from tests.golden_io import GOLDEN_DIR
+    z = np.load(os.path.join(GOLDEN_DIR, "case_u_loss_lambdas.npz"))
+    out = {k[len("in."):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in.")}
+    for i in range(int(z["n_sets"])):
+        lambdas = json.loads(str(z[f"set{i}.lambdas_json"]))
+        want = dict(zip(z[f"set{i}.keys"].tolist(), z[f"set{i}.values"].tolist()))
+        want_loss = float(z[f"set{i}.loss"])
         got_loss, got = losses.compute_error(out, None, lambdas)
         assert set(got) == set(want), (set(got), set(want))
         for k in want:
@@ -163,6 +167,7 @@ def test_compute_error_matches_the_reference_for_its_other_lambdas(emulated):
         assert abs(float(got_loss) - float(want_loss)) <= 1e-6 * max(1.0, abs(float(want_loss)))
 
 
+@needs_reference
 def test_validation_call_of_the_live_class_consumes_the_same_random_stream(emulated):
     """KeypointNeRF.forward in eval mode (validation_step, src/model.py:509-526 -> :866-884): uniform=False, jittered
     depths and a CPU-drawn importance u.  Same seed => the reference and the drop-in must draw the same numbers."""
@@ -193,6 +198,7 @@ def test_validation_call_of_the_live_class_consumes_the_same_random_stream(emula
         _close(got[k], ref[k], k)
 
 
+@needs_reference
 def test_training_step_of_the_live_class_forward_and_gradients(emulated):
     """Train mode (src/model.py:866-884 with net.training): random patch centre (numpy), per-view dropout, density noise,
     stratified depths, importance draws — and loss.backward() into the field's parameters AND, through the feature maps, into
