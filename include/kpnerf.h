@@ -30,7 +30,9 @@ extern "C" {
 
 /* 3 (round 6): kpn_render_args gained `stages` at its end (callers built against 2 must be rebuilt: the struct grew);
  * new entry points: kpn_set_density_first / kpn_get_density_first / kpn_density_stats / kpn_density_first_passes, kpn_bwd_profile_* */
-#define KPN_ABI_VERSION 3
+/* 4: additive - the perceptual term of the training loss: kpn_vgg_plain_floats / kpn_vgg_packed_floats / kpn_vgg_pack_device,
+ * kpn_vgg_workspace_bytes / kpn_vgg_stage_floats, kpn_vgg_loss (nothing of ABI 3 changed) */
+#define KPN_ABI_VERSION 4
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -398,6 +400,32 @@ int kpn_render_rays_train_backward_kept(const kpn_scene_desc* desc, const void* 
                                         const kpn_render_args* args, const kpn_train_args* train, const kpn_render_grads* grads,
                                         float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, void* state,
                                         size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The perceptual term of the training loss, VGGLoss (src/utils.py:750-805), called by compute_error on every training and
+ * validation step (src/utils.py:164-170, lambda_vgg in configs/zju.json):
+ *   loss = lambda * sum_i tap_w[i] * mean|phi_i(norm(x)) - phi_i(norm(y))|,   norm(v) = (v - mean) / std per channel,
+ * phi_i = vgg19.features[0:2], [2:7], [7:12], [12:21] (relu1_1 .. relu4_1): nine 3x3 / stride 1 / pad 1 convolutions with
+ * bias and ReLU, 2x2 / stride 2 floor-mode max-pools in front of the 3rd, 5th and 9th; widths 64 64 | 128 128 | 256 x4 | 512.
+ * x, y: (B, 3, H, W) fp32, B >= 1, H, W >= 8.  d_x (may be NULL = loss only): d loss / d x, with y detached and the VGG
+ * parameters frozen (src/utils.py:772-774,804) as autograd produces it: sign(0) = 0, ReLU passes where its output is > 0, a
+ * max-pool window's gradient goes to its first maximum in row-major order.  x and y go through bit-identical arithmetic, so
+ * x == y gives loss 0 and d_x 0 exactly; results are bit-reproducible (no float atomics).
+ *
+ * Weights: `plain` (device, kpn_vgg_plain_floats) = the nine convolutions of features[0:21] in order, each its OIHW weight
+ * then its bias; kpn_vgg_pack_device writes both packed copies the kernels read (forward, and transposed + flipped for the
+ * backward) into `packed` (device, kpn_vgg_packed_floats, 16-byte aligned).  mean_host[3], std_host[3] (VGGLoss.normalize),
+ * tap_w_host[4] (VGGLoss.weights) are host arrays.  `stages` (may be NULL; kpn_vgg_stage_floats): the post-ReLU output of
+ * every convolution, conv 1 .. 9 one after the other, each (2B, H_l, W_l, C_l) NHWC with the B images of x first, then those
+ * of y (H_l = H >> pools before it) - for the parity check.  `workspace` (kpn_vgg_workspace_bytes, 16-byte aligned). */
+size_t kpn_vgg_plain_floats(void);
+size_t kpn_vgg_packed_floats(void);
+int kpn_vgg_pack_device(const float* plain, float* packed, void* stream);
+size_t kpn_vgg_workspace_bytes(int32_t B, int32_t H, int32_t W);
+size_t kpn_vgg_stage_floats(int32_t B, int32_t H, int32_t W);
+int kpn_vgg_loss(const float* x, const float* y, int32_t B, int32_t H, int32_t W, const float* packed, const float* mean_host,
+                 const float* std_host, const float* tap_w_host, float lambda, float* loss, float* d_x, float* stages,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* FLOP / byte model of one field evaluation, for roofline reporting */
 double kpn_flops_per_point(int32_t n_views);

@@ -127,8 +127,14 @@ _SIGNATURES = {
     "kpn_row_scratch_cap_bytes": (ctypes.c_size_t, []),
     "kpn_set_row_scratch_cap_bytes": (ctypes.c_int, [ctypes.c_size_t]),
     "kpn_selftest_mfma": (ctypes.c_int, [c_p, c_p, c_p]),
+    "kpn_vgg_plain_floats": (c_sz, []),
+    "kpn_vgg_packed_floats": (c_sz, []),
+    "kpn_vgg_pack_device": (ctypes.c_int, [c_p, c_p, c_p]),
+    "kpn_vgg_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "kpn_vgg_stage_floats": (c_sz, [c_i32, c_i32, c_i32]),
+    "kpn_vgg_loss": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class KpnError(RuntimeError):

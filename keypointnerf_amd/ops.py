@@ -589,6 +589,44 @@ def pix_l1_loss(src, tar, lam, want_grad=True):
     return loss.reshape(()), d
 
 
+def vgg_pack(plain):
+    """Packs the nine convolutions of vgg19.features[0:21] (flat device fp32: each OIHW weight then its bias, in features
+    order; vgg.plain_from_module) on the device into the layout kpn_vgg_loss reads (reference src/utils.py:750-805)."""
+    L = kl.get_library()
+    w = _dev(plain, "plain").reshape(-1)
+    if w.numel() != L.kpn_vgg_plain_floats():
+        raise ValueError(f"expected {L.kpn_vgg_plain_floats()} VGG parameters, got {w.numel()}")
+    packed = torch.empty(L.kpn_vgg_packed_floats(), dtype=_f32, device=w.device)
+    L.check(L.kpn_vgg_pack_device(_p(w), _p(packed), _stream()))
+    return packed
+
+
+def vgg_loss(x, y, packed, mean, std, tap_w, lam=1.0, want_grad=True, want_stages=False):
+    """VGGLoss.forward(x, y) of the reference (src/utils.py:795-805) times lam, and d loss / d x (y detached, VGG frozen).
+    x, y: (B, 3, H, W) device fp32; packed: vgg_pack(...); mean, std (3 floats), tap_w (4 floats): VGGLoss.normalize and
+    VGGLoss.weights.  Returns (loss: 0-dim tensor, d_x like x or None, stages or None); stages (kpn_vgg_stage_floats, flat):
+    the post-ReLU output of every convolution for x and y (include/kpnerf.h)."""
+    L = kl.get_library()
+    a, b = _dev(x, "x"), _dev(y, "y")
+    if a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape:
+        raise ValueError(f"x and y must both be (B, 3, H, W), got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, _, H, W = a.shape
+    nb = L.kpn_vgg_workspace_bytes(B, H, W)
+    if nb == 0:
+        raise ValueError(f"VGG loss needs H, W >= 8 (got {H} x {W})")
+    hmean, hstd, hw = (np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)) for v in (mean, std, tap_w))
+    if hmean.size != 3 or hstd.size != 3 or hw.size != 4:
+        raise ValueError("mean / std need 3 values, tap_w 4")
+    loss = torch.empty(1, dtype=_f32, device=a.device)
+    d = torch.empty_like(a) if want_grad else None
+    st = torch.empty(L.kpn_vgg_stage_floats(B, H, W), dtype=_f32, device=a.device) if want_stages else None
+    ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
+    L.check(L.kpn_vgg_loss(_p(a), _p(b), B, H, W, _p(packed), hmean.ctypes.data_as(ctypes.c_void_p),
+                           hstd.ctypes.data_as(ctypes.c_void_p), hw.ctypes.data_as(ctypes.c_void_p), float(lam), _p(loss), _p(d),
+                           _p(st), _p(ws), nb, _stream()))
+    return loss.reshape(()), d, st
+
+
 def ssim(pred, gt, mask_at_box=None):
     """SSIM of ZJUEvaluator._compute_ssim (reference src/zju_evaluator.py:21-45): pred, gt (3,H,W) or (1,3,H,W) in [0,1];
     mask_at_box (H,W): the images are cropped to its bounding rectangle (cv2.boundingRect) first.  Returns a float."""

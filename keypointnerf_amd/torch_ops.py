@@ -20,6 +20,7 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 ``scene_ws / scene_dims / scene_scalars`` come from ``ops.PreparedScene.as_op_args()``.
 
     torch.ops.kpnerf.pix_l1_loss(src, tar, lam) -> (loss, d loss / d src)   the L1 terms of the training loss, DIFFERENTIABLE
+    torch.ops.kpnerf.vgg_loss(x, y, packed, consts, lam) -> (loss, d loss / d x)   the perceptual term, DIFFERENTIABLE w.r.t. x
 
 ``rgba2out`` and ``render_rays_train`` carry ``register_autograd`` formulas whose backward is itself a registered op
 (``kpnerf::rgba2out_backward``, ``kpnerf::render_rays_train_backward`` = kpn_render_rays_train_backward): gradients reach
@@ -315,3 +316,28 @@ def _l1_bwd(ctx, d_loss, _d_grad):
 
 
 pix_l1_loss.register_autograd(_l1_bwd, setup_context=_l1_setup)
+
+
+@_lib.custom_op("kpnerf::vgg_loss", mutates_args=(), device_types="cuda")
+def vgg_loss(x: torch.Tensor, y: torch.Tensor, packed: torch.Tensor, consts: List[float], lam: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lam * VGGLoss(x, y), d loss / d x) (reference src/utils.py:750-805, kpn_vgg_loss).  consts = mean[3] + std[3] + the four
+    tap weights of the module; packed = ops.vgg_pack(...).  Differentiable w.r.t. x (y detached, VGG parameters frozen)."""
+    loss, d, _ = ops.vgg_loss(x, y, packed, consts[0:3], consts[3:6], consts[6:10], lam, want_grad=True)
+    return loss, d
+
+
+@vgg_loss.register_fake
+def _(x, y, packed, consts, lam):
+    return x.new_empty(()), torch.empty_like(x)
+
+
+def _vgg_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _vgg_bwd(ctx, d_loss, _d_grad):
+    (g,) = ctx.saved_tensors
+    return g * d_loss, None, None, None, None
+
+
+vgg_loss.register_autograd(_vgg_bwd, setup_context=_vgg_setup)
