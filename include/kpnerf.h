@@ -32,7 +32,9 @@ extern "C" {
  * new entry points: kpn_set_density_first / kpn_get_density_first / kpn_density_stats / kpn_density_first_passes, kpn_bwd_profile_* */
 /* 4: additive - the perceptual term of the training loss: kpn_vgg_plain_floats / kpn_vgg_packed_floats / kpn_vgg_pack_device,
  * kpn_vgg_workspace_bytes / kpn_vgg_stage_floats, kpn_vgg_loss (nothing of ABI 3 changed) */
-#define KPN_ABI_VERSION 4
+/* 5: additive - forward of the two image encoders: kpn_geo_encoder_* / kpn_geo_encode (HGFilterV2), kpn_tex_encoder_* /
+ * kpn_tex_encode (ResBlkEncoder) (nothing of ABI 4 changed) */
+#define KPN_ABI_VERSION 5
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -435,6 +437,53 @@ double kpn_flops_per_row(void);
 /* Device self-test of the MFMA operand/result lane maps the kernels assume (asymmetric operands).
  * Returns 0 if D == A*B for v_mfma_f32_32x32x2_f32 in the assumed layout. */
 int kpn_selftest_mfma(float* scratch_256k, void* stream, float* max_err_host);
+
+/* -------------------------------------------------------------------------------------------------------------------------
+ * The image encoders in front of the ray march, forward only (inference): the reference's HGFilterV2 (geometry) and
+ * ResBlkEncoder (texture), src/utils.py:199-474, as attach_geo_feat / attach_tex_feat call them (src/model.py:653-680):
+ *   feat_geo = geo_encoder(2 * avg_pool2d^ds(im) - 1),   feat_tex = tex_encoder(2 * avg_pool2d^ds(im) - 1).
+ * img: (V, 3, H, W) fp32 NCHW in [0, 1] (the source images, before the ds average pools; ds = ds_geo / ds_tex, 0 or 1: one
+ * average pool is one rounding, as in the reference; more pools are refused with KPN_EINVAL).
+ * Outputs are NHWC.  Kernels: csrc/encoder_kernels.hip (fp32 MFMA implicit GEMM; no float atomics, fixed-order reductions:
+ * bit-reproducible, and the maps of an image do not depend on the other images of the call).
+ *
+ * Geometry: HGFilterV2(n_stack = 1, n_downsample = 4, hd = False, norm = "group", out_ch, out_ch_hd); h = H >> ds and
+ * w = W >> ds must be multiples of 64 (KPN_EINVAL otherwise).  feat (V, h/4, w/4, out_ch) = HGFilterV2.forward(x)[0],
+ * feat_hd (V, h, w, out_ch_hd) = [1].  Texture: ResBlkEncoder(3, out_ch, ngf, n_down, n_blocks, n_up, norm = "instance"), ngf a
+ * power of two >= 8, 1 <= n_up <= n_down <= 5; any h, w >= 1; feat (V, ht, wt, out_ch) with ht = h after n_down steps of
+ * (h - 1) / 2 + 1 and n_up doublings.  eps: the eps of the GroupNorm / InstanceNorm2d modules.
+ *
+ * Weights: `plain` (device, *_plain_floats) holds the parameters in the order the forward meets them - per convolution its
+ * OIHW (ConvTranspose2d: IOHW) weight then its bias, per GroupNorm gamma then beta, a ConvBlock as bn1, conv1, bn2, conv2, bn3,
+ * conv3 [, bn4, downsample convolution]; geometry: conv1, bn1, conv2, unpack1.conv, unpack1.norm, conv_out, conv3, conv4, the
+ * hourglass in call order (b1_4, b2_4, b1_3, b2_3, b1_2, b2_2, b1_1, b2_1, b2_plus_1, b3_1 .. b3_4), top_m_0, conv_last0,
+ * bn_end0, l0; texture: the convolutions of `layers` in order (keypointnerf_amd/encoders.py builds both from a module).
+ * *_pack_device writes `packed` (device, *_packed_floats, 16-byte aligned).  `stages` (may be NULL; *_stage_floats): named
+ * intermediate tensors, NHWC, for locating a disagreement; *_stage_info(index) gives name, offset (floats) and dims (V, H, W, C)
+ * of entry `index`, KPN_EINVAL behind the last.  `workspace` (*_workspace_bytes, 16-byte aligned; 0 = unsupported size). */
+size_t kpn_geo_encoder_plain_floats(int32_t out_ch, int32_t out_ch_hd);
+size_t kpn_geo_encoder_packed_floats(int32_t out_ch, int32_t out_ch_hd);
+int kpn_geo_encoder_pack_device(const float* plain, float* packed, int32_t out_ch, int32_t out_ch_hd, void* stream);
+size_t kpn_geo_encoder_workspace_bytes(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t out_ch, int32_t out_ch_hd);
+size_t kpn_geo_encoder_stage_floats(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t out_ch, int32_t out_ch_hd);
+int kpn_geo_encoder_stage_info(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t out_ch, int32_t out_ch_hd, int32_t index,
+                               char* name, int32_t name_cap, int64_t* offset, int32_t* dims);
+int kpn_geo_encode(const float* img, int32_t V, int32_t H, int32_t W, int32_t ds, int32_t out_ch, int32_t out_ch_hd,
+                   const float* packed, float eps, float* feat, float* feat_hd, float* stages, void* workspace,
+                   size_t workspace_bytes, void* stream);
+size_t kpn_tex_encoder_plain_floats(int32_t ngf, int32_t n_down, int32_t n_blocks, int32_t n_up, int32_t out_ch);
+size_t kpn_tex_encoder_packed_floats(int32_t ngf, int32_t n_down, int32_t n_blocks, int32_t n_up, int32_t out_ch);
+int kpn_tex_encoder_pack_device(const float* plain, float* packed, int32_t ngf, int32_t n_down, int32_t n_blocks, int32_t n_up,
+                                int32_t out_ch, void* stream);
+size_t kpn_tex_encoder_workspace_bytes(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t ngf, int32_t n_down, int32_t n_blocks,
+                                       int32_t n_up, int32_t out_ch);
+size_t kpn_tex_encoder_stage_floats(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t ngf, int32_t n_down, int32_t n_blocks,
+                                    int32_t n_up, int32_t out_ch);
+int kpn_tex_encoder_stage_info(int32_t V, int32_t H, int32_t W, int32_t ds, int32_t ngf, int32_t n_down, int32_t n_blocks, int32_t n_up,
+                               int32_t out_ch, int32_t index, char* name, int32_t name_cap, int64_t* offset, int32_t* dims);
+int kpn_tex_encode(const float* img, int32_t V, int32_t H, int32_t W, int32_t ds, int32_t ngf, int32_t n_down, int32_t n_blocks,
+                   int32_t n_up, int32_t out_ch, const float* packed, float eps, float* feat, float* stages, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,354 @@
+// encoder_kernels.hip — forward of the two image encoders in front of the ray march, HGFilterV2 (geometry) and ResBlkEncoder
+// (texture) of the reference (src/utils.py:199-474, called from attach_geo_feat / attach_tex_feat, src/model.py:653-680), on the
+// fp32 MFMA (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation).
+//
+// One convolution family, k_enc_conv: implicit GEMM  out[pixel][co] = sum_k A[pixel][k] * Wp[k][co]  over NHWC activations with
+// k = tap * cin_p + ci (cin_p = cin rounded up to 4, so the 3-channel stems pack four taps into one 16-wide K chunk).  A
+// workgroup of four wavefronts computes BM x BN outputs (64 x 64, or 128 x 32 for layers with at most 32 output channels), one
+// 32 x 32 accumulator per wavefront.  Per K chunk of 16 every thread loads one or two float4s of A and one of the packed
+// weights, the workgroup stages them in LDS (k-major: the lanes of an MFMA operand read consecutive floats of one row) and issues
+// eight MFMAs; the loads of chunk s + 1 are in flight while chunk s is multiplied.
+//   loads    : zero padding or replication padding (a clamp of the source coordinate), stride 1 / 2; per (image, channel)
+//              scale * x + shift with optional ReLU (GroupNorm / InstanceNorm + ReLU in front of the convolution); the stems read
+//              the NCHW images, average 2 x 2 blocks when ds = 1 (the avg_pool2d of attach_*_feat; the host admits ds <= 1) and apply 2 * im - 1;
+//   DECONV   : ConvTranspose2d(k = 3, stride = 2, padding = 1, output_padding = 1) as four gathers, one per output parity
+//              (py, px) with (1 + py) * (1 + px) valid taps each (blockIdx.z) — no scatter;
+//   epilogue : bias, residual add from a second tensor, ReLU, store into a channel slice of a wider NHWC tensor;
+//   split K  : layers with few pixels split the K chunks over blockIdx.y; the partial tiles go to scratch and k_enc_combine adds
+//              them in split order and runs the epilogue.  The split depends on the per-image geometry only.
+// Beside it: k_enc_stats_partial / k_enc_stats_final (GroupNorm / InstanceNorm statistics in fp64 partial sums, reduced in a
+// fixed order and folded with gamma / beta into the scale / shift the next loads use), k_enc_affine (normalise [+ ReLU]
+// [+ residual] where the value is needed as a tensor), k_enc_pool2 (avg_pool2d(x, 2, 2)), k_enc_upadd (bicubic x2,
+// align_corners = True, ATen's coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of
+// HourGlass._forward) and k_enc_pack.  No float atomics; every reduction has a fixed order, so results are bit-reproducible
+// and independent of the position of an image in the batch.
+
+struct kpn_enc_conv_args {
+    int nimg, Ho, Wo;          // GEMM rows = nimg * Ho * Wo.  DECONV: (Ho, Wo) is the source grid, row (y, x) of class (py, px)
+                               // writes output pixel (2y + py, 2x + px) of the (2 Ho, 2 Wo) result
+    int Hs, Ws;                // source size (STEM: after the 2^ds average)
+    int cin, cin_p;            // source channels; cin_p = cin rounded up to 4
+    int kh, kw, stride, pad, replicate;
+    int nk[4];                 // K chunks of 16 (DECONV: per parity class, else nk[0])
+    int64_t wofs[4];           // DECONV: offset (floats) of the class's packed weights
+    int ksplit;                // number of K ranges (gridDim.y)
+    const float* src;          // NHWC, pointer at the first channel of the slice; STEM: NCHW (nimg, cin, Hraw, Wraw)
+    int src_cs;                // channel stride of a source pixel
+    int Hraw, Wraw, ds;        // STEM
+    const float* ss;           // scale [nimg][cin] then shift [nimg][cin], or NULL
+    int relu_in;
+    const float* wp;           // packed [chunk][cout_p][16]
+    int cout, cout_p;
+    const float* bias;         // or NULL
+    float* dst;                // NHWC, pointer at the first channel of the slice
+    int dst_cs;
+    const float* res;          // or NULL; same pixel grid as dst
+    int res_cs;
+    int relu_out;
+    float* partial;            // ksplit > 1: [class][split][row][cout_p]
+};
+
+__device__ __forceinline__ void kpn_enc_epilogue(const kpn_enc_conv_args& a, int cls, int64_t q, int co, float v, bool deconv) {
+    int64_t dq = q;
+    if (deconv) {
+        const int hw = a.Ho * a.Wo;
+        const int n = (int)(q / hw), r = (int)(q % hw);
+        const int y = r / a.Wo, x = r % a.Wo;
+        dq = ((int64_t)n * 2 * a.Ho + 2 * y + (cls >> 1)) * (2 * a.Wo) + 2 * x + (cls & 1);
+    }
+    if (a.bias) v = KADD(v, a.bias[co]);
+    if (a.res) v = KADD(v, a.res[dq * a.res_cs + co]);
+    if (a.relu_out) v = v > 0.0f ? v : 0.0f;
+    a.dst[dq * a.dst_cs + co] = v;
+}
+
+// four consecutive K entries (one tap, channels [c, c + 4)) of GEMM row (n, oy, ox)
+template <bool STEM, bool DECONV>
+__device__ __forceinline__ kpn_f32x4 kpn_enc_load_a(const kpn_enc_conv_args& a, int cls, bool valid, int n, int oy, int ox, int kk) {
+    kpn_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int tap = kk / a.cin_p, c = kk - tap * a.cin_p;
+    int sy, sx;
+    if constexpr (DECONV) {
+        const int py = cls >> 1, px = cls & 1;
+        const int ntx = 1 + px;
+        const int ty = tap / ntx, tx = tap - ty * ntx;
+        if (ty > py) valid = false;                     // K padding behind the last tap
+        sy = oy + (py ? 1 - ty : 0);
+        sx = ox + (px ? 1 - tx : 0);
+    } else {
+        const int ky = tap / a.kw, kx = tap - ky * a.kw;
+        if (ky >= a.kh) valid = false;
+        sy = oy * a.stride - a.pad + ky;
+        sx = ox * a.stride - a.pad + kx;
+        if (a.replicate) {
+            sy = sy < 0 ? 0 : (sy >= a.Hs ? a.Hs - 1 : sy);
+            sx = sx < 0 ? 0 : (sx >= a.Ws ? a.Ws - 1 : sx);
+        }
+    }
+    if (!valid || sy < 0 || sy >= a.Hs || sx < 0 || sx >= a.Ws) return v;
+    if constexpr (STEM) {
+        const int f = 1 << a.ds;
+        const float inv = 1.0f / (float)(f * f);
+        for (int e = 0; e < 4; ++e) {
+            if (c + e >= a.cin) break;
+            const float* p = a.src + (((size_t)n * a.cin + c + e) * a.Hraw + (size_t)sy * f) * a.Wraw + (size_t)sx * f;
+            float s = 0.0f;
+            for (int j = 0; j < f; ++j)
+                for (int i = 0; i < f; ++i) s = KADD(s, p[(size_t)j * a.Wraw + i]);
+            v[e] = KSUB(KMUL(2.0f, KMUL(s, inv)), 1.0f);
+        }
+    } else {
+        v = *KPN_GLOBAL4(a.src + (((size_t)n * a.Hs + sy) * a.Ws + sx) * a.src_cs + c);
+        if (a.ss) {
+            const kpn_f32x4 sc = *KPN_GLOBAL4(a.ss + (size_t)n * a.cin + c);
+            const kpn_f32x4 sh = *KPN_GLOBAL4(a.ss + ((size_t)a.nimg + n) * a.cin + c);
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
+        }
+        if (a.relu_in)
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
+    }
+    return v;
+}
+
+template <int BM, int BN, bool STEM, bool DECONV>
+__global__ __launch_bounds__(256) void k_enc_conv(kpn_enc_conv_args a) {
+    static_assert((BM / 32) * (BN / 32) == 4, "four wavefronts, one 32 x 32 accumulator each");
+    constexpr int NA = BM * 4 / 256;        // float4s of A per thread and K chunk
+    constexpr int KQ = 256 / BM;            // K quarter step between the float4s of one thread
+    __shared__ float As[16][BM];
+    __shared__ float Bs[16][BN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cls = DECONV ? (int)blockIdx.z : 0;
+    const int ctiles = a.cout_p / BN;
+    const int ct = (int)(blockIdx.x % ctiles);
+    const int64_t pt = blockIdx.x / ctiles;
+    const int64_t M = (int64_t)a.nimg * a.Ho * a.Wo;
+    const int hw = a.Ho * a.Wo;
+    // A loads: one GEMM row per thread
+    const int arow = tid % BM, akq = tid / BM;
+    const int64_t p = pt * BM + arow;
+    const bool valid = p < M;
+    const int n = valid ? (int)(p / hw) : 0;
+    const int rem = valid ? (int)(p % hw) : 0;
+    const int oy = rem / a.Wo, ox = rem % a.Wo;
+    // B loads
+    const bool bload = tid < BN * 4;
+    const int bco = tid % BN, bkq = tid / BN;
+    const float* wbase = a.wp + (DECONV ? a.wofs[cls] : 0) + ((size_t)ct * BN + bco) * 16 + bkq * 4;
+    const int nk = a.nk[cls];
+    const int ks = (int)blockIdx.y;
+    const int s0 = (int)((int64_t)ks * nk / a.ksplit), s1 = (int)((int64_t)(ks + 1) * nk / a.ksplit);
+    kpn_f32x4 ra[NA], rb = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto load = [&](int s) {
+        for (int j = 0; j < NA; ++j) ra[j] = kpn_enc_load_a<STEM, DECONV>(a, cls, valid, n, oy, ox, s * 16 + (akq + j * KQ) * 4);
+        if (bload) rb = *KPN_GLOBAL4(wbase + (size_t)s * a.cout_p * 16);
+    };
+    const int wn = wave % (BN / 32), wm = wave / (BN / 32);
+    const int ai = wm * 32 + (lane & 31), bj = wn * 32 + (lane & 31), kh2 = lane >> 5;
+    kpn_f32x16 acc;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    if (s0 < s1) load(s0);
+    for (int s = s0; s < s1; ++s) {
+        for (int j = 0; j < NA; ++j)
+            for (int e = 0; e < 4; ++e) As[(akq + j * KQ) * 4 + e][arow] = ra[j][e];
+        if (bload)
+            for (int e = 0; e < 4; ++e) Bs[bkq * 4 + e][bco] = rb[e];
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+        for (int m = 0; m < 8; ++m)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * m + kh2][ai], Bs[2 * m + kh2][bj], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    // D[row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)][col = lane & 31]: rows are pixels, columns output channels
+    const int co = ct * BN + bj;
+    if (co >= a.cout) return;
+    for (int r = 0; r < 16; ++r) {
+        const int64_t q = pt * BM + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh2;
+        if (q >= M) continue;
+        if (a.ksplit > 1) a.partial[(((int64_t)cls * a.ksplit + ks) * M + q) * a.cout_p + co] = acc[r];
+        else kpn_enc_epilogue(a, cls, q, co, acc[r], DECONV);
+    }
+}
+
+// split-K combine: the partial tiles of one output element are added in split order, then the epilogue
+__global__ __launch_bounds__(256) void k_enc_combine(kpn_enc_conv_args a, int deconv) {
+    const int64_t M = (int64_t)a.nimg * a.Ho * a.Wo;
+    const int ncls = deconv ? 4 : 1;
+    const int64_t total = (int64_t)ncls * M * a.cout;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int co = (int)(i % a.cout);
+        const int64_t q = (i / a.cout) % M;
+        const int cls = (int)(i / a.cout / M);
+        float v = 0.0f;
+        for (int ks = 0; ks < a.ksplit; ++ks) v = KADD(v, a.partial[(((int64_t)cls * a.ksplit + ks) * M + q) * a.cout_p + co]);
+        kpn_enc_epilogue(a, cls, q, co, v, deconv != 0);
+    }
+}
+
+// statistics, step 1: block (chunk, image) adds x and x^2 of its pixel range per channel in fp64; the threads of one channel
+// quad are added in thread order.  partial [image][chunk][channel][2]
+struct kpn_enc_stats_args {
+    const float* src;      // NHWC slice
+    int cs, C, HW, nchunks, nimg;
+    double* partial;
+    // step 2
+    int G;                 // groups (InstanceNorm: G = C)
+    const float* gamma;    // or NULL
+    const float* beta;
+    float eps;
+    float* ss;             // scale [nimg][C] then shift [nimg][C]
+};
+__global__ __launch_bounds__(256) void k_enc_stats_partial(kpn_enc_stats_args a) {
+    __shared__ double red[256][8];
+    const int L = a.C / 4;                       // threads per pixel (a power of two, at most 256)
+    const int PP = 256 / L;
+    const int cl = threadIdx.x % L, pl = threadIdx.x / L;
+    const int chunk = blockIdx.x, n = blockIdx.y;
+    const int p0 = (int)((int64_t)chunk * a.HW / a.nchunks), p1 = (int)((int64_t)(chunk + 1) * a.HW / a.nchunks);
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = p0 + pl; p < p1; p += PP) {
+        const kpn_f32x4 v = *KPN_GLOBAL4(a.src + ((size_t)n * a.HW + p) * a.cs + cl * 4);
+        for (int e = 0; e < 4; ++e) { s[e] += (double)v[e]; q[e] += (double)v[e] * (double)v[e]; }
+    }
+    for (int e = 0; e < 4; ++e) { red[threadIdx.x][e] = s[e]; red[threadIdx.x][4 + e] = q[e]; }
+    __syncthreads();
+    if (pl == 0) {
+        for (int k = 1; k < PP; ++k)
+            for (int e = 0; e < 4; ++e) { s[e] += red[k * L + cl][e]; q[e] += red[k * L + cl][4 + e]; }
+        double* o = a.partial + (((size_t)n * a.nchunks + chunk) * a.C + cl * 4) * 2;
+        for (int e = 0; e < 4; ++e) { o[2 * e] = s[e]; o[2 * e + 1] = q[e]; }
+    }
+}
+// step 2: one thread per (image, group): chunks then channels in order; biased variance; scale = gamma * rstd,
+// shift = beta - mean * scale
+__global__ __launch_bounds__(64) void k_enc_stats_final(kpn_enc_stats_args a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.nimg * a.G) return;
+    const int n = i / a.G, g = i % a.G, cpg = a.C / a.G;
+    double S = 0.0, Q = 0.0;
+    for (int c = g * cpg; c < (g + 1) * cpg; ++c)
+        for (int k = 0; k < a.nchunks; ++k) {
+            const double* o = a.partial + (((size_t)n * a.nchunks + k) * a.C + c) * 2;
+            S += o[0]; Q += o[1];
+        }
+    const double cnt = (double)a.HW * cpg;
+    const double mean = S / cnt;
+    double var = Q / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+        const double sc = a.gamma ? (double)a.gamma[c] * rstd : rstd;
+        const double sh = (a.beta ? (double)a.beta[c] : 0.0) - mean * sc;
+        a.ss[(size_t)n * a.C + c] = (float)sc;
+        a.ss[((size_t)a.nimg + n) * a.C + c] = (float)sh;
+    }
+}
+
+// dst = [relu](src * scale + shift) [+ res], whole NHWC tensors (n, HW, C); ss may be NULL (plain add / copy)
+__global__ __launch_bounds__(256) void k_enc_affine(const float* src, const float* ss, int relu, const float* res, float* dst,
+                                                    int nimg, int HW, int C) {
+    const int c4 = C / 4;
+    const int64_t total = (int64_t)nimg * HW * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int n = (int)(i / c4 / HW);
+        kpn_f32x4 v = *KPN_GLOBAL4(src + i * 4);
+        if (ss) {
+            const kpn_f32x4 sc = *KPN_GLOBAL4(ss + (size_t)n * C + c), sh = *KPN_GLOBAL4(ss + ((size_t)nimg + n) * C + c);
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
+        }
+        if (relu)
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
+        if (res) {
+            const kpn_f32x4 r = *KPN_GLOBAL4(res + i * 4);
+            for (int e = 0; e < 4; ++e) v[e] = KADD(v[e], r[e]);
+        }
+        *reinterpret_cast<kpn_f32x4*>(dst + i * 4) = v;
+    }
+}
+
+// avg_pool2d(x, 2, stride = 2): (n, 2 Ho, 2 Wo, C) -> (n, Ho, Wo, C), rows added in window order
+__global__ __launch_bounds__(256) void k_enc_pool2(const float* src, float* dst, int nimg, int Ho, int Wo, int C) {
+    const int c4 = C / 4;
+    const int64_t total = (int64_t)nimg * Ho * Wo * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int x = (int)((i / c4) % Wo), y = (int)((i / c4 / Wo) % Ho), n = (int)(i / c4 / Wo / Ho);
+        const float* p = src + (((size_t)n * 2 * Ho + 2 * y) * (2 * Wo) + 2 * x) * C + c;
+        const kpn_f32x4 p00 = *KPN_GLOBAL4(p), p01 = *KPN_GLOBAL4(p + C);
+        const kpn_f32x4 p10 = *KPN_GLOBAL4(p + (size_t)2 * Wo * C), p11 = *KPN_GLOBAL4(p + (size_t)2 * Wo * C + C);
+        kpn_f32x4 v;
+        for (int e = 0; e < 4; ++e) v[e] = KMUL(KADD(KADD(KADD(p00[e], p01[e]), p10[e]), p11[e]), 0.25f);
+        *reinterpret_cast<kpn_f32x4*>(dst + i * 4) = v;
+    }
+}
+
+// ATen's cubic convolution coefficients (A = -0.75) for the taps at floor(s) - 1 .. floor(s) + 2
+__device__ __forceinline__ void kpn_enc_cubic(float t, float (&w)[4]) {
+    const float A = -0.75f;
+    const float x0 = t + 1.0f, x1 = t, x2 = 1.0f - t, x3 = 2.0f - t;
+    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
+    w[1] = ((A + 2.0f) * x1 - (A + 3.0f)) * x1 * x1 + 1.0f;
+    w[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
+    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
+}
+// up (n, 2h, 2w, C) += interpolate(low (n, h, w, C), scale_factor = 2, mode = 'bicubic', align_corners = True)
+__global__ __launch_bounds__(256) void k_enc_upadd(const float* low, float* up, int nimg, int h, int w, int C) {
+    const int c4 = C / 4, Ho = 2 * h, Wo = 2 * w;
+    const float sy = Ho > 1 ? (float)(h - 1) / (float)(Ho - 1) : 0.0f, sx = Wo > 1 ? (float)(w - 1) / (float)(Wo - 1) : 0.0f;
+    const int64_t total = (int64_t)nimg * Ho * Wo * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int x = (int)((i / c4) % Wo), y = (int)((i / c4 / Wo) % Ho), n = (int)(i / c4 / Wo / Ho);
+        const float fy = KMUL(sy, (float)y), fx = KMUL(sx, (float)x);
+        const int iy = (int)floorf(fy), ix = (int)floorf(fx);
+        float wy[4], wx[4];
+        kpn_enc_cubic(KSUB(fy, (float)iy), wy);
+        kpn_enc_cubic(KSUB(fx, (float)ix), wx);
+        kpn_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = 0; j < 4; ++j) {
+            int yy = iy - 1 + j;
+            yy = yy < 0 ? 0 : (yy >= h ? h - 1 : yy);
+            kpn_f32x4 row = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < 4; ++k) {
+                int xx = ix - 1 + k;
+                xx = xx < 0 ? 0 : (xx >= w ? w - 1 : xx);
+                const kpn_f32x4 v = *KPN_GLOBAL4(low + (((size_t)n * h + yy) * w + xx) * C + c);
+                for (int e = 0; e < 4; ++e) row[e] = fmaf(v[e], wx[k], row[e]);
+            }
+            for (int e = 0; e < 4; ++e) acc[e] = fmaf(row[e], wy[j], acc[e]);
+        }
+        kpn_f32x4 u = *KPN_GLOBAL4(up + i * 4);
+        for (int e = 0; e < 4; ++e) u[e] = KADD(u[e], acc[e]);
+        *reinterpret_cast<kpn_f32x4*>(up + i * 4) = u;
+    }
+}
+
+// packer of one convolution: OIHW (Conv2d) or IOHW (ConvTranspose2d, parity class cls) -> [chunk][cout_p][16] with
+// k = tap * cin_p + ci; everything beyond the real taps / channels is zero
+struct kpn_enc_pack_args {
+    const float* w;
+    float* out;
+    int cin, cin_p, cout, cout_p, kh, kw, nk, deconv, cls;
+};
+__global__ __launch_bounds__(256) void k_enc_pack(kpn_enc_pack_args a) {
+    const int64_t total = (int64_t)a.nk * a.cout_p * 16;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int e = (int)(i % 16), co = (int)((i / 16) % a.cout_p), s = (int)(i / 16 / a.cout_p);
+        const int kk = s * 16 + e, tap = kk / a.cin_p, c = kk % a.cin_p;
+        float v = 0.0f;
+        if (co < a.cout && c < a.cin) {
+            if (a.deconv) {
+                const int py = a.cls >> 1, px = a.cls & 1, ntx = 1 + px;
+                const int ty = tap / ntx, tx = tap % ntx;
+                if (ty <= py) {
+                    const int ky = py ? 2 * ty : 1, kx = px ? 2 * tx : 1;
+                    v = a.w[(((size_t)c * a.cout + co) * 3 + ky) * 3 + kx];
+                }
+            } else if (tap < a.kh * a.kw) {
+                v = a.w[((size_t)co * a.cin + c) * a.kh * a.kw + tap];
+            }
+        }
+        a.out[i] = v;
+    }
+}

@@ -1,0 +1,307 @@
+"""The two image encoders in front of the ray march on the device, forward only: the reference's HGFilterV2 (geometry) and
+ResBlkEncoder (texture), src/utils.py:199-474 — ``ops.geo_encode`` / ``ops.tex_encode`` (kpn_geo_encode / kpn_tex_encode,
+csrc/encoder_kernels.hip).
+
+The weights stay the caller's: ``NativeGeoEncoder(module)`` / ``NativeTexEncoder(module)`` read the caller's module by
+structure (sub-modules, eps, group counts, affine parameters, biases), pack once on the device and again whenever a
+parameter's identity, storage or version changes.  What the kernels do not implement is refused at construction with a
+NotImplementedError that names it: norm="batch", hd=True, n_stack != 1, a ResBlkEncoder with another norm, unexpected layers.
+
+``install_encoders(net, geo=True, tex=False)`` rebinds ``net.attach_geo_feat`` / ``net.attach_tex_feat`` on the instance
+(src/model.py:653-680): when no gradient is needed (``not net.training``, or gradients disabled, or no encoder parameter
+requires one) and the images are CUDA fp32, the maps come from the native encoders, otherwise from the module's own forward
+(training keeps autograd).  The maps have the reference's NCHW shapes, dtype and device, in channels-last memory.
+``uninstall_encoders(net)`` restores what was bound before.  Nothing changes unless the caller installs them; ``install(net)``
+does not.  The texture encoder is off by default: on the 3 x 512^2 source set it is slower than the module on MIOpen
+(profiles/encoders.md); ``tex=True`` serves it natively all the same.
+"""
+import types
+
+import torch
+
+from . import ops
+from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
+from .dropin import _version_key
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _refuse(what):
+    raise NotImplementedError(f"native encoders: {what} is not implemented")
+
+
+def _check_conv(m, where, cin, cout, k, stride, pad, bias, transposed=False):
+    nn = torch.nn
+    cls = nn.ConvTranspose2d if transposed else nn.Conv2d
+    ok = (type(m) is cls and m.in_channels == cin and m.out_channels == cout and _pair(m.kernel_size) == (k, k)
+          and _pair(m.stride) == (stride, stride) and _pair(m.padding) == (pad, pad) and _pair(m.dilation) == (1, 1)
+          and m.groups == 1 and (m.bias is not None) == bias and m.padding_mode == "zeros"
+          and (not transposed or _pair(m.output_padding) == (1, 1)))
+    if not ok:
+        _refuse(f"{where}: {m} (expected {cls.__name__}({cin}, {cout}, kernel_size={k}, stride={stride}, padding={pad}, bias={bias}))")
+    return [m.weight] + ([m.bias] if bias else [])
+
+
+def _check_gn(m, where, groups, C, eps_seen):
+    if type(m) is torch.nn.BatchNorm2d:
+        _refuse(f'{where}: norm="batch" (BatchNorm2d)')
+    if type(m) is not torch.nn.GroupNorm or m.num_groups != groups or m.num_channels != C or not m.affine:
+        _refuse(f"{where}: {m} (expected GroupNorm({groups}, {C}))")
+    eps_seen.add(float(m.eps))
+    return [m.weight, m.bias]
+
+
+def _conv_block_params(m, where, cin, cout, eps_seen):
+    """bn1, conv1, bn2, conv2, bn3, conv3 [, bn4, downsample convolution] of a ConvBlock (src/utils.py:416-474)."""
+    if type(m).__name__ != "ConvBlock":
+        _refuse(f"{where}: {type(m).__name__} where a ConvBlock is expected")
+    p, w = [], (cin, cout // 2, cout // 4)
+    outs = (cout // 2, cout // 4, cout // 4)
+    for i in range(3):
+        p += _check_gn(getattr(m, f"bn{i + 1}"), f"{where}.bn{i + 1}", min(32, w[i]), w[i], eps_seen)
+        p += _check_conv(getattr(m, f"conv{i + 1}"), f"{where}.conv{i + 1}", w[i], outs[i], 3, 1, 1, False)
+    if not isinstance(m.nl, torch.nn.ReLU):
+        _refuse(f"{where}.nl: {m.nl}")
+    if cin != cout:
+        ds = m.downsample
+        if ds is None or len(ds) != 3 or ds[0] is not m.bn4 or not isinstance(ds[1], torch.nn.ReLU):
+            _refuse(f"{where}.downsample: {ds}")
+        p += _check_gn(m.bn4, f"{where}.bn4", min(32, cin), cin, eps_seen)
+        p += _check_conv(ds[2], f"{where}.downsample[2]", cin, cout, 1, 1, 0, False)
+    elif m.downsample is not None:
+        _refuse(f"{where}.downsample: {m.downsample}")
+    return p
+
+
+def geo_params(module):
+    """(parameters in the order kpn_geo_encoder_pack_device takes them, out_ch, out_ch_hd, eps) of an HGFilterV2, after
+    checking its structure against what the kernels implement (NotImplementedError otherwise)."""
+    if type(module).__name__ != "HGFilterV2":
+        _refuse(f"{type(module).__name__} as geometry encoder (HGFilterV2 expected)")
+    if getattr(module, "n_stack", None) != 1:
+        _refuse(f"n_stack={getattr(module, 'n_stack', None)} (stacked hourglasses; n_stack=1 only)")
+    if getattr(module, "hd", False):
+        _refuse("hd=True")
+    known = {"nl", "unpack1", "conv_out", "conv1", "bn1", "conv2", "conv3", "conv4", "m0", "top_m_0", "conv_last0", "bn_end0", "l0"}
+    extra = [n for n, _ in module.named_children() if n not in known]
+    if extra or not all(hasattr(module, n) for n in known):
+        _refuse(f"an HGFilterV2 with the layers {sorted(extra) or sorted(known - {n for n, _ in module.named_children()})}")
+    eps = set()
+    p = _check_conv(module.conv1, "conv1", 3, 64, 7, 2, 3, True)
+    p += _check_gn(module.bn1, "bn1", 32, 64, eps)
+    p += _conv_block_params(module.conv2, "conv2", 64, 128, eps)
+    un = module.unpack1
+    if type(un).__name__ != "DeconvReLUGroup" or not isinstance(un.nl, torch.nn.ReLU):
+        _refuse(f"unpack1: {un}")
+    p += _check_conv(un.conv, "unpack1.conv", 128, 32, 3, 2, 1, False, transposed=True)
+    p += _check_gn(un.norm, "unpack1.norm", 32, 32, eps)
+    out_ch_hd = module.conv_out.out_channels
+    p += _check_conv(module.conv_out, "conv_out", 32, out_ch_hd, 5, 1, 2, True)
+    p += _conv_block_params(module.conv3, "conv3", 128, 128, eps)
+    p += _conv_block_params(module.conv4, "conv4", 128, 256, eps)
+    hg = module.m0
+    if type(hg).__name__ != "HourGlass" or hg.depth != 4 or hg.features != 256:
+        _refuse(f"m0: {type(hg).__name__}(depth={getattr(hg, 'depth', None)}, features={getattr(hg, 'features', None)}) (HourGlass(4, 256) only)")
+    names = [f"b{j}_{lv}" for lv in (4, 3, 2, 1) for j in (1, 2)] + ["b2_plus_1", "b3_1", "b3_2", "b3_3", "b3_4"]
+    if sorted(n for n, _ in hg.named_children()) != sorted(names):
+        _refuse(f"m0 with the layers {[n for n, _ in hg.named_children()]}")
+    for n in names:
+        p += _conv_block_params(getattr(hg, n), f"m0.{n}", 256, 256, eps)
+    p += _conv_block_params(module.top_m_0, "top_m_0", 256, 256, eps)
+    p += _check_conv(module.conv_last0, "conv_last0", 256, 256, 1, 1, 0, True)
+    p += _check_gn(module.bn_end0, "bn_end0", 32, 256, eps)
+    out_ch = module.l0.out_channels
+    p += _check_conv(module.l0, "l0", 256, out_ch, 1, 1, 0, True)
+    if len(eps) != 1:
+        _refuse(f"GroupNorm layers with different eps {sorted(eps)}")
+    return p, out_ch, out_ch_hd, eps.pop()
+
+
+def _check_in(m, where, C, eps_seen):
+    if type(m) is not torch.nn.InstanceNorm2d or m.affine or m.track_running_stats or m.num_features != C:
+        _refuse(f'{where}: {m} (a ResBlkEncoder with another norm than "instance")')
+    eps_seen.add(float(m.eps))
+
+
+def _check_pad(m, where, n):
+    if type(m) is not torch.nn.ReplicationPad2d or tuple(m.padding) != (n, n, n, n):
+        _refuse(f"{where}: {m} (expected ReplicationPad2d({n}))")
+
+
+def tex_params(module):
+    """(parameters in `layers` order, (ngf, n_downsample, n_blocks, n_upsample, out_ch), eps) of a ResBlkEncoder."""
+    if type(module).__name__ != "ResBlkEncoder":
+        _refuse(f"{type(module).__name__} as texture encoder (ResBlkEncoder expected)")
+    L = list(module.layers)
+    eps, p = set(), []
+    if len(L) < 4 or type(L[1]) is not torch.nn.Conv2d:
+        _refuse(f"a ResBlkEncoder starting with {L[:2]}")
+    ngf = L[1].out_channels
+    _check_pad(L[0], "layers.0", 3)
+    p += _check_conv(L[1], "layers.1", 3, ngf, 7, 1, 0, True)
+    _check_in(L[2], "layers.2", ngf, eps)
+    i, C, n_down, n_blocks, n_up = 4, ngf, 0, 0, 0
+    if not isinstance(L[3], torch.nn.ReLU):
+        _refuse(f"layers.3: {L[3]}")
+    while i + 2 < len(L) and type(L[i]) is torch.nn.Conv2d:
+        p += _check_conv(L[i], f"layers.{i}", C, 2 * C, 3, 2, 1, True)
+        C *= 2
+        _check_in(L[i + 1], f"layers.{i + 1}", C, eps)
+        if not isinstance(L[i + 2], torch.nn.ReLU):
+            _refuse(f"layers.{i + 2}: {L[i + 2]}")
+        i, n_down = i + 3, n_down + 1
+    while i < len(L) and type(L[i]).__name__ == "ResBlk":
+        b = list(L[i].layers)
+        if len(b) != 7 or not isinstance(b[3], torch.nn.ReLU):
+            _refuse(f"layers.{i}: a ResBlk with the layers {b}")
+        for j in (0, 4):
+            _check_pad(b[j], f"layers.{i}.layers.{j}", 1)
+            p += _check_conv(b[j + 1], f"layers.{i}.layers.{j + 1}", C, C, 3, 1, 0, True)
+            _check_in(b[j + 2], f"layers.{i}.layers.{j + 2}", C, eps)
+        i, n_blocks = i + 1, n_blocks + 1
+    while i + 2 < len(L) and type(L[i]) is torch.nn.ConvTranspose2d:
+        p += _check_conv(L[i], f"layers.{i}", C, C // 2, 3, 2, 1, True, transposed=True)
+        C //= 2
+        _check_in(L[i + 1], f"layers.{i + 1}", C, eps)
+        if not isinstance(L[i + 2], torch.nn.ReLU):
+            _refuse(f"layers.{i + 2}: {L[i + 2]}")
+        i, n_up = i + 3, n_up + 1
+    if n_up == 0 or i + 2 != len(L):
+        _refuse(f"a ResBlkEncoder whose layers continue with {L[i:i + 3]} (n_upsample=0 or unexpected layers)")
+    _check_pad(L[i], f"layers.{i}", 3)
+    out_ch = L[i + 1].out_channels
+    p += _check_conv(L[i + 1], f"layers.{i + 1}", C, out_ch, 7, 1, 0, True)
+    if len(eps) != 1:
+        _refuse(f"InstanceNorm2d layers with different eps {sorted(eps)}")
+    return p, (ngf, n_down, n_blocks, n_up, out_ch), eps.pop()
+
+
+def flat_plain(params, device=None):
+    return torch.cat([t.detach().reshape(-1).to(device=device or t.device, dtype=torch.float32) for t in params])
+
+
+class _NativeEncoder:
+    calls = 0      # native forward calls of all instances (the tests assert that a call was, or was not, served natively)
+
+    def packed_weights(self, device):
+        key = _version_key(self.params)
+        if key is None or key != self.key or self.packed is None or self.packed.device != device:
+            with torch.no_grad():
+                self.packed = self._pack(flat_plain(self.params, device=device))
+            self.key = key
+        return self.packed
+
+
+class NativeGeoEncoder(_NativeEncoder):
+    """``HGFilterV2.forward(2 * avg_pool2d^ds(im) - 1)`` of ``module`` through kpn_geo_encode."""
+
+    def __init__(self, module):
+        self.module = module
+        self.params, self.out_ch, self.out_ch_hd, self.eps = geo_params(module)
+        self.packed = self.key = None
+
+    def _pack(self, plain):
+        return ops.geo_encoder_pack(plain, self.out_ch, self.out_ch_hd)
+
+    def __call__(self, im, ds=0, want_stages=False):
+        """im: (V, 3, H, W) in [0, 1] -> [feat (V, out_ch, h/4, w/4), feat_hd (V, out_ch_hd, h, w)] (NCHW shapes, channels-last
+        memory), as HGFilterV2.forward returns them."""
+        type(self).calls += 1
+        if want_stages:
+            f, fhd, st = ops.geo_encode(im, self.packed_weights(im.device), ds, self.out_ch, self.out_ch_hd, self.eps, True)
+        else:
+            st = None
+            f, fhd = torch.ops.kpnerf.geo_encode(im, self.packed_weights(im.device), [int(ds), self.out_ch, self.out_ch_hd], self.eps)
+        out = [f.permute(0, 3, 1, 2), fhd.permute(0, 3, 1, 2)]
+        return (out, st) if want_stages else out
+
+
+class NativeTexEncoder(_NativeEncoder):
+    """``ResBlkEncoder.forward(2 * avg_pool2d^ds(im) - 1)`` of ``module`` through kpn_tex_encode."""
+
+    def __init__(self, module):
+        self.module = module
+        self.params, self.cfg, self.eps = tex_params(module)
+        self.packed = self.key = None
+
+    def _pack(self, plain):
+        return ops.tex_encoder_pack(plain, *self.cfg)
+
+    def __call__(self, im, ds=0, want_stages=False):
+        type(self).calls += 1
+        if want_stages:
+            f, st = ops.tex_encode(im, self.packed_weights(im.device), ds, *self.cfg, eps=self.eps, want_stages=True)
+        else:
+            st = None
+            f = torch.ops.kpnerf.tex_encode(im, self.packed_weights(im.device), [int(ds)] + list(self.cfg), self.eps)
+        out = f.permute(0, 3, 1, 2)
+        return (out, st) if want_stages else out
+
+
+def _served(net, enc, im):
+    no_grad = (not net.training) or (not torch.is_grad_enabled()) or not any(p.requires_grad for p in enc.params)
+    return (no_grad and isinstance(im, torch.Tensor) and ops._on_gpu(im) and im.dtype == torch.float32 and im.dim() in (4, 5)
+            and not (im.requires_grad and torch.is_grad_enabled()))
+
+
+def install_encoders(net, geo=True, tex=False):
+    """Serves ``net.attach_geo_feat`` / ``net.attach_tex_feat`` (src/model.py:653-680) natively when no gradient is needed;
+    the module's own forward (whatever was bound before, e.g. by ``dropin.install``) otherwise.  Returns ``net``."""
+    uninstall_encoders(net)
+    saved = {}
+    if geo:
+        enc = NativeGeoEncoder(net.geo_encoder)
+        prev = net.attach_geo_feat
+        saved["attach_geo_feat"] = net.__dict__.get("attach_geo_feat")
+
+        def attach_geo_feat(self, im, return_val=False):
+            im4 = im.view(-1, *im.shape[2:]) if isinstance(im, torch.Tensor) and im.dim() == 5 else im
+            if (not _served(self, enc, im4) or self.ds_geo > 1 or (im4.shape[-2] >> self.ds_geo) % 64
+                    or (im4.shape[-1] >> self.ds_geo) % 64):
+                return prev(im, return_val)
+            if not return_val:
+                self.im = im.clone()
+            self.feat_geo = enc(im4, ds=self.ds_geo)
+            st = self.__dict__.get("_kpnerf_state")
+            if st is not None and not return_val:
+                st.note_attached(im)
+            if return_val:
+                return self.feat_geo
+
+        net.attach_geo_feat = types.MethodType(attach_geo_feat, net)
+        net._kpnerf_native_geo = enc
+    if tex and getattr(net, "tex_encoder", None) is not None:
+        enct = NativeTexEncoder(net.tex_encoder)
+        prevt = net.attach_tex_feat
+        saved["attach_tex_feat"] = net.__dict__.get("attach_tex_feat")
+
+        def attach_tex_feat(self, im, return_val=False):
+            im4 = im.view(-1, *im.shape[2:]) if isinstance(im, torch.Tensor) and im.dim() == 5 else im
+            if not _served(self, enct, im4) or self.ds_tex > 1:
+                return prevt(im, return_val)
+            self.feat_tex = enct(im4, ds=self.ds_tex)
+            st = self.__dict__.get("_kpnerf_state")
+            if st is not None and not return_val:
+                st.note_attached_tex(im)
+            if return_val:
+                return self.feat_tex
+
+        net.attach_tex_feat = types.MethodType(attach_tex_feat, net)
+        net._kpnerf_native_tex = enct
+    net._kpnerf_encoder_saved = saved
+    return net
+
+
+def uninstall_encoders(net):
+    saved = net.__dict__.pop("_kpnerf_encoder_saved", None)
+    if saved is not None:
+        for k, v in saved.items():
+            if v is None:
+                net.__dict__.pop(k, None)
+            else:
+                net.__dict__[k] = v
+    for k in ("_kpnerf_native_geo", "_kpnerf_native_tex"):
+        net.__dict__.pop(k, None)
+    return net

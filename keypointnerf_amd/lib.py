@@ -133,8 +133,22 @@ _SIGNATURES = {
     "kpn_vgg_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "kpn_vgg_stage_floats": (c_sz, [c_i32, c_i32, c_i32]),
     "kpn_vgg_loss": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_geo_encoder_plain_floats": (c_sz, [c_i32, c_i32]),
+    "kpn_geo_encoder_packed_floats": (c_sz, [c_i32, c_i32]),
+    "kpn_geo_encoder_pack_device": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_p]),
+    "kpn_geo_encoder_workspace_bytes": (c_sz, [c_i32] * 6),
+    "kpn_geo_encoder_stage_floats": (c_sz, [c_i32] * 6),
+    "kpn_geo_encoder_stage_info": (ctypes.c_int, [c_i32] * 7 + [ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32)]),
+    "kpn_geo_encode": (ctypes.c_int, [c_p] + [c_i32] * 6 + [c_p, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_tex_encoder_plain_floats": (c_sz, [c_i32] * 5),
+    "kpn_tex_encoder_packed_floats": (c_sz, [c_i32] * 5),
+    "kpn_tex_encoder_pack_device": (ctypes.c_int, [c_p, c_p] + [c_i32] * 5 + [c_p]),
+    "kpn_tex_encoder_workspace_bytes": (c_sz, [c_i32] * 9),
+    "kpn_tex_encoder_stage_floats": (c_sz, [c_i32] * 9),
+    "kpn_tex_encoder_stage_info": (ctypes.c_int, [c_i32] * 10 + [ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32)]),
+    "kpn_tex_encode": (ctypes.c_int, [c_p] + [c_i32] * 9 + [c_p, c_f, c_p, c_p, c_p, c_sz, c_p]),
 }
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class KpnError(RuntimeError):

@@ -659,3 +659,92 @@ def selftest_mfma():
     if rc != 0:
         print("selftest_mfma:", L.kpn_last_error().decode())
     return rc, err.value
+
+
+def _encoder_stages(info_fn, args, flat):
+    """{name: (V, H, W, C) view} of a stage buffer, from kpn_*_encoder_stage_info."""
+    out, name = {}, ctypes.create_string_buffer(64)
+    off, dims = ctypes.c_int64(0), (ctypes.c_int32 * 4)()
+    i = 0
+    while info_fn(*args, i, name, 64, ctypes.byref(off), dims) == 0:
+        n = dims[0] * dims[1] * dims[2] * dims[3]
+        out[name.value.decode()] = flat[off.value:off.value + n].reshape(*dims)
+        i += 1
+    return out
+
+
+def geo_encoder_pack(plain, out_ch, out_ch_hd=8):
+    """Packs the parameters of an HGFilterV2 (flat device fp32 in the order of include/kpnerf.h; encoders.flat_plain(encoders.geo_params(module)[0]))
+    into the layout kpn_geo_encode reads (reference src/utils.py:313-414)."""
+    L = kl.get_library()
+    w = _dev(plain, "plain").reshape(-1)
+    want = L.kpn_geo_encoder_plain_floats(out_ch, out_ch_hd)
+    if w.numel() != want or want == 0:
+        raise ValueError(f"expected {want} geometry encoder parameters, got {w.numel()}")
+    packed = torch.empty(L.kpn_geo_encoder_packed_floats(out_ch, out_ch_hd), dtype=_f32, device=w.device)
+    L.check(L.kpn_geo_encoder_pack_device(_p(w), _p(packed), out_ch, out_ch_hd, _stream()))
+    return packed
+
+
+def geo_encode(img, packed, ds=1, out_ch=64, out_ch_hd=8, eps=1e-5, want_stages=False):
+    """HGFilterV2.forward(2 * avg_pool2d^ds(img) - 1) as attach_geo_feat calls it (reference src/model.py:653-666,
+    src/utils.py:370-414; n_stack = 1, hd = False, norm = "group").  img: (V, 3, H, W) device fp32 in [0, 1].  Returns
+    (feat (V, h/4, w/4, out_ch), feat_hd (V, h, w, out_ch_hd), stages or None), channels-last (NHWC), h = H >> ds.
+    Forward only: raises on an input that requires a gradient."""
+    L = kl.get_library()
+    if isinstance(img, torch.Tensor) and img.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("geo_encode has no backward: the native encoders are forward only")
+    a = _dev(img, "img")
+    if a.dim() != 4 or a.shape[1] != 3:
+        raise ValueError(f"img must be (V, 3, H, W), got {tuple(a.shape)}")
+    V, _, H, W = a.shape
+    args = (V, H, W, int(ds), int(out_ch), int(out_ch_hd))
+    nb = L.kpn_geo_encoder_workspace_bytes(*args)
+    if nb == 0:
+        raise ValueError(f"the geometry encoder needs a network input whose height and width are multiples of 64 (got {H >> ds} x {W >> ds})")
+    h, w = H >> ds, W >> ds
+    feat = torch.empty(V, h // 4, w // 4, out_ch, dtype=_f32, device=a.device)
+    feat_hd = torch.empty(V, h, w, out_ch_hd, dtype=_f32, device=a.device)
+    st = torch.empty(L.kpn_geo_encoder_stage_floats(*args), dtype=_f32, device=a.device) if want_stages else None
+    ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
+    L.check(L.kpn_geo_encode(_p(a), *args, _p(packed), float(eps), _p(feat), _p(feat_hd), _p(st), _p(ws), nb, _stream()))
+    return feat, feat_hd, (_encoder_stages(L.kpn_geo_encoder_stage_info, args, st) if want_stages else None)
+
+
+def tex_encoder_pack(plain, ngf=64, n_downsample=3, n_blocks=4, n_upsample=2, out_ch=8):
+    """Packs the parameters of a ResBlkEncoder (flat device fp32: each convolution's weight then bias, in `layers` order;
+    encoders.flat_plain(encoders.tex_params(module)[0])) into the layout kpn_tex_encode reads (reference src/utils.py:216-247)."""
+    L = kl.get_library()
+    cfg = (int(ngf), int(n_downsample), int(n_blocks), int(n_upsample), int(out_ch))
+    w = _dev(plain, "plain").reshape(-1)
+    want = L.kpn_tex_encoder_plain_floats(*cfg)
+    if w.numel() != want or want == 0:
+        raise ValueError(f"expected {want} texture encoder parameters, got {w.numel()}")
+    packed = torch.empty(L.kpn_tex_encoder_packed_floats(*cfg), dtype=_f32, device=w.device)
+    L.check(L.kpn_tex_encoder_pack_device(_p(w), _p(packed), *cfg, _stream()))
+    return packed
+
+
+def tex_encode(img, packed, ds=1, ngf=64, n_downsample=3, n_blocks=4, n_upsample=2, out_ch=8, eps=1e-5, want_stages=False):
+    """ResBlkEncoder.forward(2 * avg_pool2d^ds(img) - 1) as attach_tex_feat calls it (reference src/model.py:668-680,
+    src/utils.py:216-247; norm = "instance").  Returns (feat (V, ht, wt, out_ch) channels-last, stages or None).
+    Forward only: raises on an input that requires a gradient."""
+    L = kl.get_library()
+    if isinstance(img, torch.Tensor) and img.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("tex_encode has no backward: the native encoders are forward only")
+    a = _dev(img, "img")
+    if a.dim() != 4 or a.shape[1] != 3:
+        raise ValueError(f"img must be (V, 3, H, W), got {tuple(a.shape)}")
+    V, _, H, W = a.shape
+    args = (V, H, W, int(ds), int(ngf), int(n_downsample), int(n_blocks), int(n_upsample), int(out_ch))
+    nb = L.kpn_tex_encoder_workspace_bytes(*args)
+    if nb == 0:
+        raise ValueError(f"texture encoder: unsupported size or arguments {args}")
+    h, w = H >> ds, W >> ds
+    for _ in range(n_downsample):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    feat = torch.empty(V, h << n_upsample, w << n_upsample, out_ch, dtype=_f32, device=a.device)
+    st = torch.empty(L.kpn_tex_encoder_stage_floats(*args), dtype=_f32, device=a.device) if want_stages else None
+    ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
+    L.check(L.kpn_tex_encode(_p(a), *args, _p(packed), float(eps), _p(feat), _p(st), _p(ws), nb, _stream()))
+    return feat, (_encoder_stages(L.kpn_tex_encoder_stage_info, args, st) if want_stages else None)

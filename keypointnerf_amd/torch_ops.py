@@ -22,6 +22,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.pix_l1_loss(src, tar, lam) -> (loss, d loss / d src)   the L1 terms of the training loss, DIFFERENTIABLE
     torch.ops.kpnerf.vgg_loss(x, y, packed, consts, lam) -> (loss, d loss / d x)   the perceptual term, DIFFERENTIABLE w.r.t. x
 
+    torch.ops.kpnerf.geo_encode(img, packed, [ds, out_ch, out_ch_hd], eps) -> (feat, feat_hd)   the geometry encoder, channels-last,
+    torch.ops.kpnerf.tex_encode(img, packed, [ds, ngf, n_down, n_blocks, n_up, out_ch], eps) -> feat   the texture encoder; FORWARD ONLY
+
 ``rgba2out`` and ``render_rays_train`` carry ``register_autograd`` formulas whose backward is itself a registered op
 (``kpnerf::rgba2out_backward``, ``kpnerf::render_rays_train_backward`` = kpn_render_rays_train_backward): gradients reach
 the flat effective-parameter vector ``plain`` (and from there ``weight_g`` / ``weight_v`` / ``bias`` / ``ani_al`` through
@@ -341,3 +344,49 @@ def _vgg_bwd(ctx, d_loss, _d_grad):
 
 
 vgg_loss.register_autograd(_vgg_bwd, setup_context=_vgg_setup)
+
+
+def _encoder_no_autograd(ctx, inputs, output):
+    raise RuntimeError("kpnerf::geo_encode / kpnerf::tex_encode are forward only: an input requires a gradient "
+                       "(training runs the caller's encoder modules)")
+
+
+def _encoder_bwd(ctx, *grads):
+    raise RuntimeError("kpnerf::geo_encode / kpnerf::tex_encode have no backward")
+
+
+@_lib.custom_op("kpnerf::geo_encode", mutates_args=(), device_types="cuda")
+def geo_encode(img: torch.Tensor, packed: torch.Tensor, cfg: List[int], eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HGFilterV2.forward(2 * avg_pool2d^ds(img) - 1) (reference src/utils.py:370-414, src/model.py:653-666; kpn_geo_encode).
+    cfg = [ds, out_ch, out_ch_hd]; packed = ops.geo_encoder_pack(...).  Returns channels-last (V, h/4, w/4, out_ch) and
+    (V, h, w, out_ch_hd).  No autograd formula: raises on inputs that require a gradient."""
+    f, fhd, _ = ops.geo_encode(img, packed, cfg[0], cfg[1], cfg[2], eps)
+    return f, fhd
+
+
+@geo_encode.register_fake
+def _(img, packed, cfg, eps):
+    V, h, w = img.shape[0], img.shape[2] >> cfg[0], img.shape[3] >> cfg[0]
+    return img.new_empty(V, h // 4, w // 4, cfg[1]), img.new_empty(V, h, w, cfg[2])
+
+
+geo_encode.register_autograd(_encoder_bwd, setup_context=_encoder_no_autograd)
+
+
+@_lib.custom_op("kpnerf::tex_encode", mutates_args=(), device_types="cuda")
+def tex_encode(img: torch.Tensor, packed: torch.Tensor, cfg: List[int], eps: float) -> torch.Tensor:
+    """ResBlkEncoder.forward(2 * avg_pool2d^ds(img) - 1) (reference src/utils.py:216-247, src/model.py:668-680; kpn_tex_encode).
+    cfg = [ds, ngf, n_downsample, n_blocks, n_upsample, out_ch]; packed = ops.tex_encoder_pack(...).  Returns channels-last
+    (V, ht, wt, out_ch).  No autograd formula: raises on inputs that require a gradient."""
+    return ops.tex_encode(img, packed, cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], cfg[5], eps)[0]
+
+
+@tex_encode.register_fake
+def _(img, packed, cfg, eps):
+    h, w = img.shape[2] >> cfg[0], img.shape[3] >> cfg[0]
+    for _ in range(cfg[2]):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return img.new_empty(img.shape[0], h << cfg[4], w << cfg[4], cfg[5])
+
+
+tex_encode.register_autograd(_encoder_bwd, setup_context=_encoder_no_autograd)

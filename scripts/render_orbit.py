@@ -26,6 +26,11 @@ def main():
     ap.add_argument("--views", type=int, default=3)
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--save", default="")
+    ap.add_argument("--exact-encoders", action="store_true",
+                    help="with --with-encoders: the two networks layer for layer (tests/encoder_golden.py) on PyTorch / MIOpen")
+    ap.add_argument("--native-encoders", nargs="?", const="geo", choices=("geo", "both"), default=None,
+                    help="with --with-encoders: the same networks through the native encoders (keypointnerf_amd/encoders.py): the "
+                         "geometry encoder (what install_encoders does by default) or both")
     ap.add_argument("--with-encoders", action="store_true",
                     help="every frame is a new source set, as in render_video_zju: run both image encoders (cost-equivalent stand-ins of "
                          "the reference's 28 M parameters, scripts/encoder_standin.py) on the 3 x 512^2 sources and prepare the scene from "
@@ -58,13 +63,22 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import encoder_standin
         enc = (encoder_standin.GeoEncoder().cuda().eval(), encoder_standin.TexEncoder().cuda().eval())
+        encode = lambda img: encoder_standin.encode(enc[0], enc[1], img)                       # noqa: E731
+        if args.exact_encoders or args.native_encoders:
+            # the two networks layer for layer (tests/encoder_golden.py) instead of the cost-equivalent stand-ins
+            from keypointnerf_amd import encoders as kenc
+            from tests import encoder_golden as eg
+            enc = (eg.stand_in_geo(1).cuda(), eg.stand_in_tex(2).cuda())
+            geo = kenc.NativeGeoEncoder(enc[0]) if args.native_encoders else (lambda im, ds: enc[0](eg.net_input(im, ds)))
+            tex = kenc.NativeTexEncoder(enc[1]) if args.native_encoders == "both" else (lambda im, ds: enc[1](eg.net_input(im, ds)))
+            encode = lambda img: (geo(img, ds=1), tex(img, ds=1))                              # noqa: E731
 
     def render_frame(i):
         cam = cam_tars[i % 90]                                                      # camera = orbit[frame_index % 90], :214
         scene_i = ps
         if enc is not None:
             with torch.no_grad():
-                feat_geo, feat_tex = encoder_standin.encode(enc[0], enc[1], scene["img"])
+                feat_geo, feat_tex = encode(scene["img"])
             scene_i = ops.PreparedScene(scene["img"], scene["cam"], feat_geo, feat_tex, scene["sp_data"], scene["src_foreground_mask"])
         out = ops.render_rays(scene_i, w, cam, scene["bounds"], plan=plan)
         return ops.frame_to_rgb8(out["tex_fg_fine"]).permute(2, 0, 1).contiguous()  # (3,H,W) uint8, what the gather moves
