@@ -27,7 +27,7 @@ def needs_build():
     # compiles its own -S when the files are absent)
     if not os.path.exists(OUT):
         return True
-    # every file under csrc/ is part of the one translation unit kpn_api.hip (it #includes the other .hip files)
+    # every file under csrc/ is part of a translation unit: kpn_api.hip #includes the kernel files and the host parts (api_*.hip)
     deps = [os.path.join(CSRC, s) for s in sorted(os.listdir(CSRC)) if s.endswith((".hip", ".h"))]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "kpnerf.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps)

@@ -385,10 +385,7 @@ __global__ __launch_bounds__(256, KPN_BWD_OCC) void k_geo_rows_bwd(kpn_scene_dev
 
 // ---------------------------------------------------------------------------------------------
 // Weight gradient  dW[o][colmap(c)] = sum_row dY[row][o] * X[row][c],  db[o] = sum_row dY[row][o].
-// The sum over rows is the K dimension of the MFMA: lane l supplies row 2s + (l>>5) of K-step s.  A lane
-// loads MV consecutive features of dY (16 B for MV = 4) and 2 consecutive columns of X per K-step and feeds
-// MV x 2 tiles: tile (a, b) holds output feature MV*i + a (A lane i) x column c0 + 2*j + b (B lane j) — the
-// strided labelling makes the vector loads the operands of several MFMAs at once (8 MFMAs per 24 bytes).
+// The sum over rows is the K dimension of the MFMA (k_weight_grad below); a wave feeds MV x 2 tiles.
 // One launch serves several layers ("jobs", blockIdx.y): the small layers of the colour head would each fill a
 // fraction of the chip on their own.  grid (row workers, jobs); a workgroup = one row slice of one job, its waves =
 // the job's 64-column groups (dY is fetched from HBM once).  Every wave writes its partial tile block in raw
@@ -403,102 +400,17 @@ struct kpn_wgrad_job {
     int ldy, M, ldx, Kc;               // Kc: columns of X read (even)
     int Kt, in_dim, cmap, omap;        // reduce: real columns, row stride of dW, column / row maps
     int mv, which;                     // MV of the job (reduce), rows[which] = row count
-    int olab;                          // labelling of the partial tiles' output features: 0 = MV i + a (k_weight_grad_f32), 1 = 32 a + i
     int V; uint32_t keep;              // which == 0: row r belongs to view (r / 32) % V; rows of views whose keep bit is 0 (train-time
                                        // view dropout) count as zeros — their dumps are never written
 };
 struct kpn_wgrad_jobs { kpn_wgrad_job j[KPN_WGRAD_MAX_JOBS]; int n; };
 
-template <int MV>
-__global__ __launch_bounds__(256) void k_weight_grad_f32(kpn_wgrad_jobs jobs, const int64_t* __restrict__ rows_ptr) {
-    const kpn_wgrad_job& J = jobs.j[blockIdx.y];
-    const int z = threadIdx.x >> 6;
-    if (64 * z >= J.Kc) return;  // this job has fewer column groups than the launch's widest
-    const float* __restrict__ dY = J.dY;
-    const float* __restrict__ X = J.X;
-    const int ldy = J.ldy, M = J.M, ldx = J.ldx, Kc = J.Kc;
-    const int64_t rows = rows_ptr[J.which];
-    const int lane = threadIdx.x & 63, i = lane & 31, kk = lane >> 5;
-    const int worker = blockIdx.x, nworkers = gridDim.x;
-    const int c0 = z * 64;
-    const int64_t npairs = rows / 2;
-    int64_t per = (npairs + nworkers - 1) / nworkers;
-    per = (per + 3) / 4 * 4;  // whole groups of 4 K-steps
-    const int64_t pbeg = (int64_t)worker * per;
-    const int64_t pend = pbeg + per < npairs ? pbeg + per : npairs;
-    kpn_f32x16 acc[MV][2];
-#pragma unroll
-    for (int a = 0; a < MV; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    float bs[MV];
-#pragma unroll
-    for (int a = 0; a < MV; ++a) bs[a] = 0.0f;
-    const bool cok = c0 + 2 * i < Kc;  // Kc is even: both columns of the pair are in or out
-    constexpr int U = 4;               // K-steps per software-pipeline stage
-    float ya[2][U][MV];
-    float2 xb[2][U];
-    auto fetch = [&](int64_t pr, float (&y)[U][MV], float2 (&x)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t r = 2 * (pr + u) + kk;
-            const bool in = pr + u < pend && ((J.keep >> ((uint32_t)(r >> 5) % (uint32_t)J.V)) & 1u);
-            const bool yin = in && MV * i < M;  // M is a multiple of MV
-            if constexpr (MV == 4) {
-                float4 y4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (yin) y4 = *reinterpret_cast<const float4*>(dY + r * ldy + 4 * i);
-                y[u][0] = y4.x; y[u][1] = y4.y; y[u][2] = y4.z; y[u][3] = y4.w;
-            } else if constexpr (MV == 2) {
-                float2 y2 = make_float2(0.f, 0.f);
-                if (yin) y2 = *reinterpret_cast<const float2*>(dY + r * ldy + 2 * i);
-                y[u][0] = y2.x; y[u][1] = y2.y;
-            } else {
-                y[u][0] = yin ? dY[r * ldy + i] : 0.0f;
-            }
-            x[u] = make_float2(0.f, 0.f);
-            if (in && cok) x[u] = *reinterpret_cast<const float2*>(X + r * ldx + c0 + 2 * i);
-        }
-    };
-    auto consume = [&](const float (&y)[U][MV], const float2 (&x)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int a = 0; a < MV; ++a) {
-                bs[a] += y[u][a];
-                acc[a][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y[u][a], x[u].x, acc[a][0], 0, 0, 0);
-                acc[a][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y[u][a], x[u].y, acc[a][1], 0, 0, 0);
-            }
-    };
-    if (pbeg < pend) {
-        fetch(pbeg, ya[0], xb[0]);
-        for (int64_t pr = pbeg; pr < pend; pr += 2 * U) {
-            fetch(pr + U, ya[1], xb[1]);   // (reads nothing past pend)
-            consume(ya[0], xb[0]);
-            fetch(pr + 2 * U, ya[0], xb[0]);
-            consume(ya[1], xb[1]);
-        }
-    }
-    float* dst = J.partial + ((size_t)z * nworkers + worker) * (MV * 2 * 16 * 64) + lane;
-#pragma unroll
-    for (int a = 0; a < MV; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[((a * 2 + b) * 16 + r) * 64] = acc[a][b][r];
-    if (z == 0) {
-#pragma unroll
-        for (int a = 0; a < MV; ++a) J.dbp[((size_t)worker * MV + a) * 64 + lane] = bs[a];
-    }
-}
-
-// The default form (round 3): the same sum on v_mfma_f32_32x32x16_bf16 with every operand as three bf16 pieces and six products
+// The sum on v_mfma_f32_32x32x16_bf16 with every operand as three bf16 pieces and six products
 // (fp32-class, fp32's exponent range — gradients span too many decades for fp16 pieces): K = 16 rows per step, lane l supplies
-// rows 8 (l >> 5) + e of a step.  2.7x less matrix time than the fp32 form (48 MFMAs of 32 cycles per 16 rows against 64 of 64).
+// rows 8 (l >> 5) + e of a step.  2.7x less matrix time than on the fp32 MFMA (48 MFMAs of 32 cycles per 16 rows against 64 of 64).
 //
 // With the matrix time that small the kernel is bound by what feeds it, so the feeding is shared: a value of dY is split ONCE per
-// workgroup (the fp32 form and the first bf16 form split it in every wave, i.e. up to four times) — the wave that owns output
+// workgroup (not in every wave, i.e. up to four times) — the wave that owns output
 // block a loads dY[16 rows][32 a + i], splits it and parks the three pieces in LDS in operand order; after one barrier every
 // wave reads the MV blocks back (ds_read_b128) for its own 64 columns, whose X pieces never leave its registers.  Two LDS
 // stages: a stage is rewritten two steps later, behind the next step's barrier.  Waves beyond the job's column groups own
@@ -506,7 +418,7 @@ __global__ __launch_bounds__(256) void k_weight_grad_f32(kpn_wgrad_jobs jobs, co
 // (rows % 32 == 0), a lane beyond M or Kc re-reads the last valid feature / column pair (its tile rows / columns are never
 // read by the reduce), and the steps of a dropped view (never written) are skipped as a whole.  The barrier is s_barrier behind
 // s_waitcnt lgkmcnt(0) only: __syncthreads() would also drain the global loads of the next step, which are the point.
-//   labelling: tile (a, b) holds output feature 32 a + i (A lane i) x column c0 + 2 j + b (B lane j)   [olab = 1]
+//   labelling: tile (a, b) holds output feature 32 a + i (A lane i) x column c0 + 2 j + b (B lane j)
 #ifndef KPN_SIMT_EMU
 #define KPN_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #else
@@ -673,7 +585,7 @@ __global__ __launch_bounds__(256) void k_weight_grad_reduce(kpn_wgrad_jobs jobs,
     for (int k = 1; k < 8; ++k) s += red[k][el];
     if (e < TILE_E) {
         const int lane = e & 63, r = (e >> 6) & 15, ab = e >> 10, a = ab >> 1, b = ab & 1;
-        int o = J.olab ? 32 * a + KPN_ROWMAP(r, lane >> 5) : MV * KPN_ROWMAP(r, lane >> 5) + a;
+        int o = 32 * a + KPN_ROWMAP(r, lane >> 5);
         const int c = z * 64 + 2 * (lane & 31) + b;
         if (o < M && c < Kc) {
             const int f = kpn_grad_col(J.cmap, c);
@@ -682,7 +594,7 @@ __global__ __launch_bounds__(256) void k_weight_grad_reduce(kpn_wgrad_jobs jobs,
         }
     } else if (z == 0 && e < TILE_E + MV * 32) {
         const int q = e - TILE_E, a = q / 32, i = q % 32;
-        const int o = J.olab ? 32 * a + i : MV * i + a;
+        const int o = 32 * a + i;
         if (o < M) J.dB[J.omap ? kpn_xprime_to_orig(o) : o] += s;
     }
 }

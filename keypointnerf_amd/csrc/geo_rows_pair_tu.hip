@@ -7,7 +7,7 @@
 #include "kpn_field_shared.h"
 #include "geo_rows_pair_kernels.hip"
 
-// not part of the C ABI: called by run_field (kpn_api.hip) for rows modes 2 and 3
+// not part of the C ABI: called by run_field (api_field.hip) for rows modes 2 and 3
 extern "C" __attribute__((visibility("hidden"))) void kpn_internal_launch_geo_rows_pair(
     int mode, int blocks, void* stream, const kpn_scene_dev* sc, const kpn_points* ps, const float* wp, const int* list, const int* count,
     int* tickets, float* xscr, const kpn_batch* batch) {

@@ -222,7 +222,7 @@ struct kpn_scene_dev {
 // pass — the packed weights (the packers count the ones beyond it: kpn_pack_flags_off()) and the maps (kpn_scene_prepare's
 // max |value|) — is tested here, on the device, by the kernels themselves: no host round trip.  Activations are not known before
 // the pass: a non-finite result is caught behind the kernels (kpn_batch::bad) and the batch evaluated again by the fp32-range
-// kernels (run_field, kpn_api.hip).
+// kernels (run_field, api_field.hip).
 // products per term set of the two-fp16-piece kernels: 4 = hh hl lh ll, 3 = without ll (<= 2^-24 of the term).
 // Rows kernels (geo_rows_pair_kernels.hip): KPN_F16_PRODUCTS.  Per-point kernel (kpn_hlayer, kpn_device.h): KPN_FUSE_F16_PRODUCTS,
 // three as well — in the product order given there.
