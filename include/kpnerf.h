@@ -34,7 +34,9 @@ extern "C" {
  * kpn_vgg_workspace_bytes / kpn_vgg_stage_floats, kpn_vgg_loss (nothing of ABI 3 changed) */
 /* 5: additive - forward of the two image encoders: kpn_geo_encoder_* / kpn_geo_encode (HGFilterV2), kpn_tex_encoder_* /
  * kpn_tex_encode (ResBlkEncoder) (nothing of ABI 4 changed) */
-#define KPN_ABI_VERSION 5
+/* 6: additive - every pixel and mask term of the training loss in one launch: kpn_train_loss_args, kpn_train_loss_workspace_bytes,
+ * kpn_train_loss (nothing of ABI 5 changed; kpn_pix_l1_loss stays) */
+#define KPN_ABI_VERSION 6
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -309,6 +311,45 @@ int kpn_render_rays(const kpn_scene_desc* desc, const void* scene_ws, const floa
  * (the d_tex_fg / d_tex_fg_fine of kpn_render_grads).  scratch: 16,392 bytes as kpn_mse_psnr.  Deterministic. */
 int kpn_pix_l1_loss(const float* src, const float* tar, int64_t n, float lambda, float* loss, float* d_src, void* scratch,
                     void* stream);
+/* kpn_train_loss: every pixel and mask term of compute_error_nerf (src/utils.py:108-171) for the outputs the renderer produces
+ * (no auxiliary heads), values and seed gradients, in ONE launch:
+ *   terms[0] e_pix_c     = l1_c  * mean|tex - tar|                                   (src/utils.py:130-132, 179)
+ *   terms[1] e_pix_l1    = l1    * mean|tex_fine - tar|                              (src/utils.py:141, 179)
+ *   terms[2] e_pix_l2    = l2    * mean (tex_fine - tar)^2                           (src/utils.py:181)
+ *   terms[3] e_pix_lp    = lp    * mean (|tex_fine - tar| + 1e-4)^0.4                (src/utils.py:183)
+ *   terms[4] mask_loss_c = mloss * mean (clip(alpha, 1e-3, 1) - tar_alpha)^2         (src/utils.py:150-153)
+ *   terms[5] mask_loss_f = mloss * mean (clip(alpha_fine, 1e-3, 1) - tar_alpha)^2    (src/utils.py:155-158)
+ * tex, tex_fine, tar: 3n floats; alpha, alpha_fine, tar_alpha: n floats (batch 1).  A term whose weight is <= 0 or one of whose
+ * inputs is NULL is skipped: its slot is 0 and its gradient buffer is not touched.  Gradients are what torch autograd derives for
+ * an upstream gradient of 1 per term (any gradient pointer may be NULL: not written):
+ *   d_tex (3n) of terms[0];  d_tex_fine (3 x 3n): row k of terms[1 + k] (l1, l2, lp kept apart, so that a caller can scale each
+ *   by its own upstream gradient);  d_alpha (n) of terms[4];  d_alpha_fine (n) of terms[5].
+ * l1: lambda sign(d) / 3n (sign(0) = 0);  l2: 2 lambda d / 3n;  lp: 0.4 lambda (|d| + 1e-4)^-0.6 sign(d) / 3n;  mask: 2 lambda
+ * (c - t) / n where 1e-3 <= a <= 1 (both ends inclusive, torch's clamp backward) and 0 elsewhere; a NaN alpha makes its term NaN
+ * and has gradient 0, as in torch.  terms[0], terms[1], d_tex and row 0 of d_tex_fine are bit-identical to two kpn_pix_l1_loss
+ * calls.  Deterministic (per-block fp64 partial sums added in block order, no float atomics).
+ * workspace: kpn_train_loss_workspace_bytes(n) bytes (256-byte aligned); its first word is a ticket that has to be 0 on entry and that the kernel
+ * leaves at 0.  reset_ticket != 0 zeroes it first (one memset node) - pass it for the first call on a workspace of undefined
+ * contents; later calls on the same workspace (for the same or a smaller n) pass 0 and are a single launch.  Calls that share a
+ * workspace must be ordered (one stream). */
+typedef struct kpn_train_loss_args {
+    const float* tex;                 /* tex_cal (3n) or NULL */
+    const float* tex_fine;            /* tex_cal_fine (3n) or NULL */
+    const float* tar;                 /* tar_img (3n); may be NULL only if tex and tex_fine are */
+    const float* alpha;               /* (n) or NULL */
+    const float* alpha_fine;          /* (n) or NULL */
+    const float* tar_alpha;           /* (n) or NULL */
+    int64_t n;                        /* pixels */
+    float l1_c, l1, l2, lp, mloss;    /* lambda_l1_c, lambda_l1, lambda_l2, lambda_lp, lambda_mloss */
+    int32_t reset_ticket;
+    float* terms;                     /* 6 floats */
+    float* d_tex;                     /* 3n or NULL */
+    float* d_tex_fine;                /* 3 x 3n or NULL */
+    float* d_alpha;                   /* n or NULL */
+    float* d_alpha_fine;              /* n or NULL */
+} kpn_train_loss_args;
+size_t kpn_train_loss_workspace_bytes(int64_t n);
+int kpn_train_loss(const kpn_train_loss_args* args, void* workspace, void* stream);
 int kpn_frame_to_rgb8(const float* chw, int32_t height, int32_t width, int32_t bgr, uint8_t* hwc_out, void* stream);
 int kpn_mse_psnr(const float* pred, const float* gt, int64_t n, double* out2, void* scratch, void* stream);
 /* kpn_ssim: ZJUEvaluator._compute_ssim (src/zju_evaluator.py:21-45) = skimage 0.19 (environment.yml:135)

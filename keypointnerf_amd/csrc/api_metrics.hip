@@ -31,6 +31,30 @@ extern "C" int kpn_pix_l1_loss(const float* src, const float* tar, int64_t n, fl
     return check_launch("kpn_pix_l1_loss");
 }
 
+// compute_error_nerf's pixel and mask terms (reference src/utils.py:108-171, pix_loss :173-183) in one launch: k_train_loss
+// (loss_kernels.hip).  The grid rule is kpn_pix_l1_loss's, over the 3n pixel elements, so that the L1 terms add up in the same order.
+static int64_t train_loss_blocks(int64_t n) {
+    const int64_t blocks = (3 * n + 255) / 256;
+    return blocks > 2048 ? 2048 : blocks;
+}
+extern "C" size_t kpn_train_loss_workspace_bytes(int64_t n) {
+    if (n <= 0 || n > (int64_t)1 << 40) return 0;
+    return 256 + align_up((size_t)train_loss_blocks(n) * 6 * sizeof(double), 256);
+}
+extern "C" int kpn_train_loss(const kpn_train_loss_args* args, void* workspace, void* stream) {
+    KPN_REQUIRE(args && workspace && args->terms, "null pointer");
+    KPN_REQUIRE(args->n > 0 && args->n <= (int64_t)1 << 40, "bad pixel count");
+    KPN_REQUIRE(args->tar || (!args->tex && !args->tex_fine), "tex / tex_fine need tar");
+    kpn_loss_kargs k;
+    k.a = *args;
+    const int64_t blocks = train_loss_blocks(args->n);
+    k.ticket = static_cast<int*>(workspace);                          // first, so that a workspace serves any smaller n as well
+    k.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + 256);
+    if (args->reset_ticket) (void)hipMemsetAsync(k.ticket, 0, sizeof(int), (hipStream_t)stream);
+    KPN_LAUNCH(k_train_loss, dim3((unsigned)blocks), dim3(256), stream, k);
+    return check_launch("kpn_train_loss");
+}
+
 extern "C" size_t kpn_ssim_scratch_bytes(int32_t w, int32_t h) {
     if (w < 7 || h < 7) return 0;
     return align_up((size_t)5 * 3 * (h - 6) * w * sizeof(float), 256) + 2048 * sizeof(double) + 256;

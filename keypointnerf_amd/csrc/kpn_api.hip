@@ -30,6 +30,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "fuse_bwd_kernels.hip"
 #include "vgg_kernels.hip"
 #include "encoder_kernels.hip"
+#include "loss_kernels.hip"
 
 // host parts
 #include "api_common.h"

@@ -53,6 +53,13 @@ class TrainArgs(ctypes.Structure):
                [("keep_coarse", ctypes.c_uint32), ("keep_fine", ctypes.c_uint32), ("rand_noise_std", c_f)]
 
 
+class TrainLossArgs(ctypes.Structure):
+    """struct kpn_train_loss_args"""
+    _fields_ = [(n, c_p) for n in ("tex", "tex_fine", "tar", "alpha", "alpha_fine", "tar_alpha")] + [("n", c_i64)] + \
+               [(n, c_f) for n in ("l1_c", "l1", "l2", "lp", "mloss")] + [("reset_ticket", c_i32)] + \
+               [(n, c_p) for n in ("terms", "d_tex", "d_tex_fine", "d_alpha", "d_alpha_fine")]
+
+
 class RenderGrads(ctypes.Structure):
     """struct kpn_render_grads"""
     _fields_ = [(n, c_p) for n in ("d_tex_fg", "d_depth", "d_alpha", "d_tex_fg_fine", "d_depth_fine", "d_alpha_fine", "d_sdf")]
@@ -121,6 +128,8 @@ _SIGNATURES = {
                                                            ctypes.POINTER(TrainArgs), ctypes.POINTER(RenderGrads), c_p, c_p, c_p, c_p,
                                                            c_p, c_sz, c_p, c_sz, c_p]),
     "kpn_pix_l1_loss": (ctypes.c_int, [c_p, c_p, ctypes.c_int64, ctypes.c_float, c_p, c_p, c_p, c_p]),
+    "kpn_train_loss_workspace_bytes": (c_sz, [c_i64]),
+    "kpn_train_loss": (ctypes.c_int, [ctypes.POINTER(TrainLossArgs), c_p, c_p]),
     "kpn_profile_collect": (ctypes.c_int, [c_p, c_p, c_p]),
     "kpn_profile_collect2": (ctypes.c_int, [c_p, c_p, c_p, c_p]),
     "kpn_profile_collect3": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
@@ -148,7 +157,7 @@ _SIGNATURES = {
     "kpn_tex_encoder_stage_info": (ctypes.c_int, [c_i32] * 10 + [ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32)]),
     "kpn_tex_encode": (ctypes.c_int, [c_p] + [c_i32] * 9 + [c_p, c_f, c_p, c_p, c_p, c_sz, c_p]),
 }
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class KpnError(RuntimeError):

@@ -589,6 +589,55 @@ def pix_l1_loss(src, tar, lam, want_grad=True):
     return loss.reshape(()), d
 
 
+_TRAIN_LOSS_WS = {}   # (device, stream handle) -> workspace whose ticket the kernel has left at zero
+
+
+def train_loss(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights, want_grad=True):
+    """The pixel and mask terms of compute_error_nerf (reference src/utils.py:108-171) and their seed gradients in one launch
+    (kpn_train_loss).  tex / tex_fine / tar: 3n floats, alpha / alpha_fine / tar_alpha: n floats, any but tar may be None;
+    weights = (lambda_l1_c, lambda_l1, lambda_l2, lambda_lp, lambda_mloss).  Returns (terms (6,): e_pix_c, e_pix_l1, e_pix_l2,
+    e_pix_lp, mask_loss_c, mask_loss_f, already weighted; d_tex like tex; d_tex_fine (3, *tex_fine.shape): the l1 / l2 / lp
+    gradients apart; d_alpha; d_alpha_fine) — a gradient is None without its input or with want_grad=False, and the part of a
+    skipped term (weight <= 0, missing input) is left UNWRITTEN."""
+    L = kl.get_library()
+    t = _dev(tar, "tar")
+    if t.numel() == 0 or t.numel() % 3:
+        raise ValueError("tar must hold 3 n floats")
+    n = t.numel() // 3
+    ins = [None if v is None else _dev(v, name) for v, name in ((tex, "tex"), (tex_fine, "tex_fine"), (alpha, "alpha"),
+                                                                (alpha_fine, "alpha_fine"), (tar_alpha, "tar_alpha"))]
+    for v, name, want in zip(ins, ("tex", "tex_fine", "alpha", "alpha_fine", "tar_alpha"), (3 * n, 3 * n, n, n, n)):
+        if v is not None and v.numel() != want:
+            raise ValueError(f"{name} has {v.numel()} elements, expected {want}")
+    x, xf, a, af, ta = ins
+    if len(weights) != 5:
+        raise ValueError("weights = (l1_c, l1, l2, lp, mloss)")
+    terms = torch.empty(6, dtype=_f32, device=t.device)
+    g = lambda v, *lead: torch.empty(*lead, *v.shape, dtype=_f32, device=t.device) if (want_grad and v is not None) else None
+    d_x, d_xf, d_a, d_af = g(x), g(xf, 3), g(a), g(af)
+    stream = _stream()
+    # the kernel leaves its ticket at zero, so a workspace is zeroed only before its first use; per stream, because calls that
+    # share one must be ordered.  Under graph capture the workspace is the capture's own (the pool's memory is not ours to keep).
+    capturing = t.is_cuda and torch.cuda.is_current_stream_capturing()
+    key = (t.device, 0 if stream is None else (stream.value or 0))     # c_void_p(0).value is None: the default stream is 0
+    ws = None if capturing else _TRAIN_LOSS_WS.get(key)
+    nb = L.kpn_train_loss_workspace_bytes(n)
+    fresh = ws is None or ws.numel() < nb
+    if fresh:
+        ws = torch.empty(nb, dtype=torch.uint8, device=t.device)
+    args = kl.TrainLossArgs(tex=_p(x), tex_fine=_p(xf), tar=_p(t), alpha=_p(a), alpha_fine=_p(af), tar_alpha=_p(ta), n=n,
+                            l1_c=float(weights[0]), l1=float(weights[1]), l2=float(weights[2]), lp=float(weights[3]),
+                            mloss=float(weights[4]), reset_ticket=int(fresh), terms=_p(terms), d_tex=_p(d_x), d_tex_fine=_p(d_xf),
+                            d_alpha=_p(d_a), d_alpha_fine=_p(d_af))
+    rc = L.kpn_train_loss(ctypes.byref(args), _p(ws), stream)
+    if rc != 0:
+        _TRAIN_LOSS_WS.pop(key, None)
+    L.check(rc)
+    if not capturing:
+        _TRAIN_LOSS_WS[key] = ws
+    return terms, d_x, d_xf, d_a, d_af
+
+
 def vgg_pack(plain):
     """Packs the nine convolutions of vgg19.features[0:21] (flat device fp32: each OIHW weight then its bias, in features
     order; vgg.plain_from_module) on the device into the layout kpn_vgg_loss reads (reference src/utils.py:750-805)."""

@@ -21,6 +21,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 
     torch.ops.kpnerf.pix_l1_loss(src, tar, lam) -> (loss, d loss / d src)   the L1 terms of the training loss, DIFFERENTIABLE
     torch.ops.kpnerf.vgg_loss(x, y, packed, consts, lam) -> (loss, d loss / d x)   the perceptual term, DIFFERENTIABLE w.r.t. x
+    torch.ops.kpnerf.train_loss(tex?, tex_fine?, tar, alpha?, alpha_fine?, tar_alpha?, [l1_c, l1, l2, lp, mloss])
+                                 -> (terms (6,), d_tex, d_tex_fine (3, ...), d_alpha, d_alpha_fine)   every pixel and mask term of
+                                 the training loss in one launch, DIFFERENTIABLE w.r.t. tex, tex_fine, alpha, alpha_fine
 
     torch.ops.kpnerf.geo_encode(img, packed, [ds, out_ch, out_ch_hd], eps) -> (feat, feat_hd)   the geometry encoder, channels-last,
     torch.ops.kpnerf.tex_encode(img, packed, [ds, ngf, n_down, n_blocks, n_up, out_ch], eps) -> feat   the texture encoder; FORWARD ONLY
@@ -319,6 +322,56 @@ def _l1_bwd(ctx, d_loss, _d_grad):
 
 
 pix_l1_loss.register_autograd(_l1_bwd, setup_context=_l1_setup)
+
+
+@_lib.custom_op("kpnerf::train_loss", mutates_args=(), device_types="cuda")
+def train_loss(tex: Optional[torch.Tensor], tex_fine: Optional[torch.Tensor], tar: torch.Tensor, alpha: Optional[torch.Tensor],
+               alpha_fine: Optional[torch.Tensor], tar_alpha: Optional[torch.Tensor], weights: List[float]
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The pixel and mask terms of compute_error_nerf (reference src/utils.py:108-171; kpn_train_loss), weights = [lambda_l1_c,
+    lambda_l1, lambda_l2, lambda_lp, lambda_mloss]: terms (6,) = e_pix_c, e_pix_l1, e_pix_l2, e_pix_lp, mask_loss_c, mask_loss_f
+    (0 for a term that is switched off or lacks an input) and the seed gradients autograd derives for them — d_tex, d_tex_fine
+    (3, ...: l1 / l2 / lp apart), d_alpha, d_alpha_fine; an absent input's gradient is an empty tensor, a skipped term's part is
+    uninitialised.  Differentiable w.r.t. tex, tex_fine, alpha, alpha_fine; the backward launches no kernel of the library."""
+    terms, d_x, d_xf, d_a, d_af = ops.train_loss(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights, want_grad=True)
+    none = lambda v: terms.new_empty(0) if v is None else v
+    return terms, none(d_x), none(d_xf), none(d_a), none(d_af)
+
+
+@train_loss.register_fake
+def _(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights):
+    like = lambda v, *lead: tar.new_empty(0) if v is None else tar.new_empty(*lead, *v.shape)
+    return tar.new_empty(6), like(tex), like(tex_fine, 3), like(alpha), like(alpha_fine)
+
+
+def _train_loss_active(inputs):
+    """which of the six terms the kernel evaluated (kpn_train_loss's rule: weight > 0 and every input present)"""
+    tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, w = inputs
+    return (tex is not None and w[0] > 0.0, tex_fine is not None and w[1] > 0.0, tex_fine is not None and w[2] > 0.0,
+            tex_fine is not None and w[3] > 0.0, alpha is not None and tar_alpha is not None and w[4] > 0.0,
+            alpha_fine is not None and tar_alpha is not None and w[4] > 0.0)
+
+
+def _train_loss_setup(ctx, inputs, output):
+    ctx.active = _train_loss_active(inputs)
+    ctx.save_for_backward(*output[1:])
+
+
+def _train_loss_bwd(ctx, d_terms, *_d_grads):
+    d_x, d_xf, d_a, d_af = ctx.saved_tensors
+    on = ctx.active
+    g = d_terms.unbind(0)
+    g_x = d_x * g[0] if on[0] else None
+    g_xf = None
+    for k in range(3):                                   # the three fine pixel terms, each by its own upstream gradient
+        if on[1 + k]:
+            g_xf = d_xf[k] * g[1 + k] if g_xf is None else torch.addcmul(g_xf, d_xf[k], g[1 + k])
+    g_a = d_a * g[4] if on[4] else None
+    g_af = d_af * g[5] if on[5] else None
+    return g_x, g_xf, None, g_a, g_af, None, None
+
+
+train_loss.register_autograd(_train_loss_bwd, setup_context=_train_loss_setup)
 
 
 @_lib.custom_op("kpnerf::vgg_loss", mutates_args=(), device_types="cuda")
