@@ -17,6 +17,14 @@ struct Carver {
     size_t o = 0;
     size_t take(size_t n, size_t align = 256) { const size_t r = o; o += align_up(n, align); return r; }
 };
+// The grid and the scratch of the deterministic fp64 reductions (kpn_reduce.h; kpn_mse_psnr, kpn_pix_l1_loss, kpn_ssim and, for the
+// grid, kpn_train_loss): at most 2048 blocks of 256 threads, and 16,392 bytes holding the blocks' partials and then the ticket.
+static inline int64_t reduce_blocks(int64_t n) { return std::min<int64_t>((n + 255) / 256, 2048); }
+struct ReduceScratch { double* partial; int* ticket; };
+static inline ReduceScratch reduce_scratch(void* scratch) {
+    double* partial = static_cast<double*>(scratch);
+    return {partial, reinterpret_cast<int*>(partial + 2048)};
+}
 namespace {
 bool stream_is_capturing(void* stream) {
 #ifndef KPN_SIMT_EMU

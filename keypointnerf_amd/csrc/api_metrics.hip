@@ -9,12 +9,9 @@ extern "C" int kpn_frame_to_rgb8(const float* chw, int32_t H, int32_t W, int32_t
 extern "C" int kpn_mse_psnr(const float* pred, const float* gt, int64_t n, double* out2, void* scratch, void* stream) {
     KPN_REQUIRE(pred && gt && out2 && scratch, "null pointer");
     KPN_REQUIRE(n > 0, "empty image");
-    double* partial = static_cast<double*>(scratch);
-    int* ticket = reinterpret_cast<int*>(partial + 2048);
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    (void)hipMemsetAsync(ticket, 0, sizeof(int), (hipStream_t)stream);
-    KPN_LAUNCH(k_mse_psnr, dim3((unsigned)blocks), dim3(256), stream, n, pred, gt, partial, ticket, out2);
+    const ReduceScratch r = reduce_scratch(scratch);
+    (void)hipMemsetAsync(r.ticket, 0, sizeof(int), (hipStream_t)stream);
+    KPN_LAUNCH(k_mse_psnr, dim3((unsigned)reduce_blocks(n)), dim3(256), stream, n, pred, gt, r.partial, r.ticket, out2);
     return check_launch("kpn_mse_psnr");
 }
 
@@ -22,21 +19,15 @@ extern "C" int kpn_pix_l1_loss(const float* src, const float* tar, int64_t n, fl
                                void* stream) {
     KPN_REQUIRE(src && tar && loss && scratch, "null pointer");
     KPN_REQUIRE(n > 0, "empty image");
-    double* partial = static_cast<double*>(scratch);
-    int* ticket = reinterpret_cast<int*>(partial + 2048);
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    (void)hipMemsetAsync(ticket, 0, sizeof(int), (hipStream_t)stream);
-    KPN_LAUNCH(k_pix_l1, dim3((unsigned)blocks), dim3(256), stream, n, lambda, src, tar, partial, ticket, loss, d_src);
+    const ReduceScratch r = reduce_scratch(scratch);
+    (void)hipMemsetAsync(r.ticket, 0, sizeof(int), (hipStream_t)stream);
+    KPN_LAUNCH(k_pix_l1, dim3((unsigned)reduce_blocks(n)), dim3(256), stream, n, lambda, src, tar, r.partial, r.ticket, loss, d_src);
     return check_launch("kpn_pix_l1_loss");
 }
 
 // compute_error_nerf's pixel and mask terms (reference src/utils.py:108-171, pix_loss :173-183) in one launch: k_train_loss
 // (loss_kernels.hip).  The grid rule is kpn_pix_l1_loss's, over the 3n pixel elements, so that the L1 terms add up in the same order.
-static int64_t train_loss_blocks(int64_t n) {
-    const int64_t blocks = (3 * n + 255) / 256;
-    return blocks > 2048 ? 2048 : blocks;
-}
+static int64_t train_loss_blocks(int64_t n) { return reduce_blocks(3 * n); }
 extern "C" size_t kpn_train_loss_workspace_bytes(int64_t n) {
     if (n <= 0 || n > (int64_t)1 << 40) return 0;
     return 256 + align_up((size_t)train_loss_blocks(n) * 6 * sizeof(double), 256);
@@ -65,14 +56,12 @@ extern "C" int kpn_ssim(const float* pred_chw, const float* gt_chw, int32_t H, i
     KPN_REQUIRE(x0 >= 0 && y0 >= 0 && w >= 7 && h >= 7 && x0 + w <= W && y0 + h <= H, "crop must lie inside the image and be at least 7x7 (win_size)");
     char* base = static_cast<char*>(scratch);
     float* tmp = reinterpret_cast<float*>(base);
-    double* partial = reinterpret_cast<double*>(base + align_up((size_t)5 * 3 * (h - 6) * w * sizeof(float), 256));
-    int* ticket = reinterpret_cast<int*>(partial + 2048);
-    (void)hipMemsetAsync(ticket, 0, sizeof(int), (hipStream_t)stream);
+    const ReduceScratch r = reduce_scratch(base + align_up((size_t)5 * 3 * (h - 6) * w * sizeof(float), 256));
+    (void)hipMemsetAsync(r.ticket, 0, sizeof(int), (hipStream_t)stream);
     KPN_LAUNCH(k_ssim_vertical, grid1d((int64_t)3 * (h - 6) * w, 256), dim3(256), stream, pred_chw, gt_chw, (int)H, (int)W, (int)x0, (int)y0,
                (int)w, (int)h, tmp);
-    int64_t blocks = ((int64_t)3 * (h - 6) * (w - 6) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    KPN_LAUNCH(k_ssim_map, dim3((unsigned)blocks), dim3(256), stream, (const float*)tmp, (int)w, (int)h, partial, ticket, out);
+    KPN_LAUNCH(k_ssim_map, dim3((unsigned)reduce_blocks((int64_t)3 * (h - 6) * (w - 6))), dim3(256), stream, (const float*)tmp, (int)w, (int)h,
+               r.partial, r.ticket, out);
     return check_launch("kpn_ssim");
 }
 extern "C" double kpn_flops_per_row(void) { return 2.0 * 70080.0; }

@@ -11,6 +11,7 @@
 
 #include "../../include/kpnerf.h"
 #include "kpn_device.h"
+#include "kpn_reduce.h"
 
 // kernels (ray_kernels.hip / field_kernels.hip)
 #include "ray_kernels.hip"

@@ -625,73 +625,21 @@ __global__ void k_frame_to_rgb8(int HW, int bgr, const float* __restrict__ chw, 
     }
 }
 
-// grid-stride squared-error sum in fp64; the last workgroup to finish (ticket) folds the partials
+// grid-stride squared-error sum in fp64, reduced in a fixed order (kpn_reduce.h)
 __global__ __launch_bounds__(256) void k_mse_psnr(int64_t n, const float* __restrict__ a, const float* __restrict__ b,
                                                   double* __restrict__ partial, int* __restrict__ ticket,
                                                   double* __restrict__ out2) {
-    __shared__ double red[256];
-    __shared__ int last;
-    double acc = 0.0;
+    __shared__ double red[1][256];
+    double acc[1] = {0.0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float d = KSUB(a[i], b[i]);
-        acc += (double)KMUL(d, d);  // (pred-gt)**2 is an fp32 op in the reference
+        acc[0] += (double)KMUL(d, d);  // (pred-gt)**2 is an fp32 op in the reference
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = red[0];
-        __threadfence();
-        last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();
-        double tot = 0.0;
-        for (unsigned k = 0; k < gridDim.x; ++k) tot += ((volatile double*)partial)[k];
+    if (kpn_block_sums_last(acc, red, partial, ticket, blockIdx.x, gridDim.x, threadIdx.x == 0)) {
+        const double tot = kpn_partials_in_order(partial, gridDim.x, 1, 0);
         const double mse = tot / (double)n;
         out2[0] = mse;
         out2[1] = -10.0 * log(mse) / log(10.0);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// pix_loss's L1 term (reference src/utils.py:164-168): loss = lambda * mean|src - tar|, and what autograd derives for it,
-// d loss / d src = lambda * sign(src - tar) / n (sign(0) = 0, torch's abs backward) — the seed gradient of
-// kpn_render_rays_train_backward for tex_fg (lambda_l1_c, coarse) and tex_fg_fine (lambda_l1, fine), src/utils.py:128-145.
-// Deterministic: per-block fp64 partial sums, the last block adds them in block order.
-__global__ __launch_bounds__(256) void k_pix_l1(int64_t n, float lambda, const float* __restrict__ src, const float* __restrict__ tar,
-                                                double* __restrict__ partial, int* __restrict__ ticket, float* __restrict__ loss,
-                                                float* __restrict__ d_src) {
-    __shared__ double red[256];
-    __shared__ int last;
-    double acc = 0.0;
-    const float gscale = lambda / (float)n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float d = KSUB(src[i], tar[i]);
-        acc += (double)fabsf(d);
-        if (d_src) d_src[i] = d > 0.0f ? gscale : (d < 0.0f ? -gscale : 0.0f);
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = red[0];
-        __threadfence();
-        last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();
-        double tot = 0.0;
-        for (unsigned k = 0; k < gridDim.x; ++k) tot += ((volatile double*)partial)[k];
-        loss[0] = lambda * (float)(tot / (double)n);
     }
 }
 
@@ -719,17 +667,16 @@ __global__ __launch_bounds__(256) void k_ssim_vertical(const float* __restrict__
     const size_t plane = (size_t)3 * hv * w;
     for (int q = 0; q < 5; ++q) tmp[q * plane + i] = (float)(s[q] / 7.0);
 }
-// pass 2: horizontal 7-tap means, the SSIM map, its sum in fp64 (last workgroup folds the partials)
+// pass 2: horizontal 7-tap means, the SSIM map, its sum in fp64 (kpn_reduce.h)
 __global__ __launch_bounds__(256) void k_ssim_map(const float* __restrict__ tmp, int w, int h, double* __restrict__ partial,
                                                   int* __restrict__ ticket, double* __restrict__ out) {
-    __shared__ double red[256];
-    __shared__ int last;
+    __shared__ double red[1][256];
     const int hv = h - 6, wv = w - 6;
     const int64_t n = (int64_t)3 * hv * wv;
     const size_t plane = (size_t)3 * hv * w;
     const float C1 = KMUL(KMUL(0.01f, 2.0f), KMUL(0.01f, 2.0f)), C2 = KMUL(KMUL(0.03f, 2.0f), KMUL(0.03f, 2.0f));
     const float cov_norm = 49.0f / 48.0f;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % wv), y = (int)((i / wv) % hv), c = (int)(i / ((int64_t)wv * hv));
         float m[5];
@@ -744,24 +691,10 @@ __global__ __launch_bounds__(256) void k_ssim_map(const float* __restrict__ tmp,
         const float vxy = KMUL(cov_norm, KSUB(m[4], KMUL(ux, uy)));
         const float A1 = KADD(KMUL(KMUL(2.0f, ux), uy), C1), A2 = KADD(KMUL(2.0f, vxy), C2);
         const float B1 = KADD(KADD(KMUL(ux, ux), KMUL(uy, uy)), C1), B2 = KADD(KADD(vx, vy), C2);
-        acc += (double)(KMUL(A1, A2) / KMUL(B1, B2));
+        acc[0] += (double)(KMUL(A1, A2) / KMUL(B1, B2));
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = red[0];
-        __threadfence();
-        last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();
-        double tot = 0.0;
-        for (unsigned k = 0; k < gridDim.x; ++k) tot += ((volatile double*)partial)[k];
+    if (kpn_block_sums_last(acc, red, partial, ticket, blockIdx.x, gridDim.x, threadIdx.x == 0)) {
+        const double tot = kpn_partials_in_order(partial, gridDim.x, 1, 0);
         out[0] = tot / (double)n;
     }
 }

@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void k_vgg_conv(kpn_vgg_conv_args a) {
     }
 }
 
-// the four L1 terms: block (k, t) sums |phi_x - phi_y| over its stride of tap t in fp64; the last block to finish adds the
-// partials in block order and writes loss = lambda * sum_t w_t * S_t / n_t
+// the four L1 terms: block (k, t) sums |phi_x - phi_y| over its stride of tap t in fp64 (kpn_reduce.h); the last block to finish
+// adds the partials in a fixed tree of its own and writes loss = lambda * sum_t w_t * S_t / n_t
 #define KPN_VGG_L1_BLOCKS 64
 struct kpn_vgg_l1_args {
     const float* act[4];
@@ -196,37 +196,25 @@ struct kpn_vgg_l1_args {
     float* loss;
 };
 __global__ __launch_bounds__(256) void k_vgg_l1(kpn_vgg_l1_args a) {
-    __shared__ double red[256];
-    __shared__ int last;
+    __shared__ double red[1][256];
     const int t = blockIdx.y;
     const float* px = a.act[t];
     const int64_t n = a.n[t];
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)KPN_VGG_L1_BLOCKS * blockDim.x)
-        acc += (double)fabsf(KSUB(px[i], px[n + i]));
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.partial[t * KPN_VGG_L1_BLOCKS + blockIdx.x] = red[0];
-        __threadfence();
-        last = (atomicAdd(a.ticket, 1) == 4 * KPN_VGG_L1_BLOCKS - 1);
-    }
-    __syncthreads();
-    if (last) {                                  // block-uniform: the whole last block adds the partials, fixed tree
-        __threadfence();
-        red[threadIdx.x] = ((volatile double*)a.partial)[threadIdx.x];   // 256 = 4 taps x KPN_VGG_L1_BLOCKS
+        acc[0] += (double)fabsf(KSUB(px[i], px[n + i]));
+    // block-uniform: the whole last block adds the partials, fixed tree
+    if (kpn_block_sums_last(acc, red, a.partial, a.ticket, t * KPN_VGG_L1_BLOCKS + blockIdx.x, 4 * KPN_VGG_L1_BLOCKS, true)) {
+        double* const r = red[0];
+        r[threadIdx.x] = ((volatile double*)a.partial)[threadIdx.x];   // 256 = 4 taps x KPN_VGG_L1_BLOCKS
         __syncthreads();
         for (int s = KPN_VGG_L1_BLOCKS / 2; s > 0; s >>= 1) {
-            if ((int)(threadIdx.x % KPN_VGG_L1_BLOCKS) < s) red[threadIdx.x] += red[threadIdx.x + s];
+            if ((int)(threadIdx.x % KPN_VGG_L1_BLOCKS) < s) r[threadIdx.x] += r[threadIdx.x + s];
             __syncthreads();
         }
         if (threadIdx.x == 0) {
             double tot = 0.0;
-            for (int u = 0; u < 4; ++u) tot += a.w[u] * (red[u * KPN_VGG_L1_BLOCKS] / (double)a.n[u]);
+            for (int u = 0; u < 4; ++u) tot += a.w[u] * (r[u * KPN_VGG_L1_BLOCKS] / (double)a.n[u]);
             a.loss[0] = (float)(a.lambda * tot);
         }
     }

@@ -21,6 +21,7 @@ from . import lib as kl
 from .weights import effective_weights, flatten_plain
 
 _f32 = torch.float32
+_REDUCE_SCRATCH_BYTES = 16392   # include/kpnerf.h, kpn_mse_psnr / kpn_pix_l1_loss: 2048 fp64 block partials and the ticket
 
 
 def _stream():
@@ -51,16 +52,26 @@ class PackedWeights:
 
     def __init__(self, state_dict_or_module, device="cuda"):
         sd = state_dict_or_module.state_dict() if hasattr(state_dict_or_module, "state_dict") else state_dict_or_module
-        L = kl.get_library()
-        plain = flatten_plain(effective_weights(sd))
-        if plain.size != L.kpn_plain_weight_floats():
-            raise ValueError("unexpected hot-path parameter count")
-        packed = np.zeros(L.kpn_packed_weight_floats(), np.float32)
-        L.check(L.kpn_pack_weights(plain.ctypes.data_as(ctypes.c_void_p), packed.ctypes.data_as(ctypes.c_void_p)))
+        packed = self._pack_on_host(flatten_plain(effective_weights(sd)))
         # the packers' count of weights beyond fp16's range (include/kpnerf.h kpn_packed_f16_range_check).  Nothing to do here:
         # the two-fp16-piece kernels read the same count on the device and leave the work to the fp32-range kernels (range guard)
         self.f16_beyond = int(packed[-4])
         self.tensor = torch.from_numpy(packed).to(device)
+
+    @staticmethod
+    def _pack_on_host(plain):
+        L = kl.get_library()
+        if plain.size != L.kpn_plain_weight_floats():
+            raise ValueError("unexpected hot-path parameter count")
+        packed = np.zeros(L.kpn_packed_weight_floats(), np.float32)
+        L.check(L.kpn_pack_weights(plain.ctypes.data_as(ctypes.c_void_p), packed.ctypes.data_as(ctypes.c_void_p)))
+        return packed
+
+    @classmethod
+    def wrap(cls, tensor):
+        self = cls.__new__(cls)
+        self.tensor = tensor
+        return self
 
     @classmethod
     def from_plain(cls, plain, device="cuda"):
@@ -71,19 +82,12 @@ class PackedWeights:
             flat = plain.detach().to(_f32).contiguous()
             if flat.numel() != L.kpn_plain_weight_floats():
                 raise ValueError("unexpected hot-path parameter count")
-            self = cls.__new__(cls)
-            self.tensor = torch.empty(L.kpn_packed_weight_floats(), dtype=_f32, device=flat.device)
+            self = cls.wrap(torch.empty(L.kpn_packed_weight_floats(), dtype=_f32, device=flat.device))
             L.check(L.kpn_pack_weights_device(_p(flat), _p(self.tensor), _stream()))
             self._plain = flat  # keeps the source alive until the stream has consumed it
             return self
         flat = np.ascontiguousarray(plain.detach().float().cpu().numpy() if isinstance(plain, torch.Tensor) else plain, dtype=np.float32)
-        if flat.size != L.kpn_plain_weight_floats():
-            raise ValueError("unexpected hot-path parameter count")
-        packed = np.zeros(L.kpn_packed_weight_floats(), np.float32)
-        L.check(L.kpn_pack_weights(flat.ctypes.data_as(ctypes.c_void_p), packed.ctypes.data_as(ctypes.c_void_p)))
-        self = cls.__new__(cls)
-        self.tensor = torch.from_numpy(packed).to(device)
-        return self
+        return cls.wrap(torch.from_numpy(cls._pack_on_host(flat)).to(device))
 
 
 class PreparedScene:
@@ -190,14 +194,18 @@ class _Rgba2Out(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_color, d_depth, d_alpha, d_contrib, d_sdf):
-        L = kl.get_library()
-        rgba, z = ctx.saved_tensors
-        q, zz = _dev(rgba, "rgba"), _dev(z, "z")
-        B, R, S = zz.shape
-        g = [None if x is None else _dev(x, "grad") for x in (d_color, d_depth, d_alpha, d_sdf)]
-        d_rgba = torch.empty_like(q)
-        L.check(L.kpn_rgba2out_backward(_p(q), _p(zz), B * R, S, _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), _p(d_rgba), _stream()))
-        return d_rgba, None
+        return rgba2out_backward(*ctx.saved_tensors, d_color, d_depth, d_alpha, d_sdf), None
+
+
+def rgba2out_backward(rgba, z, d_color, d_depth, d_alpha, d_sdf):
+    """d_rgba from the upstream gradients of rgba2out's color / depth / alpha / sdf, any of them None (kpn_rgba2out_backward)."""
+    L = kl.get_library()
+    q, zz = _dev(rgba, "rgba"), _dev(z, "z")
+    B, R, S = zz.shape
+    g = [None if x is None else _dev(x, "grad") for x in (d_color, d_depth, d_alpha, d_sdf)]
+    d_rgba = torch.empty_like(q)
+    L.check(L.kpn_rgba2out_backward(_p(q), _p(zz), B * R, S, _p(g[0]), _p(g[1]), _p(g[2]), _p(g[3]), _p(d_rgba), _stream()))
+    return d_rgba
 
 
 def rgba2out(rgba, z):
@@ -241,6 +249,19 @@ def query(scene, weights, pts, view, mode=0):
     return out.view(1, N, 5), valid.view(1, N, 1).bool()
 
 
+def _grad_buffers(scene, device, with_tex):
+    """zeroed accumulators of a backward call: the flat parameter gradient and the channels-last map gradients"""
+    d = scene.desc
+    maps = [(d.geo0_h, d.geo0_w, 64), (d.geo1_h, d.geo1_w, 8)] + ([(d.tex_h, d.tex_w, 8)] if with_tex else [])
+    return (torch.zeros(kl.get_library().kpn_plain_weight_floats(), dtype=_f32, device=device),
+            *(torch.zeros(scene.n_views, h, w, c, dtype=_f32, device=device) for h, w, c in maps))
+
+
+def _nchw(d_plain, *d_maps):
+    """what the backward wrappers return: the map gradients as NCHW views of the channels-last accumulators"""
+    return (d_plain, *(m.permute(0, 3, 1, 2) for m in d_maps))
+
+
 def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF):
     """Reverse pass of the per-(point,view) geometry rows (kpn_geo_rows_backward): MLPUNet.layers1 and the
     feat_geo gathers (reference src/utils.py:691-716, src/model.py:763-765).
@@ -254,15 +275,13 @@ def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF):
     if tuple(g.shape) != (N, V, 64):
         raise ValueError(f"d_x must be (N, V, 64) = {(N, V, 64)}, got {tuple(g.shape)}")
     d = scene.desc
-    d_plain = torch.zeros(L.kpn_plain_weight_floats(), dtype=_f32, device=p.device)
-    d_g0 = torch.zeros(V, d.geo0_h, d.geo0_w, 64, dtype=_f32, device=p.device)
-    d_g1 = torch.zeros(V, d.geo1_h, d.geo1_w, 8, dtype=_f32, device=p.device)
+    d_plain, d_g0, d_g1 = _grad_buffers(scene, p.device, with_tex=False)
     if N > 0:
         nb = L.kpn_geo_rows_backward_workspace_bytes(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
         L.check(L.kpn_geo_rows_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
                                         _p(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(ws), nb, _stream()))
-    return d_plain, d_g0.permute(0, 3, 1, 2), d_g1.permute(0, 3, 1, 2)
+    return _nchw(d_plain, d_g0, d_g1)
 
 
 def query_backward_geometry(scene, weights, pts, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0):
@@ -280,16 +299,14 @@ def query_backward_geometry(scene, weights, pts, d_out, mode=1, keep_mask=0xFFFF
     if nz is not None and nz.shape[0] != N:
         raise ValueError("noise must have one value per point")
     d = scene.desc
-    d_plain = torch.zeros(L.kpn_plain_weight_floats(), dtype=_f32, device=p.device)
-    d_g0 = torch.zeros(V, d.geo0_h, d.geo0_w, 64, dtype=_f32, device=p.device)
-    d_g1 = torch.zeros(V, d.geo1_h, d.geo1_w, 8, dtype=_f32, device=p.device)
+    d_plain, d_g0, d_g1 = _grad_buffers(scene, p.device, with_tex=False)
     if N > 0:
         nb = L.kpn_query_backward_geometry_workspace_bytes(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
         L.check(L.kpn_query_backward_geometry(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(mode),
                                               int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g),
                                               _p(d_plain), _p(d_g0), _p(d_g1), _p(ws), nb, _stream()))
-    return d_plain, d_g0.permute(0, 3, 1, 2), d_g1.permute(0, 3, 1, 2)
+    return _nchw(d_plain, d_g0, d_g1)
 
 
 def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0):
@@ -308,17 +325,14 @@ def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFF
     if nz is not None and nz.shape[0] != N:
         raise ValueError("noise must have one value per point")
     d = scene.desc
-    d_plain = torch.zeros(L.kpn_plain_weight_floats(), dtype=_f32, device=p.device)
-    d_g0 = torch.zeros(V, d.geo0_h, d.geo0_w, 64, dtype=_f32, device=p.device)
-    d_g1 = torch.zeros(V, d.geo1_h, d.geo1_w, 8, dtype=_f32, device=p.device)
-    d_tx = torch.zeros(V, d.tex_h, d.tex_w, 8, dtype=_f32, device=p.device)
+    d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, p.device, with_tex=True)
     if N > 0:
         nb = L.kpn_query_backward_workspace_bytes(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
         L.check(L.kpn_query_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
                                      int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g), _p(d_plain),
                                      _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
-    return d_plain, d_g0.permute(0, 3, 1, 2), d_g1.permute(0, 3, 1, 2), d_tx.permute(0, 3, 1, 2)
+    return _nchw(d_plain, d_g0, d_g1, d_tx)
 
 
 class RenderPlan:
@@ -361,6 +375,34 @@ class RenderPlan:
         return self.grid[3] * self.grid[4]
 
 
+def _set_camera(a, cam_tar, bounds):
+    """Fills the target-camera fields of a RenderArgs; returns the three small tensors it points to (keep them alive)."""
+    K, RT, b = _dev(cam_tar["K"], "cam_tar['K']").reshape(4, 4), _dev(cam_tar["RT"], "cam_tar['RT']").reshape(4, 4), _dev(bounds, "bounds").reshape(2, 3)
+    a.K, a.RT, a.bounds = K.data_ptr(), RT.data_ptr(), b.data_ptr()
+    a.znear, a.zfar = float(cam_tar["znear"]), float(cam_tar["zfar"])
+    return K, RT, b
+
+
+def _keep_bits(k):
+    """a view-dropout argument as the bit mask the C ABI takes: an int is one already, a (V,) 0/1 vector sets bit i for view i"""
+    return int(k) if isinstance(k, int) else int(sum(1 << i for i, x in enumerate(k.reshape(-1).tolist()) if x > 0.5))
+
+
+def _train_args(R, pix, u_coarse, u_fine, keep_coarse, keep_fine, noise_coarse, noise_fine, rand_noise_std, n_coarse, n_fine):
+    """kpn_train_args of the training render and its backward -> (TrainArgs, the tensors it points to)"""
+    px = pix.to(torch.int32).contiguous()
+    if not _on_gpu(px):
+        raise RuntimeError("pix must live on the GPU")
+    uc, uf = _dev(u_coarse, "u_coarse").reshape(R, n_coarse), _dev(u_fine, "u_fine").reshape(R, n_fine)
+    nc = _dev(noise_coarse, "noise_coarse").reshape(-1) if noise_coarse is not None else None
+    nf = _dev(noise_fine, "noise_fine").reshape(-1) if noise_fine is not None else None
+    t = kl.TrainArgs()
+    t.pix, t.u_coarse, t.u_fine = px.data_ptr(), uc.data_ptr(), uf.data_ptr()
+    t.noise_coarse, t.noise_fine = (None if v is None else v.data_ptr() for v in (nc, nf))
+    t.keep_coarse, t.keep_fine, t.rand_noise_std = _keep_bits(keep_coarse), _keep_bits(keep_fine), float(rand_noise_std)
+    return t, (px, uc, uf, nc, nf)
+
+
 def render_rays(scene, weights, cam_tar, bounds, grid=None, n_coarse=64, n_fine=64, fine=True, chunk_rays=0, plan=None, stages=False):
     """Eval-mode batch_render_pifu_nerf for the pixel grid (x0, y0, step, nx, ny) of the target camera
     cam_tar {K (1,4,4), RT (1,4,4), znear, zfar}.  Returns the reference's out dict (B=1):
@@ -370,10 +412,8 @@ def render_rays(scene, weights, cam_tar, bounds, grid=None, n_coarse=64, n_fine=
     L = kl.get_library()
     if plan is None:
         plan = RenderPlan(scene, grid, n_coarse, n_fine, fine, chunk_rays)
-    K, RT, b = _dev(cam_tar["K"], "cam_tar['K']").reshape(4, 4), _dev(cam_tar["RT"], "cam_tar['RT']").reshape(4, 4), _dev(bounds, "bounds").reshape(2, 3)
     a = plan.args
-    a.K, a.RT, a.bounds = K.data_ptr(), RT.data_ptr(), b.data_ptr()
-    a.znear, a.zfar = float(cam_tar["znear"]), float(cam_tar["zfar"])
+    cam = _set_camera(a, cam_tar, bounds)
     st = None
     if stages:
         R, Sc, Sf = plan.n_rays(), int(a.n_coarse), int(a.n_fine) if plan.fine else 0
@@ -392,7 +432,7 @@ def render_rays(scene, weights, cam_tar, bounds, grid=None, n_coarse=64, n_fine=
     finally:
         if stages:
             a.stages = ctypes.POINTER(kl.RenderStages)()
-    plan._keep = (K, RT, b)  # keep the small tensors alive until the stream has consumed them
+    plan._keep = cam  # keep the small tensors alive until the stream has consumed them
     return (plan.out, st) if stages else plan.out
 
 
@@ -403,30 +443,17 @@ def render_rays_train(scene, weights, cam_tar, bounds, pix, u_coarse, u_fine, ke
     u_fine (R,Sf); keep_* = (V,) 0/1 view-dropout vectors (or bit masks) of the coarse / fine query; noise_* flat
     density noise.  Returns the out dict with (1,3,R) / (1,R) tensors in patch order (reshape to (out_h,out_w))."""
     L = kl.get_library()
-    px = pix.to(torch.int32).contiguous()
-    if not _on_gpu(px):
-        raise RuntimeError("pix must live on the GPU")
-    R = px.shape[0]
+    R = pix.shape[0]
+    t, draws = _train_args(R, pix, u_coarse, u_fine, keep_coarse, keep_fine, noise_coarse, noise_fine, rand_noise_std, n_coarse, n_fine)
     plan = RenderPlan(scene, (0, 0, 1, R, 1), n_coarse, n_fine, fine=True, chunk_rays=chunk_rays)
-    K, RT, b = _dev(cam_tar["K"], "cam_tar['K']").reshape(4, 4), _dev(cam_tar["RT"], "cam_tar['RT']").reshape(4, 4), _dev(bounds, "bounds").reshape(2, 3)
     a = plan.args
-    a.K, a.RT, a.bounds = K.data_ptr(), RT.data_ptr(), b.data_ptr()
-    a.znear, a.zfar = float(cam_tar["znear"]), float(cam_tar["zfar"])
-    bits = lambda k: int(k) if isinstance(k, int) else int(sum(1 << i for i, x in enumerate(k.reshape(-1).tolist()) if x > 0.5))
-    uc, uf = _dev(u_coarse, "u_coarse").reshape(R, n_coarse), _dev(u_fine, "u_fine").reshape(R, n_fine)
-    nc = _dev(noise_coarse, "noise_coarse").reshape(-1) if noise_coarse is not None else None
-    nf = _dev(noise_fine, "noise_fine").reshape(-1) if noise_fine is not None else None
-    t = kl.TrainArgs()
-    t.pix, t.u_coarse, t.u_fine = px.data_ptr(), uc.data_ptr(), uf.data_ptr()
-    t.noise_coarse = nc.data_ptr() if nc is not None else None
-    t.noise_fine = nf.data_ptr() if nf is not None else None
-    t.keep_coarse, t.keep_fine, t.rand_noise_std = bits(keep_coarse), bits(keep_fine), float(rand_noise_std)
+    cam = _set_camera(a, cam_tar, bounds)  # cam and draws are not read again: they keep the tensors behind a and t alive for the calls below
     state = None
     if keep_state:
         nb = L.kpn_render_rays_train_state_bytes(ctypes.byref(scene.desc), ctypes.byref(a))
         if nb == 0:
             raise kl.KpnError("bad render arguments: " + L.kpn_last_error().decode())
-        state = torch.empty(nb, dtype=torch.uint8, device=px.device)
+        state = torch.empty(nb, dtype=torch.uint8, device=pix.device)
         L.check(L.kpn_render_rays_train_keep(ctypes.byref(scene.desc), _p(scene.ws), _p(weights.tensor), ctypes.byref(a),
                                              ctypes.byref(t), _p(state), nb, _stream()))
     else:
@@ -447,25 +474,12 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
     `state`: the tensor render_rays_train(..., keep_state=True) returned for the SAME arguments (kpn_render_rays_train_
     backward_kept: the forward is not repeated).  Returns (d_plain, d_geo0, d_geo1, d_tex) as ops.query_backward."""
     L = kl.get_library()
-    px = pix.to(torch.int32).contiguous()
-    if not _on_gpu(px):
-        raise RuntimeError("pix must live on the GPU")
-    R, V = px.shape[0], scene.n_views
-    K, RT, b = _dev(cam_tar["K"], "cam_tar['K']").reshape(4, 4), _dev(cam_tar["RT"], "cam_tar['RT']").reshape(4, 4), _dev(bounds, "bounds").reshape(2, 3)
+    R = pix.shape[0]
+    t, draws = _train_args(R, pix, u_coarse, u_fine, keep_coarse, keep_fine, noise_coarse, noise_fine, rand_noise_std, n_coarse, n_fine)
     a = kl.RenderArgs()
-    a.K, a.RT, a.bounds = K.data_ptr(), RT.data_ptr(), b.data_ptr()
-    a.znear, a.zfar = float(cam_tar["znear"]), float(cam_tar["zfar"])
+    cam = _set_camera(a, cam_tar, bounds)  # cam and draws are not read again: they keep the tensors behind a and t alive for the calls below
     a.x0, a.y0, a.step, a.nx, a.ny = 0, 0, 1, R, 1
     a.n_coarse, a.n_fine, a.fine, a.chunk_rays = int(n_coarse), int(n_fine), 1, int(chunk_rays)
-    bits = lambda k: int(k) if isinstance(k, int) else int(sum(1 << i for i, x in enumerate(k.reshape(-1).tolist()) if x > 0.5))
-    uc, uf = _dev(u_coarse, "u_coarse").reshape(R, n_coarse), _dev(u_fine, "u_fine").reshape(R, n_fine)
-    nc = _dev(noise_coarse, "noise_coarse").reshape(-1) if noise_coarse is not None else None
-    nf = _dev(noise_fine, "noise_fine").reshape(-1) if noise_fine is not None else None
-    t = kl.TrainArgs()
-    t.pix, t.u_coarse, t.u_fine = px.data_ptr(), uc.data_ptr(), uf.data_ptr()
-    t.noise_coarse = nc.data_ptr() if nc is not None else None
-    t.noise_fine = nf.data_ptr() if nf is not None else None
-    t.keep_coarse, t.keep_fine, t.rand_noise_std = bits(keep_coarse), bits(keep_fine), float(rand_noise_std)
     g, keep_alive = kl.RenderGrads(), []
     for name in ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf"):
         if grads.get(name) is not None:
@@ -475,11 +489,8 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
             keep_alive.append(gt)
             setattr(g, "d_" + name, gt.data_ptr())
     d = scene.desc
-    dv = px.device
-    d_plain = torch.zeros(L.kpn_plain_weight_floats(), dtype=_f32, device=dv)
-    d_g0 = torch.zeros(V, d.geo0_h, d.geo0_w, 64, dtype=_f32, device=dv)
-    d_g1 = torch.zeros(V, d.geo1_h, d.geo1_w, 8, dtype=_f32, device=dv)
-    d_tx = torch.zeros(V, d.tex_h, d.tex_w, 8, dtype=_f32, device=dv)
+    dv = pix.device
+    d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, dv, with_tex=True)
     nb = L.kpn_render_rays_train_backward_workspace_bytes(ctypes.byref(d), ctypes.byref(a))
     if nb == 0:
         raise kl.KpnError("bad render arguments: " + L.kpn_last_error().decode())
@@ -492,7 +503,7 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
         L.check(L.kpn_render_rays_train_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
                                                  ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
     # no host sync (stream-ordered reuse of freed blocks, see render_rays_train)
-    return d_plain, d_g0.permute(0, 3, 1, 2), d_g1.permute(0, 3, 1, 2), d_tx.permute(0, 3, 1, 2)
+    return _nchw(d_plain, d_g0, d_g1, d_tx)
 
 
 def set_geo_rows_mode(mode):
@@ -539,7 +550,6 @@ def range_guard_count():
 
 def packed_f16_range_check(packed):
     """Number of packed layers1 weights that fp16 cannot hold (rows mode 3 needs 0); synchronises the current stream."""
-    import ctypes
     L = kl.get_library()
     beyond = ctypes.c_int32(-1)
     L.check(L.kpn_packed_f16_range_check(packed.data_ptr(), _stream(), ctypes.byref(beyond)))
@@ -570,7 +580,7 @@ def mse_psnr(pred, gt):
     if a.shape != b.shape:
         raise ValueError("pred and gt must have the same shape")
     out = torch.empty(2, dtype=torch.float64, device=a.device)
-    scratch = torch.empty(2048 * 8 + 8, dtype=torch.uint8, device=a.device)
+    scratch = torch.empty(_REDUCE_SCRATCH_BYTES, dtype=torch.uint8, device=a.device)
     L.check(L.kpn_mse_psnr(_p(a), _p(b), a.numel(), _p(out), _p(scratch), _stream()))
     return out
 
@@ -584,7 +594,7 @@ def pix_l1_loss(src, tar, lam, want_grad=True):
         raise ValueError("src and tar must have the same shape")
     loss = torch.empty(1, dtype=_f32, device=a.device)
     d = torch.empty_like(a) if want_grad else None
-    scratch = torch.empty(2048 * 8 + 8, dtype=torch.uint8, device=a.device)
+    scratch = torch.empty(_REDUCE_SCRATCH_BYTES, dtype=torch.uint8, device=a.device)
     L.check(L.kpn_pix_l1_loss(_p(a), _p(b), a.numel(), float(lam), _p(loss), _p(d), _p(scratch), _stream()))
     return loss.reshape(()), d
 

@@ -33,7 +33,6 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 the flat effective-parameter vector ``plain`` (and from there ``weight_g`` / ``weight_v`` / ``bias`` / ``ani_al`` through
 ``weights.plain_tensor_from_module``) and the three encoder feature maps.  This is the op the training drop-in calls.
 """
-import ctypes
 from typing import List, Optional, Tuple
 
 import torch
@@ -59,14 +58,7 @@ def _(rgba, z):
 @_lib.custom_op("kpnerf::rgba2out_backward", mutates_args=(), device_types="cuda")
 def rgba2out_backward(rgba: torch.Tensor, z: torch.Tensor, d_color: Optional[torch.Tensor], d_depth: Optional[torch.Tensor],
                       d_alpha: Optional[torch.Tensor], d_sdf: Optional[torch.Tensor]) -> torch.Tensor:
-    L = kl.get_library()
-    q, zz = ops._dev(rgba, "rgba"), ops._dev(z, "z")
-    B, R, S = zz.shape
-    g = [None if x is None else ops._dev(x, "grad") for x in (d_color, d_depth, d_alpha, d_sdf)]
-    d_rgba = torch.empty_like(q)
-    L.check(L.kpn_rgba2out_backward(ops._p(q), ops._p(zz), B * R, S, ops._p(g[0]), ops._p(g[1]), ops._p(g[2]), ops._p(g[3]),
-                                    ops._p(d_rgba), ops._stream()))
-    return d_rgba
+    return ops.rgba2out_backward(rgba, z, d_color, d_depth, d_alpha, d_sdf)
 
 
 @rgba2out_backward.register_fake
@@ -125,9 +117,7 @@ class _SceneView:
 @_lib.custom_op("kpnerf::field_query", mutates_args=(), device_types="cuda")
 def field_query(scene_ws: torch.Tensor, scene_dims: List[int], scene_scalars: List[float], weights: torch.Tensor,
                 pts: torch.Tensor, view: torch.Tensor, mode: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    w = ops.PackedWeights.__new__(ops.PackedWeights)
-    w.tensor = weights
-    return ops.query(_SceneView(scene_ws, list(scene_dims), list(scene_scalars)), w, pts, view, mode=mode)
+    return ops.query(_SceneView(scene_ws, list(scene_dims), list(scene_scalars)), ops.PackedWeights.wrap(weights), pts, view, mode=mode)
 
 
 @field_query.register_fake
@@ -147,11 +137,9 @@ def render_rays(scene_ws: torch.Tensor, scene_dims: List[int], scene_scalars: Li
                 n_coarse: int, n_fine: int, fine: bool) -> _OUT7:
     """Eval branch of batch_render_pifu_nerf (kpn_render_rays) for the pixel grid (x0, y0, step, nx, ny).  With
     fine=False the four fine outputs are empty tensors."""
-    w = ops.PackedWeights.__new__(ops.PackedWeights)
-    w.tensor = weights
     sv = _SceneView(scene_ws, list(scene_dims), list(scene_scalars))
-    out = ops.render_rays(sv, w, {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, grid=tuple(grid), n_coarse=n_coarse,
-                          n_fine=n_fine, fine=fine)
+    out = ops.render_rays(sv, ops.PackedWeights.wrap(weights), {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, grid=tuple(grid),
+                          n_coarse=n_coarse, n_fine=n_fine, fine=fine)
     return tuple(out[k] if k in out else scene_ws.new_empty(0) for k in _OUT_KEYS)
 
 
