@@ -36,7 +36,9 @@ extern "C" {
  * kpn_tex_encode (ResBlkEncoder) (nothing of ABI 4 changed) */
 /* 6: additive - every pixel and mask term of the training loss in one launch: kpn_train_loss_args, kpn_train_loss_workspace_bytes,
  * kpn_train_loss (nothing of ABI 5 changed; kpn_pix_l1_loss stays) */
-#define KPN_ABI_VERSION 6
+/* 7: additive - the parameter leg of a training step: kpn_param_table, kpn_fold_params, kpn_fold_params_backward, kpn_fold_norm_floats,
+ * kpn_adam_segment, kpn_adam_args, kpn_adam_step (nothing of ABI 6 changed) */
+#define KPN_ABI_VERSION 7
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -525,6 +527,60 @@ int kpn_tex_encoder_stage_info(int32_t V, int32_t H, int32_t W, int32_t ds, int3
 int kpn_tex_encode(const float* img, int32_t V, int32_t H, int32_t W, int32_t ds, int32_t ngf, int32_t n_down, int32_t n_blocks,
                    int32_t n_up, int32_t out_ch, const float* packed, float eps, float* feat, float* stages, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The parameter leg of a training step: the live parameter tensors <-> the flat vector `plain` of kpn_pack_weights, and the
+ * optimizer step, one launch each.  Deterministic (fixed-order fp64 row sums, no atomics).
+ *
+ * kpn_param_table: the tensors of the KPN_PARAM_LAYERS layers in the order of `plain` (synthetic.py:HOTPATH_LAYERS).  For a layer
+ * the reference wraps in torch.nn.utils.weight_norm (src/utils.py:542-543: mlp_geo.layers1.layers.0-2, layers2.layers.0-1)
+ * g = weight_g (out) and v_or_w = weight_v (out,in); for every other layer g = NULL and v_or_w = weight (out,in).  b = bias (out),
+ * ani_al = mlp_tex.ani_al (1).  The same struct names the destinations of the gradients. */
+#define KPN_PARAM_LAYERS 19
+typedef struct kpn_param_table {
+    float* g[KPN_PARAM_LAYERS];
+    float* v_or_w[KPN_PARAM_LAYERS];
+    float* b[KPN_PARAM_LAYERS];
+    float* ani_al;
+} kpn_param_table;
+/* floats of the side buffer kpn_fold_params leaves for its backward: per weight-normed row (504) the row norm in fp64 and the
+ * fp32 scale g / norm; 8-byte aligned */
+size_t kpn_fold_norm_floats(void);
+/* kpn_fold_params: replaces torch._weight_norm(v, g, 0) per layer (what weight_norm's hook evaluates, src/utils.py:542-543), the
+ * reshapes and the concatenation of weights.plain_tensor_from_module.  Per weight-normed row n = sqrt(sum v^2) and g / n in
+ * fp64, s = (float)(g / n), W = v * s: within 2^-23 relative of the exact fold; weights of the other layers, biases and the raw
+ * ani_al are copied.  table is read only.  plain_out: kpn_plain_weight_floats(); norms_out: kpn_fold_norm_floats().
+ * A row of zero norm gives inf / NaN as torch does.  Null or inconsistent tables: KPN_EINVAL. */
+int kpn_fold_params(const kpn_param_table* table, float* plain_out, float* norms_out, void* stream);
+/* kpn_fold_params_backward: replaces what loss.backward() runs behind plain_tensor_from_module (the cat's 39 slices and five
+ * weight-norm backwards): d_plain -> the gradients of the tensors of `table`, written to the same slots of grads_table (an entry
+ * that is NULL is skipped).  dg = dot / n, dv = s dW - (g dot / n^3) v with dot = sum dW v in fp64; everything else is a copy.
+ * norms: what kpn_fold_params left for the same table values.  accumulate = 0 overwrites the destinations, != 0 adds to them
+ * (.grad's semantics under accumulate_grad_batches). */
+int kpn_fold_params_backward(const kpn_param_table* table, const float* norms, const float* d_plain,
+                             const kpn_param_table* grads_table, int32_t accumulate, void* stream);
+/* kpn_adam_step: replaces the step of the optimizer configure_optimizers returns (torch.optim.Adam, src/model.py:46-47) for the
+ * tensors listed in segments_host (a HOST array, read during the call; at most KPN_ADAM_MAX_SEGMENTS per launch, more are served
+ * by further launches).  torch.optim.Adam's semantics with amsgrad = False, maximize = False, for step number `step` (counted
+ * from 1, kept by the caller on the host: no device-to-host copy, no synchronisation):
+ *   g' = g + weight_decay p;  m <- m + (1 - beta1)(g' - m);  v <- beta2 v + (1 - beta2) g'^2;
+ *   p <- p - lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * evaluated per element in fp64 on the fp32 state, m, v and p rounded once each. */
+#define KPN_ADAM_MAX_SEGMENTS 64
+typedef struct kpn_adam_segment {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t count;                    /* elements */
+} kpn_adam_segment;
+typedef struct kpn_adam_args {
+    const kpn_adam_segment* segments_host;
+    int32_t n_segments;
+    int64_t step;
+    double lr, beta1, beta2, eps, weight_decay;
+} kpn_adam_args;
+int kpn_adam_step(const kpn_adam_args* args, void* stream);
 
 #ifdef __cplusplus
 }

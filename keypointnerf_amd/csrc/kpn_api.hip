@@ -32,6 +32,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "vgg_kernels.hip"
 #include "encoder_kernels.hip"
 #include "loss_kernels.hip"
+#include "param_kernels.hip"
 
 // host parts
 #include "api_common.h"
@@ -44,6 +45,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "api_metrics.hip"
 #include "api_vgg.hip"
 #include "api_encoders.hip"
+#include "api_params.hip"
 
 extern "C" int kpn_abi_version(void) { return KPN_ABI_VERSION; }
 extern "C" const char* kpn_last_error(void) { return g_err.c_str(); }

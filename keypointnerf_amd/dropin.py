@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .weights import plain_tensor_from_module
+from .weights import hot_tensors, plain_tensor_from_module
 
 _OUT_KEYS = ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf")
 _SEAMS = ("batch_render_pifu_nerf", "render_pifu_nerf", "query", "rgba2out", "importance_sample", "ray_bbox_intersection")
@@ -79,8 +79,10 @@ def encoder_sigma(net):
 
 
 class _State:
-    def __init__(self, net):
+    def __init__(self, net, native_params=False):
         self.net = net
+        self.native_params = bool(native_params)
+        self.hot = None              # native_params: the 44 live tensors in kpn_param_table order
         self.weights = None
         self.weights_key = None
         self.plans = {}
@@ -92,7 +94,38 @@ class _State:
         self.attached = None         # (encoder key, feat_geo object)
         self.attached_tex = None     # feat_tex object computed by attach_tex_feat(im) for the SAME im, else None
 
+    @staticmethod
+    def fold(tensors):
+        from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
+        return torch.ops.kpnerf.fold_params(tensors)
+
+    def native_tensors(self):
+        if self.hot is None:                                         # resolved once: install() again after replacing parameter objects
+            self.hot = hot_tensors(self.net)
+        return self.hot
+
+    def native_packed(self, plain=None):
+        """native_params=True: the packed operands of this parameter version (_version_key of the 44 live tensors), built on a
+        miss only — from `plain` when the caller has just folded it, else from a fold of its own."""
+        tensors = self.native_tensors()
+        key = _version_key(tensors)
+        if key is None or key != self.weights_key:
+            if plain is None:
+                with torch.no_grad():
+                    plain = self.fold(tensors)
+            self.weights = ops.PackedWeights.from_plain(plain.detach(), device=plain.device)
+            self.weights_key = key
+        return self.weights
+
+    def native_plain(self):
+        """native_params=True: the flat effective parameters by one launch (torch.ops.kpnerf.fold_params; differentiable where
+        gradients are enabled) and the packed operands of this parameter version.  Returns (plain, packed)."""
+        plain = self.fold(self.native_tensors())
+        return plain, self.native_packed(plain)
+
     def packed_weights(self):
+        if self.native_params:
+            return self.native_packed()
         params = [p for n, p in self.net.named_parameters() if n.startswith(_HOT_PREFIXES)]
         key = _version_key(params)
         if key is None or key != self.weights_key:
@@ -209,15 +242,18 @@ def _draw_keep_bits(n_views, dev):
     return int(sum(1 << i for i, x in enumerate(k.tolist()) if x > 0.5))
 
 
-def install(net, rows_mode=None):
+def install(net, rows_mode=None, native_params=False):
     """Rebinds the hot-path attributes of a reference ``KeypointNeRF`` instance to the HIP operators.
     Returns ``net``.  ``uninstall(net)`` restores the reference's methods.  ``rows_mode`` (optional) selects the rows
-    kernel process-wide (``ops.set_geo_rows_mode``: 3 = default, two fp16 pieces per operand; 2 = three bf16 pieces; 0 = fp32 MFMA)."""
+    kernel process-wide (``ops.set_geo_rows_mode``: 3 = default, two fp16 pieces per operand; 2 = three bf16 pieces; 0 = fp32 MFMA).
+    ``native_params=True`` (opt-in) folds the live parameters into the kernels' flat vector with one launch, and its gradient back
+    with one more (``torch.ops.kpnerf.fold_params``), instead of torch's weight-norm / reshape / cat graph, and packs the operands
+    once per parameter version; pair it with ``keypointnerf_amd.optim.Adam``."""
     from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
     check_supported(net)
     if rows_mode is not None:
         ops.set_geo_rows_mode(rows_mode)
-    st = _State(net)
+    st = _State(net, native_params)
     cls = type(net)
     ref = {k: getattr(cls, k) for k in _SEAMS if hasattr(cls, k)}
 
@@ -271,7 +307,11 @@ def install(net, rows_mode=None):
         extrin = sp_data["extrin"] if "extrin" in sp_data else cam_in["extrin"]
         if "transf" in cam_in:
             raise NotImplementedError("cam['transf'] (src/model.py:716-718) is not served")
-        if torch.is_grad_enabled():
+        if st.native_params:
+            # the operands of this parameter version go to the render_rays_train call below, which then does not pack them again
+            plain, packed = st.native_plain()
+            torch_ops.seed_packed(plain, packed)
+        elif torch.is_grad_enabled():
             plain = plain_tensor_from_module(net)
         else:
             with torch.no_grad():

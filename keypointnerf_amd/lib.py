@@ -65,6 +65,22 @@ class RenderGrads(ctypes.Structure):
     _fields_ = [(n, c_p) for n in ("d_tex_fg", "d_depth", "d_alpha", "d_tex_fg_fine", "d_depth_fine", "d_alpha_fine", "d_sdf")]
 
 
+class ParamTable(ctypes.Structure):
+    """struct kpn_param_table"""
+    _fields_ = [("g", c_p * 19), ("v_or_w", c_p * 19), ("b", c_p * 19), ("ani_al", c_p)]
+
+
+class AdamSegment(ctypes.Structure):
+    """struct kpn_adam_segment"""
+    _fields_ = [(n, c_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("count", c_i64)]
+
+
+class AdamArgs(ctypes.Structure):
+    """struct kpn_adam_args"""
+    _fields_ = [("segments_host", ctypes.POINTER(AdamSegment)), ("n_segments", c_i32), ("step", c_i64)] + \
+               [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
 # name -> (restype, argtypes); mirrors include/kpnerf.h one to one
 _SIGNATURES = {
     "kpn_abi_version": (ctypes.c_int, []),
@@ -156,8 +172,12 @@ _SIGNATURES = {
     "kpn_tex_encoder_stage_floats": (c_sz, [c_i32] * 9),
     "kpn_tex_encoder_stage_info": (ctypes.c_int, [c_i32] * 10 + [ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32)]),
     "kpn_tex_encode": (ctypes.c_int, [c_p] + [c_i32] * 9 + [c_p, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_fold_norm_floats": (c_sz, []),
+    "kpn_fold_params": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, c_p]),
+    "kpn_fold_params_backward": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, ctypes.POINTER(ParamTable), c_i32, c_p]),
+    "kpn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamArgs), c_p]),
 }
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class KpnError(RuntimeError):

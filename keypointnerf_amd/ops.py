@@ -648,6 +648,92 @@ def train_loss(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights, want_g
     return terms, d_x, d_xf, d_a, d_af
 
 
+def _hot_layout():
+    """per slot of the 44-tensor list (weights.hot_tensor_names): (kpn_param_table field, layer index or None, shape)"""
+    from .synthetic import HOTPATH_LAYERS
+    slots = []
+    for l, (_, _, (o, i), wn) in enumerate(HOTPATH_LAYERS):
+        if wn:
+            slots.append(("g", l, (o, 1)))
+        slots += [("v_or_w", l, (o, i)), ("b", l, (o,))]
+    return slots + [("ani_al", None, ())]
+
+
+def _param_table(tensors, what):
+    """kpn_param_table over a 44-tensor list in weights.hot_tensor_names order; an entry of `tensors` may be None (a NULL slot)"""
+    slots = _hot_layout()
+    if len(tensors) != len(slots):
+        raise ValueError(f"{what}: expected {len(slots)} tensors (weights.hot_tensor_names), got {len(tensors)}")
+    table = kl.ParamTable()
+    for t, (field, l, shape) in zip(tensors, slots):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not _on_gpu(t):
+            raise RuntimeError(f"{what} must be GPU tensors; keypointnerf_amd has no CPU path")
+        if t.dtype != _f32 or not t.is_contiguous() or t.numel() != int(np.prod(shape, dtype=np.int64)):
+            raise ValueError(f"{what}: slot {field}[{l}] must be contiguous float32 with {shape} elements, got {t.dtype} {tuple(t.shape)}")
+        if l is None:
+            table.ani_al = t.data_ptr()
+        else:
+            getattr(table, field)[l] = t.data_ptr()
+    return table
+
+
+def fold_params(tensors):
+    """The live hot-path tensors (weights.hot_tensors) -> (plain, norms): the flat effective-parameter vector of
+    weights.flatten_plain's layout — weight-norm folded (torch._weight_norm(v, g, 0), reference src/utils.py:542-543), everything
+    else copied — and the side buffer fold_params_backward needs, in one launch (kpn_fold_params)."""
+    L = kl.get_library()
+    tensors = [t.detach() for t in tensors]
+    table = _param_table(tensors, "fold_params tensors")
+    dev = tensors[0].device
+    plain = torch.empty(L.kpn_plain_weight_floats(), dtype=_f32, device=dev)
+    norms = torch.empty(L.kpn_fold_norm_floats() // 2, dtype=torch.float64, device=dev).view(_f32)     # 8-byte aligned
+    L.check(L.kpn_fold_params(ctypes.byref(table), _p(plain), _p(norms), _stream()))
+    return plain, norms
+
+
+def fold_params_backward(tensors, norms, d_plain, out=None, accumulate=False):
+    """d_plain -> the gradients of the 44 tensors in one launch (kpn_fold_params_backward).  out=None: returns new tensors.  out = a 44-list of destinations (None entries are skipped): written in place — overwritten, or added to with
+    accumulate=True (.grad's semantics) — and returned."""
+    L = kl.get_library()
+    tensors = [t.detach() for t in tensors]
+    table = _param_table(tensors, "fold_params tensors")
+    g = _dev(d_plain, "d_plain").reshape(-1)
+    if g.numel() != L.kpn_plain_weight_floats() or norms.numel() != L.kpn_fold_norm_floats():
+        raise ValueError("d_plain / norms have the wrong size")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs destinations (out)")
+        out = [torch.empty_like(t) for t in tensors]      # separate allocations: the outputs of a custom operator may not alias
+    grads = _param_table([None if t is None else t.detach() for t in out], "fold_params gradients")
+    L.check(L.kpn_fold_params_backward(ctypes.byref(table), _p(norms), _p(g), ctypes.byref(grads), int(bool(accumulate)), _stream()))
+    return out
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1, beta2, eps, weight_decay):
+    """One torch.optim.Adam step (amsgrad=False, maximize=False) of every listed tensor, in place, in one launch per 64 tensors
+    (kpn_adam_step).  step: the step number of this update (>= 1), a host integer: nothing is read back from the device.  The
+    parameters' version counters are moved, as an in-place torch operation would move them."""
+    L = kl.get_library()
+    n = len(params)
+    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)) or n == 0:
+        raise ValueError("adam_step needs as many grads, exp_avgs and exp_avg_sqs as params (at least one)")
+    segs = (kl.AdamSegment * n)()
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        for t, name in ((p, "param"), (g, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
+            if not _on_gpu(t):
+                raise RuntimeError(f"adam_step: {name} must live on the GPU; keypointnerf_amd has no CPU path")
+            if t.dtype != _f32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise ValueError(f"adam_step: {name} must be contiguous float32 of the parameter's size")
+        segs[i].param, segs[i].grad, segs[i].exp_avg, segs[i].exp_avg_sq, segs[i].count = (p.data_ptr(), g.data_ptr(), m.data_ptr(),
+                                                                                         v.data_ptr(), p.numel())
+    args = kl.AdamArgs(segments_host=segs, n_segments=n, step=int(step), lr=float(lr), beta1=float(beta1), beta2=float(beta2),
+                       eps=float(eps), weight_decay=float(weight_decay))
+    L.check(L.kpn_adam_step(ctypes.byref(args), _stream()))
+    torch.autograd.graph.increment_version(list(params))
+
+
 def vgg_pack(plain):
     """Packs the nine convolutions of vgg19.features[0:21] (flat device fp32: each OIHW weight then its bias, in features
     order; vgg.plain_from_module) on the device into the layout kpn_vgg_loss reads (reference src/utils.py:750-805)."""

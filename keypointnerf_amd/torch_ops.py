@@ -17,6 +17,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
                                        bounds, znear, zfar, pix, u_c, u_f, noise_c?, noise_f?, keep_c, keep_f, noise_std,
                                        n_coarse, n_fine) -> the same seven outputs, DIFFERENTIABLE
 
+    torch.ops.kpnerf.fold_params(tensors) -> plain   the 44 live hot-path tensors (weights.hot_tensors) -> the flat effective
+                                 parameters in one launch, DIFFERENTIABLE w.r.t. every tensor (one more launch in the backward)
+
 ``scene_ws / scene_dims / scene_scalars`` come from ``ops.PreparedScene.as_op_args()``.
 
     torch.ops.kpnerf.pix_l1_loss(src, tar, lam) -> (loss, d loss / d src)   the L1 terms of the training loss, DIFFERENTIABLE
@@ -175,6 +178,7 @@ import threading
 class _IterCache:
     lock = threading.Lock()
     key = scene = w = pinned = None
+    seed = None            # (key of plain, plain, packed operands) left by seed_packed for the next miss
     hits = misses = 0      # observable by the tests
 
 
@@ -186,7 +190,21 @@ def _tensor_key(t):
 
 def _iter_cache_clear():
     with _IterCache.lock:
-        _IterCache.key = _IterCache.scene = _IterCache.w = _IterCache.pinned = None
+        _IterCache.key = _IterCache.scene = _IterCache.w = _IterCache.pinned = _IterCache.seed = None
+
+
+def seed_packed(plain, w):
+    """The drop-in with native_params=True holds the packed operands of the current parameter version: it leaves them in the
+    iteration cache for the render_rays_train call it makes next with this very `plain`, which then prepares only the scene.  The
+    seed holds `plain`, so an equal (storage address, version) key means the same values; any other call drops it."""
+    with _IterCache.lock:
+        _IterCache.seed = (_tensor_key(plain), plain, w)
+
+
+def _take_seed(plain):
+    with _IterCache.lock:
+        seed, _IterCache.seed = _IterCache.seed, None
+    return seed[2] if seed is not None and seed[0] == _tensor_key(plain) else None
 
 
 def _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scal):
@@ -197,7 +215,9 @@ def _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask,
             _IterCache.hits += 1
             return _IterCache.scene, _IterCache.w
     scene = _raw_scene(geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scal)
-    w = ops.PackedWeights.from_plain(plain, device=geo0.device)
+    w = _take_seed(plain)
+    if w is None:
+        w = ops.PackedWeights.from_plain(plain, device=geo0.device)
     with _IterCache.lock:
         _IterCache.misses += 1
         _IterCache.key, _IterCache.scene, _IterCache.w, _IterCache.pinned = key, scene, w, tensors
@@ -385,6 +405,51 @@ def _vgg_bwd(ctx, d_loss, _d_grad):
 
 
 vgg_loss.register_autograd(_vgg_bwd, setup_context=_vgg_setup)
+
+
+@_lib.custom_op("kpnerf::fold_params_norms", mutates_args=(), device_types="cuda")
+def fold_params_norms(tensors: List[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(plain, norms) of the 44 live hot-path tensors (kpn_fold_params): what torch.ops.kpnerf.fold_params returns, and the row
+    norms its backward reads.  Differentiable w.r.t. every tensor through plain."""
+    return ops.fold_params(tensors)
+
+
+@fold_params_norms.register_fake
+def _(tensors):
+    L = kl.get_library()
+    return tensors[0].new_empty(L.kpn_plain_weight_floats()), tensors[0].new_empty(L.kpn_fold_norm_floats())
+
+
+@_lib.custom_op("kpnerf::fold_params_backward", mutates_args=(), device_types="cuda")
+def fold_params_backward(tensors: List[torch.Tensor], norms: torch.Tensor, d_plain: torch.Tensor) -> List[torch.Tensor]:
+    """One gradient per tensor of fold_params' input from d_plain (kpn_fold_params_backward, overwrite mode)."""
+    return ops.fold_params_backward(tensors, norms, d_plain)
+
+
+@fold_params_backward.register_fake
+def _(tensors, norms, d_plain):
+    return [torch.empty_like(t) for t in tensors]
+
+
+def _fold_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[0], output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _fold_bwd(ctx, d_plain, _d_norms):
+    *tensors, norms = ctx.saved_tensors
+    if d_plain is None:
+        return (None,)
+    return (torch.ops.kpnerf.fold_params_backward(list(tensors), norms, d_plain.contiguous()),)
+
+
+fold_params_norms.register_autograd(_fold_bwd, setup_context=_fold_setup)
+
+# torch.ops.kpnerf.fold_params(tensors) -> plain: fold_params_norms without the side buffer; it decomposes into that operator,
+# whose autograd formula serves it
+_fragment = torch.library.Library("kpnerf", "FRAGMENT")
+_fragment.define("fold_params(Tensor[] tensors) -> Tensor")
+_fragment.impl("fold_params", lambda tensors: torch.ops.kpnerf.fold_params_norms(tensors)[0], "CompositeImplicitAutograd")
 
 
 def _encoder_no_autograd(ctx, inputs, output):

@@ -112,3 +112,43 @@ def plain_tensor_from_module(net):
         parts += [w.reshape(-1).float(), params[prefix + ".bias"].reshape(-1).float()]
     parts.append(params["mlp_tex.ani_al"].reshape(1).float())
     return torch.cat(parts)
+
+
+def hot_tensor_names(params):
+    """The 44 hot-path tensors of ``params`` (a name -> tensor mapping, Lightning's ``model.`` prefix already stripped) in the
+    order of the C ABI's ``kpn_param_table``: per layer of HOTPATH_LAYERS ``weight_g, weight_v, bias`` (either weight-norm
+    spelling: ``weight_g`` / ``weight_v`` or ``parametrizations.weight.original0`` / ``original1``) or ``weight, bias``; then
+    ``mlp_tex.ani_al``.  The weight-normed layers must be the reference's (src/utils.py:542-543)."""
+    names = []
+    for name, prefix, shape, wn in HOTPATH_LAYERS:
+        if (prefix + ".weight_g") in params:
+            gv = [prefix + ".weight_g", prefix + ".weight_v"]
+        elif (prefix + ".parametrizations.weight.original0") in params:
+            gv = [prefix + ".parametrizations.weight.original0", prefix + ".parametrizations.weight.original1"]
+        else:
+            gv = [prefix + ".weight"]
+        if (len(gv) == 2) != wn:
+            raise ValueError(f"unsupported architecture: {prefix} is {'not ' if wn else ''}weight-normed in the reference")
+        if tuple(params[gv[-1]].shape) != tuple(shape):
+            raise ValueError(f"unsupported architecture: {prefix} has shape {tuple(params[gv[-1]].shape)}, expected {shape}")
+        names += gv + [prefix + ".bias"]
+    return names + ["mlp_tex.ani_al"]
+
+
+def live_parameters(net):
+    """name -> parameter of a live module, Lightning's ``model.`` prefix stripped (as ``_strip_prefix`` does for a state dict)"""
+    return _strip_prefix(dict(net.named_parameters()))
+
+
+def hot_tensors(net):
+    """``hot_tensor_names`` resolved on a live module: the list ``torch.ops.kpnerf.fold_params`` takes."""
+    params = live_parameters(net)
+    return [params[n] for n in hot_tensor_names(params)]
+
+
+def plain_tensor_native(net):
+    """``plain_tensor_from_module``'s contract — the flat effective-parameter vector as a differentiable tensor of the live
+    parameters — in one launch (``torch.ops.kpnerf.fold_params`` = kpn_fold_params), and one more in ``loss.backward()``
+    (kpn_fold_params_backward), instead of the cat's and the five weight-norms' autograd graph."""
+    from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
+    return torch.ops.kpnerf.fold_params(hot_tensors(net))
