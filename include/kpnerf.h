@@ -38,7 +38,9 @@ extern "C" {
  * kpn_train_loss (nothing of ABI 5 changed; kpn_pix_l1_loss stays) */
 /* 7: additive - the parameter leg of a training step: kpn_param_table, kpn_fold_params, kpn_fold_params_backward, kpn_fold_norm_floats,
  * kpn_adam_segment, kpn_adam_args, kpn_adam_step (nothing of ABI 6 changed) */
-#define KPN_ABI_VERSION 7
+/* 8: additive - one stride-1 convolution with its three gradients: kpn_conv2d_desc, kpn_conv2d_packed_floats, kpn_conv2d_pack_device,
+ * kpn_conv2d_workspace_bytes, kpn_conv2d_wgrad_ranges, kpn_conv2d_forward, kpn_conv2d_backward (nothing of ABI 7 changed) */
+#define KPN_ABI_VERSION 8
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -581,6 +583,41 @@ typedef struct kpn_adam_args {
     double lr, beta1, beta2, eps, weight_decay;
 } kpn_adam_args;
 int kpn_adam_step(const kpn_adam_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * One convolution of the image encoders, forward and backward: replaces torch.nn.functional.conv2d and its autograd
+ * (convolution_backward) as the layers of ConvBlock, HourGlass and HGFilterV2 call them (src/utils.py:416-474, 261-309, 322-414).
+ * Scope: groups = 1, dilation = 1, stride 1, a square kernel k in {1, 3, 5}, zero padding 0 <= pad <= k - 1, optional bias, fp32,
+ * cin and cout multiples of 4 (at most 1024).  Anything else - stride 2, the 7x7 stems, replication padding, ConvTranspose2d -
+ * is refused with KPN_EINVAL; kpn_last_error() names the field.
+ * Activations are NHWC (torch channels_last): x (N, H, W, cin), y and dy (N, Ho, Wo, cout), Ho = H + 2 pad - k + 1; the weight
+ * is OIHW as nn.Conv2d holds it.  Kernels: csrc/encoder_kernels.hip (fp32 MFMA, exact fp32 products, fp32 accumulation).
+ *   y  = conv(x, w) + bias                                 k_enc_conv (the encoders' forward kernel), split K as there
+ *   dx = conv(dy, w'[ci][co][k-1-ky][k-1-kx], pad k-1-pad)  k_enc_conv over the second packed copy
+ *   dw[co][ci][ky][kx] = sum_pixels x[pixel + tap] dy[pixel][co]   k_enc_wgrad: fp32 chains over ranges of output pixels (from the
+ *                        shape alone, kpn_conv2d_wgrad_ranges), the ranges added in order in fp64 and rounded once
+ *   db[co] = sum_pixels dy[pixel][co]                      fp64 partial sums over fixed pixel chunks, added in order, rounded once
+ * No float atomics: every result is bit-identical from run to run.
+ * kpn_conv2d_packed_floats / kpn_conv2d_pack_device read only cin, cout, k of the descriptor: `packed` (device, 16-byte aligned)
+ * holds the forward copy, then the input-gradient copy.  `workspace` (kpn_conv2d_workspace_bytes, 16-byte aligned; 0 = unsupported
+ * descriptor) serves the forward and the backward alike.  bias: NULL exactly when has_bias = 0.
+ * kpn_conv2d_backward: each of dx, dw, db may be NULL - that leg is not launched and nothing is written for it; dw (OIHW) and db
+ * are overwritten, not accumulated.  packed is read for dx only, x for dw only. */
+typedef struct kpn_conv2d_desc {
+    int32_t N, H, W;                  /* input images and their size */
+    int32_t cin, cout, k, pad, has_bias;
+} kpn_conv2d_desc;
+size_t kpn_conv2d_packed_floats(const kpn_conv2d_desc* desc);
+int kpn_conv2d_pack_device(const kpn_conv2d_desc* desc, const float* w_oihw, float* packed, void* stream);
+size_t kpn_conv2d_workspace_bytes(const kpn_conv2d_desc* desc);
+/* pixel ranges of the weight gradient (0 = unsupported descriptor): chunks = ceil(N Ho Wo / 16), tiles = ceil(k k cin / BM) *
+ * ceil(cout / BN) with (BM, BN) = (64, 64), or (128, 32) when cout <= 32; chunks per range = max(20, ceil(chunks / clamp(1024 / tiles,
+ * 1, 64))); ranges = ceil(chunks / chunks per range) */
+int32_t kpn_conv2d_wgrad_ranges(const kpn_conv2d_desc* desc);
+int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, const float* packed, const float* bias, float* y,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
+                        float* db, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

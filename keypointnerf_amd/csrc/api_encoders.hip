@@ -91,6 +91,14 @@ struct Ctx {
     }
 
     static int tile_n(int cout) { return cout > 32 ? 64 : 32; }
+    // split K by the per-image geometry only: an image's result must not depend on how many images are encoded with it
+    // (api_conv.hip splits its single layers by the same rule)
+    static int ksplit_of(int Ho, int Wo, int bm, int bn, int cout_p, int ncls, int nkmin) {
+        const int64_t tiles_img = ((int64_t)Ho * Wo + bm - 1) / bm * (cout_p / bn) * ncls;
+        int ksplit = 1;
+        if (tiles_img < 128) ksplit = (int)std::min<int64_t>(std::min(nkmin, 16), (256 + tiles_img - 1) / tiles_img);
+        return ksplit < 1 ? 1 : ksplit;
+    }
     static int taps_of(const ConvSpec& s, int cls) { return s.deconv ? (1 + (cls >> 1)) * (1 + (cls & 1)) : s.kh * s.kw; }
 
     // src: the stem reads `img` instead (stem != 0).  ss: offset of scale / shift in the workspace or -1
@@ -125,11 +133,7 @@ struct Ctx {
         if (s.deconv) { a.Ho = src.H; a.Wo = src.W; }
         else { a.Ho = dst.H; a.Wo = dst.W; }
         a.kh = s.kh; a.kw = s.kw; a.stride = s.stride; a.pad = s.pad; a.replicate = s.replicate;
-        // split K by the per-image geometry only: an image's result must not depend on how many images are encoded with it
-        const int64_t tiles_img = ((int64_t)a.Ho * a.Wo + bm - 1) / bm * (a.cout_p / bn) * ncls;
-        int ksplit = 1;
-        if (tiles_img < 128) ksplit = (int)std::min<int64_t>(std::min(nkmin, 16), (256 + tiles_img - 1) / tiles_img);
-        if (ksplit < 1) ksplit = 1;
+        const int ksplit = ksplit_of(a.Ho, a.Wo, bm, bn, a.cout_p, ncls, nkmin);
         a.ksplit = ksplit;
         const int64_t M = (int64_t)nimg * a.Ho * a.Wo;
         const int64_t part = ksplit > 1 ? (int64_t)ncls * ksplit * M * a.cout_p : 0;

@@ -325,11 +325,13 @@ __global__ __launch_bounds__(256) void k_enc_upadd(const float* low, float* up, 
 }
 
 // packer of one convolution: OIHW (Conv2d) or IOHW (ConvTranspose2d, parity class cls) -> [chunk][cout_p][16] with
-// k = tap * cin_p + ci; everything beyond the real taps / channels is zero
+// k = tap * cin_p + ci; everything beyond the real taps / channels is zero.  tflip: the operand of the input gradient of a
+// stride-1 Conv2d, w'[ci][co][kh - 1 - ky][kw - 1 - kx] read from the same OIHW tensor (cin / cout are those of the gradient's
+// GEMM: cin = the layer's output channels, cout = its input channels)
 struct kpn_enc_pack_args {
     const float* w;
     float* out;
-    int cin, cin_p, cout, cout_p, kh, kw, nk, deconv, cls;
+    int cin, cin_p, cout, cout_p, kh, kw, nk, deconv, cls, tflip;
 };
 __global__ __launch_bounds__(256) void k_enc_pack(kpn_enc_pack_args a) {
     const int64_t total = (int64_t)a.nk * a.cout_p * 16;
@@ -346,9 +348,136 @@ __global__ __launch_bounds__(256) void k_enc_pack(kpn_enc_pack_args a) {
                     v = a.w[(((size_t)c * a.cout + co) * 3 + ky) * 3 + kx];
                 }
             } else if (tap < a.kh * a.kw) {
-                v = a.w[((size_t)co * a.cin + c) * a.kh * a.kw + tap];
+                v = a.tflip ? a.w[((size_t)c * a.cout + co) * a.kh * a.kw + (a.kh * a.kw - 1 - tap)]
+                            : a.w[((size_t)co * a.cin + c) * a.kh * a.kw + tap];
             }
         }
         a.out[i] = v;
     }
+}
+
+// ---- gradients of one stride-1 convolution (api_conv.hip).  The input gradient is k_enc_conv over the tflip copy of the weight.
+//
+// Weight gradient: dW[(tap, ci)][co] = sum over output pixels of A[pixel][(tap, ci)] * dY[pixel][co], A the forward's implicit
+// im2col row (kpn_enc_load_a: the padding logic exists once).  The MFMA K dimension is the pixel index.  A workgroup of four
+// wavefronts owns BM K-rows x BN output channels (64 x 64, or 128 x 32 for at most 32 output channels), one 32 x 32 accumulator per
+// wavefront, and walks the 16-pixel chunks [range * cpr, (range + 1) * cpr) of blockIdx.y: both operands are staged in LDS per
+// chunk (pixel-major: the lanes of an MFMA operand read consecutive floats of one pixel) with the next chunk's loads in flight.
+// After every chunk the accumulator is added to an fp64 sum and cleared: no fp32 chain is longer than 16 pixels (activations behind
+// a ReLU times a gradient with a mean give sums of like-signed terms, whose fp32 chains lose a digit per 100 terms).  The tile of a
+// range goes, rounded to fp32, to partial[range][k-row][co] - padded K rows and channels are never stored - and
+// k_enc_wgrad_combine adds the ranges in order in fp64, rounds once and writes OIHW.  No atomics.
+struct kpn_enc_wgrad_args {
+    kpn_enc_conv_args c;       // the forward's geometry and source (ss = NULL, no ReLU); wp, dst, partial unused
+    const float* dy;           // NHWC (nimg, Ho, Wo, cout), dense
+    int krows;                 // kh * kw * cin
+    int nchunks, cpr, nranges; // 16-pixel chunks in all / per range; ranges (gridDim.y)
+    float* partial;            // [range][krows][cout]
+    float* dw;                 // OIHW
+};
+template <int BM, int BN>
+__global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
+    static_assert((BM / 32) * (BN / 32) == 4, "four wavefronts, one 32 x 32 accumulator each");
+    constexpr int QA = BM / 4, PA = 256 / QA, NA = 16 / PA;     // K-row quads per chunk row; pixels per pass; passes
+    constexpr int QB = BN / 4;
+    __shared__ __attribute__((aligned(16))) float As[16][BM];
+    __shared__ __attribute__((aligned(16))) float Bs[16][BN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ctiles = a.c.cout_p / BN;
+    const int ct = (int)(blockIdx.x % ctiles), kt = (int)(blockIdx.x / ctiles);
+    const int64_t M = (int64_t)a.c.nimg * a.c.Ho * a.c.Wo;
+    const int hw = a.c.Ho * a.c.Wo;
+    const int aq = tid % QA, ap = tid / QA;                     // A loads: K-row quad, pixel of the chunk (+ j * PA)
+    const int bq = tid % QB, bp = tid / QB;                     // dY loads: channel quad, pixel of the chunk
+    const bool bload = bp < 16;
+    const int bco = ct * BN + bq * 4;
+    const int s0 = (int)blockIdx.y * a.cpr, s1 = min(s0 + a.cpr, a.nchunks);
+    kpn_f32x4 ra[NA], rb = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto load = [&](int s) {
+        for (int j = 0; j < NA; ++j) {
+            const int64_t p = (int64_t)s * 16 + ap + j * PA;
+            const bool valid = p < M;
+            const int n = valid ? (int)(p / hw) : 0, rem = valid ? (int)(p % hw) : 0;
+            ra[j] = kpn_enc_load_a<false, false>(a.c, 0, valid, n, rem / a.c.Wo, rem % a.c.Wo, kt * BM + aq * 4);
+        }
+        if (bload) {
+            const int64_t p = (int64_t)s * 16 + bp;
+            rb = kpn_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.dy + (size_t)p * a.c.cout + bco);
+        }
+    };
+    const int wn = wave % (BN / 32), wm = wave / (BN / 32);
+    const int ai = wm * 32 + (lane & 31), bj = wn * 32 + (lane & 31), kh2 = lane >> 5;
+    kpn_f32x16 acc;
+    double sum[16];
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.0f; sum[r] = 0.0; }
+    if (s0 < s1) load(s0);
+    for (int s = s0; s < s1; ++s) {
+        for (int j = 0; j < NA; ++j) *reinterpret_cast<kpn_f32x4*>(&As[ap + j * PA][aq * 4]) = ra[j];
+        if (bload) *reinterpret_cast<kpn_f32x4*>(&Bs[bp][bq * 4]) = rb;
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+        for (int m = 0; m < 8; ++m)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * m + kh2][ai], Bs[2 * m + kh2][bj], acc, 0, 0, 0);
+        for (int r = 0; r < 16; ++r) { sum[r] += (double)acc[r]; acc[r] = 0.0f; }   // an fp32 chain is one chunk long; above it, fp64
+        __syncthreads();
+    }
+    // D[row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)][col = lane & 31]: rows are K-rows, columns output channels
+    const int co = ct * BN + bj;
+    if (co >= a.c.cout) return;
+    float* out = a.partial + (size_t)blockIdx.y * a.krows * a.c.cout;
+    for (int r = 0; r < 16; ++r) {
+        const int krow = kt * BM + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh2;
+        if (krow < a.krows) out[(size_t)krow * a.c.cout + co] = (float)sum[r];
+    }
+}
+// the ranges of one dW element, added in range order in fp64 and rounded once; [k-row = tap * cin + ci][co] -> OIHW
+__global__ __launch_bounds__(256) void k_enc_wgrad_combine(kpn_enc_wgrad_args a) {
+    const int64_t total = (int64_t)a.krows * a.c.cout;
+    const int taps = a.c.kh * a.c.kw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int co = (int)(i % a.c.cout), krow = (int)(i / a.c.cout);
+        const int tap = krow / a.c.cin, ci = krow - tap * a.c.cin;
+        double v = 0.0;
+        for (int r = 0; r < a.nranges; ++r) v += (double)a.partial[(size_t)r * total + i];
+        a.dw[((size_t)co * a.c.cin + ci) * taps + tap] = (float)v;
+    }
+}
+
+// Bias gradient db[co] = sum over pixels of dY[pixel][co]: block `chunk` adds its pixel range per channel in fp64 (the threads
+// of one channel quad in thread order), k_enc_dbias_final adds the chunks in order and rounds once.  partial [chunk][C]
+struct kpn_enc_dbias_args {
+    const float* dy;       // (M, C) dense
+    int64_t M;
+    int C, nchunks;
+    double* partial;
+    float* db;
+};
+__global__ __launch_bounds__(256) void k_enc_dbias_partial(kpn_enc_dbias_args a) {
+    __shared__ double red[256][4];
+    const int L = a.C / 4;                       // threads per pixel (at most 256)
+    const int PP = 256 / L;
+    const int cl = threadIdx.x % L, pl = threadIdx.x / L;
+    const int chunk = blockIdx.x;
+    const int64_t p0 = chunk * a.M / a.nchunks, p1 = (chunk + 1) * a.M / a.nchunks;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (pl < PP)
+        for (int64_t p = p0 + pl; p < p1; p += PP) {
+            const kpn_f32x4 v = *KPN_GLOBAL4(a.dy + (size_t)p * a.C + cl * 4);
+            for (int e = 0; e < 4; ++e) s[e] += (double)v[e];
+        }
+    for (int e = 0; e < 4; ++e) red[threadIdx.x][e] = s[e];
+    __syncthreads();
+    if (pl == 0) {
+        for (int k = 1; k < PP; ++k)
+            for (int e = 0; e < 4; ++e) s[e] += red[k * L + cl][e];
+        for (int e = 0; e < 4; ++e) a.partial[(size_t)chunk * a.C + cl * 4 + e] = s[e];
+    }
+}
+__global__ __launch_bounds__(64) void k_enc_dbias_final(kpn_enc_dbias_args a) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.C) return;
+    double S = 0.0;
+    for (int k = 0; k < a.nchunks; ++k) S += a.partial[(size_t)k * a.C + c];
+    a.db[c] = (float)S;
 }

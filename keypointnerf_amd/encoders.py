@@ -14,6 +14,9 @@ requires one) and the images are CUDA fp32, the maps come from the native encode
 ``uninstall_encoders(net)`` restores what was bound before.  Nothing changes unless the caller installs them; ``install(net)``
 does not.  The texture encoder is off by default: on the 3 x 512^2 source set it is slower than the module on MIOpen
 (profiles/encoders.md); ``tex=True`` serves it natively all the same.
+
+``install_native_convs(module)`` is a separate opt-in for training: it puts torch.ops.kpnerf.conv2d (HIP forward and backward of one
+stride-1 convolution) behind the eligible ``nn.Conv2d`` instances of a module tree; ``uninstall_native_convs`` undoes it.
 """
 import types
 
@@ -305,3 +308,72 @@ def uninstall_encoders(net):
     for k in ("_kpnerf_native_geo", "_kpnerf_native_tex"):
         net.__dict__.pop(k, None)
     return net
+
+
+# ---- training convolutions natively: torch.ops.kpnerf.conv2d behind the nn.Conv2d instances of a module tree ----
+def _conv_ineligible(m):
+    """None if kpn_conv2d_* serves this nn.Conv2d, else the reason it is left on torch"""
+    k, s, p, d = _pair(m.kernel_size), _pair(m.stride), m.padding, _pair(m.dilation)
+    if isinstance(p, str):
+        return f"padding={p!r}"
+    p = _pair(p)
+    if s != (1, 1):
+        return f"stride={s[0] if s[0] == s[1] else s}"
+    if d != (1, 1):
+        return f"dilation={d}"
+    if m.groups != 1:
+        return f"groups={m.groups}"
+    if m.padding_mode != "zeros":
+        return f"padding_mode={m.padding_mode!r}"
+    if k[0] != k[1] or k[0] not in (1, 3, 5):
+        return f"kernel_size={k} (1, 3 or 5, square)"
+    if p[0] != p[1] or not 0 <= p[0] <= k[0] - 1:
+        return f"padding={p} (0 .. k - 1, the same on both axes)"
+    if m.in_channels % 4 or m.out_channels % 4 or not ops.conv2d_supported(m.in_channels, m.out_channels, k[0]):
+        return f"channels {m.in_channels} -> {m.out_channels} (multiples of 4, at most 1024)"
+    return None
+
+
+def install_native_convs(module):
+    """Opt-in: rebinds ``forward`` on every eligible ``nn.Conv2d`` instance under ``module`` to torch.ops.kpnerf.conv2d, forward and
+    backward in HIP (kpn_conv2d_forward / kpn_conv2d_backward).  Eligible: groups = 1, dilation = 1, stride 1, a square kernel of
+    1, 3 or 5, zero padding 0 .. k - 1 (``padding_mode="zeros"``), channel counts that are multiples of 4.  Every other layer
+    (stride 2, the 7x7 stems, ConvTranspose2d, ...) is left on torch, not refused.  The rebound forward serves CUDA fp32 input and
+    calls the module's own forward for anything else; its result is channels_last.  The module tree, the parameter names and the
+    state_dict are untouched.  Independent of ``install_encoders``: both may be installed on one ``net`` (the whole-network
+    native forward still wins where it is served).  Returns (served, left): the names served, and {name: reason} of the
+    nn.Conv2d layers left alone."""
+    uninstall_native_convs(module)
+    served, left = [], {}
+    for name, m in module.named_modules():
+        if type(m) is not torch.nn.Conv2d:
+            continue
+        why = _conv_ineligible(m)
+        if why is not None:
+            left[name] = why
+            continue
+        prev = m.forward
+        m._kpnerf_conv_saved = m.__dict__.get("forward")
+
+        def forward(self, x, _prev=prev):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                    and self.weight.is_cuda and self.weight.dtype == torch.float32):
+                return _prev(x)
+            return torch.ops.kpnerf.conv2d(x, self.weight, self.bias, _pair(self.padding)[0])
+
+        m.forward = types.MethodType(forward, m)
+        served.append(name)
+    return served, left
+
+
+def uninstall_native_convs(module):
+    """Restores what ``forward`` was on every layer ``install_native_convs`` rebound (the class's bound method, or an earlier
+    instance attribute)."""
+    for m in module.modules():
+        if "_kpnerf_conv_saved" in m.__dict__:
+            saved = m.__dict__.pop("_kpnerf_conv_saved")
+            if saved is None:
+                m.__dict__.pop("forward", None)
+            else:
+                m.__dict__["forward"] = saved
+    return module

@@ -81,6 +81,11 @@ class AdamArgs(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
+class Conv2dDesc(ctypes.Structure):
+    """struct kpn_conv2d_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "cin", "cout", "k", "pad", "has_bias")]
+
+
 # name -> (restype, argtypes); mirrors include/kpnerf.h one to one
 _SIGNATURES = {
     "kpn_abi_version": (ctypes.c_int, []),
@@ -176,8 +181,14 @@ _SIGNATURES = {
     "kpn_fold_params": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, c_p]),
     "kpn_fold_params_backward": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, ctypes.POINTER(ParamTable), c_i32, c_p]),
     "kpn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamArgs), c_p]),
+    "kpn_conv2d_packed_floats": (c_sz, [ctypes.POINTER(Conv2dDesc)]),
+    "kpn_conv2d_pack_device": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p]),
+    "kpn_conv2d_workspace_bytes": (c_sz, [ctypes.POINTER(Conv2dDesc)]),
+    "kpn_conv2d_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dDesc)]),
+    "kpn_conv2d_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv2d_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class KpnError(RuntimeError):

@@ -893,3 +893,108 @@ def tex_encode(img, packed, ds=1, ngf=64, n_downsample=3, n_blocks=4, n_upsample
     ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
     L.check(L.kpn_tex_encode(_p(a), *args, _p(packed), float(eps), _p(feat), _p(st), _p(ws), nb, _stream()))
     return feat, (_encoder_stages(L.kpn_tex_encoder_stage_info, args, st) if want_stages else None)
+
+
+# ------------------------------------------------------------------------------------------------
+# One stride-1 convolution and its gradients (kpn_conv2d_*; torch.nn.functional.conv2d and its autograd, reference
+# src/utils.py:416-474, 261-309, 322-414).  Activations are channels_last tensors of logical shape (N, C, H, W).
+def _conv_desc(N, H, W, cin, cout, k, padding, has_bias):
+    d = kl.Conv2dDesc()
+    d.N, d.H, d.W, d.cin, d.cout, d.k, d.pad, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(k), int(padding), int(has_bias)
+    return d
+
+
+def _conv_cl(t, name, channels=None):
+    """a CUDA fp32 (N, C, H, W) tensor that is dense in channels_last (NHWC) memory, as it is"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not _on_gpu(t):
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); keypointnerf_amd has no CPU path")
+    if t.dtype != _f32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() != 4 or (channels is not None and t.shape[1] != channels):
+        raise ValueError(f"{name} must be (N, {channels if channels is not None else 'C'}, H, W), got {tuple(t.shape)}")
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError(f"{name} must be dense in channels_last memory (x.contiguous(memory_format=torch.channels_last))")
+    return t
+
+
+def _conv_weight(w):
+    if not isinstance(w, torch.Tensor) or not _on_gpu(w):
+        raise RuntimeError("weight must be a tensor on the GPU; keypointnerf_amd has no CPU path")
+    if w.dtype != _f32 or w.dim() != 4 or w.shape[2] != w.shape[3]:
+        raise ValueError(f"weight must be float32 (cout, cin, k, k), got {w.dtype} {tuple(w.shape)}")
+    return w.contiguous()
+
+
+def conv2d_supported(cin, cout, k):
+    """whether kpn_conv2d_* serves a stride-1 convolution of these channel counts and this square kernel"""
+    return kl.get_library().kpn_conv2d_packed_floats(ctypes.byref(_conv_desc(1, 1, 1, cin, cout, k, 0, 0))) > 0
+
+
+def conv2d_pack(weight):
+    """The two packed copies of an OIHW weight that conv2d_forward (first) and the input gradient of conv2d_backward (second:
+    transposed and flipped) read (kpn_conv2d_pack_device)."""
+    L = kl.get_library()
+    w = _conv_weight(weight.detach())
+    d = _conv_desc(1, 1, 1, w.shape[1], w.shape[0], w.shape[2], 0, 0)
+    n = L.kpn_conv2d_packed_floats(ctypes.byref(d))
+    if n == 0:
+        L.kpn_conv2d_pack_device(ctypes.byref(d), None, None, None)
+        raise ValueError(f"conv2d: unsupported weight {tuple(w.shape)}: {L.kpn_last_error().decode()}")
+    packed = torch.empty(n, dtype=_f32, device=w.device)
+    L.check(L.kpn_conv2d_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
+    return packed
+
+
+def _conv_workspace(L, d, device):
+    nb = L.kpn_conv2d_workspace_bytes(ctypes.byref(d))
+    if nb == 0:
+        L.kpn_conv2d_forward(ctypes.byref(d), None, None, None, None, None, 0, None)
+        raise ValueError(f"conv2d: unsupported convolution: {L.kpn_last_error().decode()}")
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def conv2d_forward(x, packed, bias, cout, k, padding):
+    """conv2d(x, w, bias, stride=1, padding=padding) for packed = conv2d_pack(w) (kpn_conv2d_forward).  x: (N, cin, H, W)
+    channels_last; returns (N, cout, Ho, Wo) channels_last."""
+    L = kl.get_library()
+    x = _conv_cl(x, "x")
+    N, cin, H, W = x.shape
+    d = _conv_desc(N, H, W, cin, cout, k, padding, bias is not None)
+    ws, nb = _conv_workspace(L, d, x.device)
+    if packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError("packed does not belong to this convolution (conv2d_pack)")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    if b is not None and tuple(b.shape) != (cout,):
+        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
+    Ho, Wo = H + 2 * padding - k + 1, W + 2 * padding - k + 1
+    y = torch.empty(N, Ho, Wo, cout, dtype=_f32, device=x.device)
+    L.check(L.kpn_conv2d_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
+    return y.permute(0, 3, 1, 2)
+
+
+def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want_dw=True, want_db=True):
+    """(dx, dw, db) of conv2d_forward for the output gradient dy (N, cout, Ho, Wo) channels_last (kpn_conv2d_backward); a
+    gradient that is not wanted is None and its leg is not launched.  x (channels_last) is read for dw only and packed for dx
+    only: either may be None when its leg is off.  dx is channels_last, dw OIHW."""
+    L = kl.get_library()
+    dy = _conv_cl(dy, "dy")
+    N, cout, Ho, Wo = dy.shape
+    H, W = Ho - 2 * padding + k - 1, Wo - 2 * padding + k - 1
+    want_db = bool(want_db and has_bias)
+    d = _conv_desc(N, H, W, cin, cout, k, padding, has_bias)
+    ws, nb = _conv_workspace(L, d, dy.device)
+    if want_dw:
+        x = _conv_cl(x, "x", cin)
+        if tuple(x.shape) != (N, cin, H, W):
+            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
+    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
+        raise ValueError("packed does not belong to this convolution (conv2d_pack)")
+    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
+    dw = torch.empty(cout, cin, k, k, dtype=_f32, device=dy.device) if want_dw else None
+    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
+    if want_dx or want_dw or want_db:
+        L.check(L.kpn_conv2d_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
+                                      _p(db), _p(ws), nb, _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db

@@ -31,6 +31,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.geo_encode(img, packed, [ds, out_ch, out_ch_hd], eps) -> (feat, feat_hd)   the geometry encoder, channels-last,
     torch.ops.kpnerf.tex_encode(img, packed, [ds, ngf, n_down, n_blocks, n_up, out_ch], eps) -> feat   the texture encoder; FORWARD ONLY
 
+    torch.ops.kpnerf.conv2d(x, weight, bias?, padding) -> y   one stride-1 convolution (k in {1, 3, 5}, zero padding, channels multiples
+                                 of 4), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_conv2d_forward / _backward)
+
 ``rgba2out`` and ``render_rays_train`` carry ``register_autograd`` formulas whose backward is itself a registered op
 (``kpnerf::rgba2out_backward``, ``kpnerf::render_rays_train_backward`` = kpn_render_rays_train_backward): gradients reach
 the flat effective-parameter vector ``plain`` (and from there ``weight_g`` / ``weight_v`` / ``bias`` / ``ani_al`` through
@@ -496,3 +499,113 @@ def _(img, packed, cfg, eps):
 
 
 tex_encode.register_autograd(_encoder_bwd, setup_context=_encoder_no_autograd)
+
+
+# ---- torch.ops.kpnerf.conv2d: one stride-1 convolution, DIFFERENTIABLE w.r.t. x, weight and bias ----
+# The two packed copies of a weight (forward order; transposed + flipped for the input gradient) are kept per weight: the key is
+# _tensor_key (storage address, version counter, shape, device) and the entry holds the weight it was packed from, so an equal
+# address means the same storage and an in-place update (an optimizer step) moves the version: a miss and a re-pack, never a stale
+# hit.  Inference tensors have no version counter: they are packed on every call and not kept.  At most _ConvPackCache.limit
+# weights stay resident (least recently used first out); conv2d_cache_clear() drops them all.
+import collections
+
+
+class _ConvPackCache:
+    lock = threading.Lock()
+    entries = collections.OrderedDict()     # data_ptr -> (key, weight, packed)
+    limit = 512
+    hits = misses = 0                       # observable by the tests
+
+
+def conv2d_cache_clear():
+    with _ConvPackCache.lock:
+        _ConvPackCache.entries.clear()
+
+
+def _conv_packed(weight):
+    if weight.is_inference():
+        return ops.conv2d_pack(weight)
+    key = _tensor_key(weight)
+    C = _ConvPackCache
+    with C.lock:
+        e = C.entries.get(key[0])
+        if e is not None and e[0] == key:
+            C.entries.move_to_end(key[0])
+            C.hits += 1
+            return e[2]
+    packed = ops.conv2d_pack(weight)
+    with C.lock:
+        C.misses += 1
+        C.entries[key[0]] = (key, weight, packed)
+        C.entries.move_to_end(key[0])
+        while len(C.entries) > C.limit:
+            C.entries.popitem(last=False)
+    return packed
+
+
+@_lib.custom_op("kpnerf::conv2d_cl", mutates_args=(), device_types="cuda")
+def conv2d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], padding: int) -> torch.Tensor:
+    """conv2d(x, weight, bias, stride=1, padding=padding) for a channels_last x (kpn_conv2d_forward): what torch.ops.kpnerf.conv2d
+    runs after its memory-format conversion.  weight (cout, cin, k, k), k in {1, 3, 5}, 0 <= padding < k, cin and cout multiples of 4.
+    Returns (N, cout, Ho, Wo) channels_last."""
+    return ops.conv2d_forward(x, _conv_packed(weight), bias, weight.shape[0], weight.shape[2], padding)
+
+
+@conv2d_cl.register_fake
+def _(x, weight, bias, padding):
+    N, _, H, W = x.shape
+    cout, _, k, _ = weight.shape
+    return x.new_empty(N, H + 2 * padding - k + 1, W + 2 * padding - k + 1, cout).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::conv2d_backward", mutates_args=(), device_types="cuda")
+def conv2d_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, padding: int, has_bias: bool,
+                    mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of kpnerf::conv2d_cl for the output gradient dy (kpn_conv2d_backward); mask = [dx, dweight, dbias]
+    wanted: a leg that is not wanted is not launched and its result is an empty tensor."""
+    cout, cin, k, _ = weight.shape
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = ops.conv2d_backward(x, dy, _conv_packed(weight) if mask[0] else None, cin, k, padding, has_bias,
+                                     want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    none = lambda v: dy.new_empty(0) if v is None else v
+    return none(dx), none(dw), none(db)
+
+
+@conv2d_backward.register_fake
+def _(x, weight, dy, padding, has_bias, mask):
+    e = x.new_empty(0)
+    return (torch.empty_like(x) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
+            x.new_empty(weight.shape[0]) if mask[2] and has_bias else e)
+
+
+def _conv2d_setup(ctx, inputs, output):
+    x, weight, bias, padding = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.padding, ctx.has_bias = padding, bias is not None
+    ctx.set_materialize_grads(False)
+
+
+def _conv2d_bwd(ctx, dy):
+    if dy is None:
+        return None, None, None, None
+    x, weight = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
+    if not any(mask):
+        return None, None, None, None
+    dx, dw, db = torch.ops.kpnerf.conv2d_backward(x, weight, dy, ctx.padding, ctx.has_bias, mask)
+    return (dx if mask[0] else None), (dw if mask[1] else None), (db if mask[2] else None), None
+
+
+conv2d_cl.register_autograd(_conv2d_bwd, setup_context=_conv2d_setup)
+
+
+# torch.ops.kpnerf.conv2d(x, weight, bias, padding): x in any memory format.  A contiguous NCHW input is converted to channels_last
+# ONCE here (one copy, differentiable: its backward is the reverse copy); the operator behind it and its backward then both read the
+# converted tensor.  A channels_last input passes through as it is.  The result is channels_last.
+def _conv2d(x, weight, bias, padding):
+    return torch.ops.kpnerf.conv2d_cl(x.contiguous(memory_format=torch.channels_last), weight, bias, padding)
+
+
+_fragment.define("conv2d(Tensor x, Tensor weight, Tensor? bias, int padding) -> Tensor")
+_fragment.impl("conv2d", _conv2d, "CompositeImplicitAutograd")
