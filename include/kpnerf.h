@@ -40,7 +40,9 @@ extern "C" {
  * kpn_adam_segment, kpn_adam_args, kpn_adam_step (nothing of ABI 6 changed) */
 /* 8: additive - one stride-1 convolution with its three gradients: kpn_conv2d_desc, kpn_conv2d_packed_floats, kpn_conv2d_pack_device,
  * kpn_conv2d_workspace_bytes, kpn_conv2d_wgrad_ranges, kpn_conv2d_forward, kpn_conv2d_backward (nothing of ABI 7 changed) */
-#define KPN_ABI_VERSION 8
+/* 9: additive - GroupNorm / InstanceNorm2d [+ ReLU] with its gradients: kpn_group_norm_desc, kpn_group_norm_stats_floats,
+ * kpn_group_norm_workspace_bytes, kpn_group_norm_forward, kpn_group_norm_backward (nothing of ABI 8 changed) */
+#define KPN_ABI_VERSION 9
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -618,6 +620,40 @@ int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, const float*
                        void* workspace, size_t workspace_bytes, void* stream);
 int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
                         float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * One normalisation of the image encoders with the ReLU behind it, forward and backward: replaces torch.nn.functional.group_norm
+ * [+ relu] and their autograd as the legs of ConvBlock call them (GroupNorm -> ReLU -> Conv2d, src/utils.py:416-474), and
+ * InstanceNorm2d without affine parameters (G = C, affine = 0; ResBlkEncoder, src/utils.py:199-247).
+ * Activations are NHWC (torch channels_last), dense, fp32: x, y, dy, dx (N, H, W, C).  Groups are G blocks of cpg = C / G
+ * consecutive channels; statistics are per (image, group) over cpg H W values, biased variance.
+ * Scope: C a power of two in 4 .. 1024, G dividing C, N in 1 .. 65535, H, W >= 1, N H W C < 2^31, eps > 0, affine and relu in
+ * {0, 1}; gamma and beta non-NULL exactly when affine; every pointer 16-byte aligned.  Anything else is refused with KPN_EINVAL;
+ * kpn_last_error() names the field.  Kernels: csrc/encoder_kernels.hip.
+ *   forward:  the encoders' own statistics (fp64 sums over nchunks = clamp(H W / 256, 1, 64) pixel ranges per image, added in a
+ *             fixed order) folded into scale = gamma rstd, shift = beta - mean scale, each rounded once;
+ *             y = [relu](fma(x, scale, shift))
+ *   backward: g = relu ? (fma(x, scale, shift) > 0 ? dy : 0) : dy - the forward's own bits, recomputed from `stats`, y is not read;
+ *             A_c = sum g, B_c = sum g x per (image, channel) in fp64 over the same pixel ranges; per (image, group)
+ *             ds = sum_c gamma_c B_c, db = sum_c gamma_c A_c, cnt = cpg H W, c2 = (db mean - ds) rstd^3 / cnt,
+ *             c3 = -c2 mean - db rstd / cnt;  dx = fma(g, gamma_c rstd, fma(x, c2, c3));
+ *             dgamma_c = sum_n (B_nc - mean A_nc) rstd, dbeta_c = sum_n A_nc: fp64, images in order, rounded once
+ * No float atomics: every result is bit-identical from run to run, and an image's y and dx do not depend on its batch.
+ * `stats` (kpn_group_norm_stats_floats; written by the forward, read by the backward): scale [N][C], shift [N][C], then
+ * mean [N][G], rstd [N][G] - the fp64 statistics rounded once.  `workspace` (kpn_group_norm_workspace_bytes; 0 = unsupported
+ * descriptor) serves the forward and the backward alike.
+ * kpn_group_norm_backward: each of dx, dgamma, dbeta may be NULL - nothing is written for it (dx = NULL: the elementwise pass is
+ * not launched); dgamma and dbeta are overwritten, not accumulated, and refused when affine = 0. */
+typedef struct kpn_group_norm_desc {
+    int32_t N, H, W, C, G, affine, relu;
+    float eps;
+} kpn_group_norm_desc;
+size_t kpn_group_norm_stats_floats(const kpn_group_norm_desc* desc);
+size_t kpn_group_norm_workspace_bytes(const kpn_group_norm_desc* desc);
+int kpn_group_norm_forward(const kpn_group_norm_desc* desc, const float* x, const float* gamma, const float* beta, float* y,
+                           float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int kpn_group_norm_backward(const kpn_group_norm_desc* desc, const float* x, const float* dy, const float* gamma, const float* stats,
+                            float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,10 +18,11 @@
 //              them in split order and runs the epilogue.  The split depends on the per-image geometry only.
 // Beside it: k_enc_stats_partial / k_enc_stats_final (GroupNorm / InstanceNorm statistics in fp64 partial sums, reduced in a
 // fixed order and folded with gamma / beta into the scale / shift the next loads use), k_enc_affine (normalise [+ ReLU]
-// [+ residual] where the value is needed as a tensor), k_enc_pool2 (avg_pool2d(x, 2, 2)), k_enc_upadd (bicubic x2,
-// align_corners = True, ATen's coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of
-// HourGlass._forward) and k_enc_pack.  No float atomics; every reduction has a fixed order, so results are bit-reproducible
-// and independent of the position of an image in the batch.
+// [+ residual] where the value is needed as a tensor), k_enc_norm_bwd_partial / _final / _dx (the gradient of statistics +
+// affine, api_norm.hip), k_enc_pool2 (avg_pool2d(x, 2, 2)), k_enc_upadd (bicubic x2, align_corners = True, ATen's
+// coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of HourGlass._forward) and k_enc_pack.  No float
+// atomics; every reduction has a fixed order, so results are bit-reproducible and independent of the position of an image in
+// the batch.
 
 struct kpn_enc_conv_args {
     int nimg, Ho, Wo;          // GEMM rows = nimg * Ho * Wo.  DECONV: (Ho, Wo) is the source grid, row (y, x) of class (py, px)
@@ -197,6 +198,7 @@ struct kpn_enc_stats_args {
     const float* beta;
     float eps;
     float* ss;             // scale [nimg][C] then shift [nimg][C]
+    float* mr;             // or NULL: mean [nimg][G] then rstd [nimg][G], the fp64 values rounded once (kept for a backward)
 };
 __global__ __launch_bounds__(256) void k_enc_stats_partial(kpn_enc_stats_args a) {
     __shared__ double red[256][8];
@@ -219,6 +221,19 @@ __global__ __launch_bounds__(256) void k_enc_stats_partial(kpn_enc_stats_args a)
         for (int e = 0; e < 4; ++e) { o[2 * e] = s[e]; o[2 * e + 1] = q[e]; }
     }
 }
+// s0 += p[k C][0], s1 += p[k C][1] for the chunks k = 0 .. nchunks - 1 of one (image, channel), added in chunk order.  The loads of
+// sixteen chunks are issued before their adds: one thread walks up to 64 chunks, and a load per add is a latency chain
+typedef double kpn_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void kpn_enc_add_chunks(const double* p, int C, int nchunks, double& s0, double& s1) {
+    for (int k0 = 0; k0 < nchunks; k0 += 16) {
+        kpn_f64x2 v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = *reinterpret_cast<const kpn_f64x2*>(p + (size_t)(k0 + j < nchunks ? k0 + j : k0) * C * 2);
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (k0 + j < nchunks) { s0 += v[j][0]; s1 += v[j][1]; }
+    }
+}
 // step 2: one thread per (image, group): chunks then channels in order; biased variance; scale = gamma * rstd,
 // shift = beta - mean * scale
 __global__ __launch_bounds__(64) void k_enc_stats_final(kpn_enc_stats_args a) {
@@ -227,15 +242,13 @@ __global__ __launch_bounds__(64) void k_enc_stats_final(kpn_enc_stats_args a) {
     const int n = i / a.G, g = i % a.G, cpg = a.C / a.G;
     double S = 0.0, Q = 0.0;
     for (int c = g * cpg; c < (g + 1) * cpg; ++c)
-        for (int k = 0; k < a.nchunks; ++k) {
-            const double* o = a.partial + (((size_t)n * a.nchunks + k) * a.C + c) * 2;
-            S += o[0]; Q += o[1];
-        }
+        kpn_enc_add_chunks(a.partial + ((size_t)n * a.nchunks * a.C + c) * 2, a.C, a.nchunks, S, Q);
     const double cnt = (double)a.HW * cpg;
     const double mean = S / cnt;
     double var = Q / cnt - mean * mean;
     if (var < 0.0) var = 0.0;
     const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    if (a.mr) { a.mr[(size_t)n * a.G + g] = (float)mean; a.mr[((size_t)a.nimg + n) * a.G + g] = (float)rstd; }
     for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
         const double sc = a.gamma ? (double)a.gamma[c] * rstd : rstd;
         const double sh = (a.beta ? (double)a.beta[c] : 0.0) - mean * sc;
@@ -264,6 +277,125 @@ __global__ __launch_bounds__(256) void k_enc_affine(const float* src, const floa
             for (int e = 0; e < 4; ++e) v[e] = KADD(v[e], r[e]);
         }
         *reinterpret_cast<kpn_f32x4*>(dst + i * 4) = v;
+    }
+}
+
+// ---- gradient of y = [relu](x * scale + shift), scale / shift / mean / rstd as k_enc_stats_final left them (api_norm.hip).
+// With g = the gradient behind the ReLU (the mask is recomputed from fmaf(x, scale, shift): the forward's own bits),
+// A_c = sum g and B_c = sum g x per (image, channel), ds = sum_c gamma_c B_c, db = sum_c gamma_c A_c over a group, cnt = cpg HW:
+//   dx = gamma_c rstd g + c2 x + c3,   c2 = (db mean - ds) rstd^3 / cnt,   c3 = -c2 mean - db rstd / cnt
+//   dgamma_c = sum_n (B_nc - mean A_nc) rstd,   dbeta_c = sum_n A_nc
+// Every sum is fp64 in a fixed order (no atomics); each result is rounded once.
+struct kpn_enc_norm_bwd_args {
+    const float* x;        // NHWC dense (nimg, HW, C)
+    const float* dy;
+    const float* ss;       // scale [nimg][C] then shift [nimg][C]
+    const float* mr;       // mean [nimg][G] then rstd [nimg][G]
+    const float* gamma;    // or NULL
+    int relu, C, HW, nchunks, nimg, G;
+    double* partial;       // [image][chunk][channel][2]: A, B
+    float* coef;           // a [nimg][C], then c2 [nimg][C], then c3 [nimg][C]; NULL: dx is not wanted
+    float* dx;
+    float* dgamma;         // or NULL
+    float* dbeta;          // or NULL
+};
+__device__ __forceinline__ kpn_f32x4 kpn_enc_norm_g(kpn_f32x4 x, kpn_f32x4 dy, kpn_f32x4 sc, kpn_f32x4 sh, int relu) {
+    kpn_f32x4 g = dy;
+    if (relu)
+        for (int e = 0; e < 4; ++e) g[e] = fmaf(x[e], sc[e], sh[e]) > 0.0f ? dy[e] : 0.0f;
+    return g;
+}
+// pass 1: grid and thread mapping of k_enc_stats_partial; products in fp64
+__global__ __launch_bounds__(256) void k_enc_norm_bwd_partial(kpn_enc_norm_bwd_args a) {
+    __shared__ double red[256][8];
+    const int L = a.C / 4;                       // threads per pixel (a power of two, at most 256)
+    const int PP = 256 / L;
+    const int cl = threadIdx.x % L, pl = threadIdx.x / L;
+    const int chunk = blockIdx.x, n = blockIdx.y;
+    const int p0 = (int)((int64_t)chunk * a.HW / a.nchunks), p1 = (int)((int64_t)(chunk + 1) * a.HW / a.nchunks);
+    const kpn_f32x4 sc = *KPN_GLOBAL4(a.ss + (size_t)n * a.C + cl * 4), sh = *KPN_GLOBAL4(a.ss + ((size_t)a.nimg + n) * a.C + cl * 4);
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = p0 + pl; p < p1; p += 4 * PP) {          // four pixels' loads in flight, their adds in pixel order
+        kpn_f32x4 v[4], d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t o = ((size_t)n * a.HW + (p + j * PP < p1 ? p + j * PP : p)) * a.C + cl * 4;
+            v[j] = *KPN_GLOBAL4(a.x + o); d[j] = *KPN_GLOBAL4(a.dy + o);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (p + j * PP >= p1) break;
+            const kpn_f32x4 g = kpn_enc_norm_g(v[j], d[j], sc, sh, a.relu);
+            for (int e = 0; e < 4; ++e) { s[e] += (double)g[e]; q[e] += (double)g[e] * (double)v[j][e]; }
+        }
+    }
+    for (int e = 0; e < 4; ++e) { red[threadIdx.x][e] = s[e]; red[threadIdx.x][4 + e] = q[e]; }
+    __syncthreads();
+    if (pl == 0) {
+        for (int k = 1; k < PP; ++k)
+            for (int e = 0; e < 4; ++e) { s[e] += red[k * L + cl][e]; q[e] += red[k * L + cl][4 + e]; }
+        double* o = a.partial + (((size_t)n * a.nchunks + chunk) * a.C + cl * 4) * 2;
+        for (int e = 0; e < 4; ++e) { o[2 * e] = s[e]; o[2 * e + 1] = q[e]; }
+    }
+}
+// pass 2: thread i < nimg G serves one (image, group) - chunks then channels in order -> the coefficients of pass 3; thread
+// nimg G + c serves channel c - chunks then images in order -> dgamma, dbeta.  B - mean A cancels: fp64 throughout
+__global__ __launch_bounds__(64) void k_enc_norm_bwd_final(kpn_enc_norm_bwd_args a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ng = a.nimg * a.G, cpg = a.C / a.G;
+    if (i < ng) {
+        if (!a.coef) return;
+        const int n = i / a.G, g = i % a.G;
+        const double mean = (double)a.mr[(size_t)n * a.G + g], rstd = (double)a.mr[((size_t)a.nimg + n) * a.G + g];
+        double ds = 0.0, db = 0.0;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+            double A = 0.0, B = 0.0;
+            kpn_enc_add_chunks(a.partial + ((size_t)n * a.nchunks * a.C + c) * 2, a.C, a.nchunks, A, B);
+            const double gm = a.gamma ? (double)a.gamma[c] : 1.0;
+            ds += gm * B; db += gm * A;
+        }
+        const double cnt = (double)a.HW * cpg;
+        const double c2 = (db * mean - ds) * rstd * rstd * rstd / cnt;
+        const double c3 = -c2 * mean - db * rstd / cnt;
+        const size_t nc = (size_t)a.nimg * a.C;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+            a.coef[(size_t)n * a.C + c] = (float)((a.gamma ? (double)a.gamma[c] : 1.0) * rstd);
+            a.coef[nc + (size_t)n * a.C + c] = (float)c2;
+            a.coef[2 * nc + (size_t)n * a.C + c] = (float)c3;
+        }
+        return;
+    }
+    const int c = i - ng;
+    if (c >= a.C || (!a.dgamma && !a.dbeta)) return;
+    const int g = c / cpg;
+    double dg = 0.0, dbt = 0.0;
+    for (int n = 0; n < a.nimg; ++n) {
+        double A = 0.0, B = 0.0;
+        kpn_enc_add_chunks(a.partial + ((size_t)n * a.nchunks * a.C + c) * 2, a.C, a.nchunks, A, B);
+        const double mean = (double)a.mr[(size_t)n * a.G + g], rstd = (double)a.mr[((size_t)a.nimg + n) * a.G + g];
+        dg += (B - mean * A) * rstd;
+        dbt += A;
+    }
+    if (a.dgamma) a.dgamma[c] = (float)dg;
+    if (a.dbeta) a.dbeta[c] = (float)dbt;
+}
+// pass 3: dx = g a + (x c2 + c3), elementwise over float4s like k_enc_affine
+__global__ __launch_bounds__(256) void k_enc_norm_bwd_dx(kpn_enc_norm_bwd_args a) {
+    const int c4 = a.C / 4;
+    const int64_t total = (int64_t)a.nimg * a.HW * c4;
+    const size_t nc = (size_t)a.nimg * a.C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int n = (int)(i / c4 / a.HW);
+        const size_t k = (size_t)n * a.C + c;
+        const kpn_f32x4 v = *KPN_GLOBAL4(a.x + i * 4);
+        kpn_f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f}, sh = sc;
+        if (a.relu) { sc = *KPN_GLOBAL4(a.ss + k); sh = *KPN_GLOBAL4(a.ss + nc + k); }
+        const kpn_f32x4 g = kpn_enc_norm_g(v, *KPN_GLOBAL4(a.dy + i * 4), sc, sh, a.relu);
+        const kpn_f32x4 ca = *KPN_GLOBAL4(a.coef + k), c2 = *KPN_GLOBAL4(a.coef + nc + k), c3 = *KPN_GLOBAL4(a.coef + 2 * nc + k);
+        kpn_f32x4 o;
+        for (int e = 0; e < 4; ++e) o[e] = fmaf(g[e], ca[e], fmaf(v[e], c2[e], c3[e]));
+        *reinterpret_cast<kpn_f32x4*>(a.dx + i * 4) = o;
     }
 }
 

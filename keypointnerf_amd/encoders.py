@@ -17,6 +17,9 @@ does not.  The texture encoder is off by default: on the 3 x 512^2 source set it
 
 ``install_native_convs(module)`` is a separate opt-in for training: it puts torch.ops.kpnerf.conv2d (HIP forward and backward of one
 stride-1 convolution) behind the eligible ``nn.Conv2d`` instances of a module tree; ``uninstall_native_convs`` undoes it.
+``install_native_norms`` does the same for ``nn.GroupNorm`` / ``nn.InstanceNorm2d`` (torch.ops.kpnerf.group_norm), and
+``install_native_blocks`` rebinds whole ConvBlocks to ``group_norm(relu=True)`` + ``conv2d`` legs.  The three are independent:
+they rebind different modules, so they compose and uninstall in any order.
 """
 import types
 
@@ -369,11 +372,145 @@ def install_native_convs(module):
 def uninstall_native_convs(module):
     """Restores what ``forward`` was on every layer ``install_native_convs`` rebound (the class's bound method, or an earlier
     instance attribute)."""
+    return _restore_forward(module, "_kpnerf_conv_saved")
+
+
+# ---- training normalisations natively: torch.ops.kpnerf.group_norm behind nn.GroupNorm / nn.InstanceNorm2d ----
+class NativeTraining:
+    """native forward calls served by the rebound norms and blocks of all modules (the tests assert that a call was served natively)"""
+    norm_calls = 0
+    block_calls = 0
+
+
+def _pow2_channels(C):
+    return 4 <= C <= 1024 and not C & (C - 1)
+
+
+def _norm_ineligible(m):
+    """None if kpn_group_norm_* serves this nn.GroupNorm / nn.InstanceNorm2d, else the reason it is left on torch"""
+    if type(m) is torch.nn.InstanceNorm2d:
+        if m.affine:
+            return "affine=True (an InstanceNorm2d with parameters)"
+        if m.track_running_stats:
+            return "track_running_stats=True (running statistics)"
+        C = m.num_features
+    else:
+        C = m.num_channels
+    if not _pow2_channels(C):
+        return f"channels {C} (a power of two in 4 .. 1024)"
+    return None
+
+
+def _native_input(x, *params):
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and all(p is None or (p.is_cuda and p.dtype == torch.float32) for p in params))
+
+
+def install_native_norms(module):
+    """Opt-in: rebinds ``forward`` on every eligible ``nn.GroupNorm`` and ``nn.InstanceNorm2d`` instance under ``module`` to
+    torch.ops.kpnerf.group_norm (``relu=False``), forward and backward in HIP (kpn_group_norm_forward / kpn_group_norm_backward).
+    Eligible: a channel count that is a power of two in 4 .. 1024; an InstanceNorm2d only with ``affine=False`` and
+    ``track_running_stats=False``.  Every other layer is left on torch, not refused.  The rebound forward serves CUDA fp32
+    (N, C, H, W) input and calls the module's own forward for anything else; its result is channels_last.  The module tree, the
+    parameter names and the state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of the layers
+    left alone."""
+    uninstall_native_norms(module)
+    served, left = [], {}
+    for name, m in module.named_modules():
+        if type(m) not in (torch.nn.GroupNorm, torch.nn.InstanceNorm2d):
+            continue
+        why = _norm_ineligible(m)
+        if why is not None:
+            left[name] = why
+            continue
+        prev = m.forward
+        m._kpnerf_norm_saved = m.__dict__.get("forward")
+
+        def forward(self, x, _prev=prev):
+            w, b = getattr(self, "weight", None), getattr(self, "bias", None)
+            if not _native_input(x, w, b):
+                return _prev(x)
+            NativeTraining.norm_calls += 1
+            groups = self.num_groups if isinstance(self, torch.nn.GroupNorm) else self.num_features
+            return torch.ops.kpnerf.group_norm(x, w, b, groups, self.eps, False)
+
+        m.forward = types.MethodType(forward, m)
+        served.append(name)
+    return served, left
+
+
+def _restore_forward(module, key):
     for m in module.modules():
-        if "_kpnerf_conv_saved" in m.__dict__:
-            saved = m.__dict__.pop("_kpnerf_conv_saved")
+        if key in m.__dict__:
+            saved = m.__dict__.pop(key)
             if saved is None:
                 m.__dict__.pop("forward", None)
             else:
                 m.__dict__["forward"] = saved
     return module
+
+
+def uninstall_native_norms(module):
+    """Restores what ``forward`` was on every layer ``install_native_norms`` rebound."""
+    return _restore_forward(module, "_kpnerf_norm_saved")
+
+
+# ---- whole ConvBlocks natively: group_norm(relu=True) + conv2d per leg ----
+def _block_ineligible(m, name):
+    """None if every leg of this ConvBlock is served by kpn_group_norm_* and kpn_conv2d_*, else the reason"""
+    try:
+        cin, cout = m.bn1.num_channels, 2 * m.conv1.out_channels
+        _conv_block_params(m, name or "block", cin, cout, set())
+    except NotImplementedError as e:
+        return str(e)
+    except AttributeError as e:
+        return f"native encoders: {name or 'block'}: {e}"
+    widths = (cin, cout // 2, cout // 4)
+    if not all(_pow2_channels(w) for w in widths):
+        return f"channels {widths} (the norms need powers of two in 4 .. 1024)"
+    return None
+
+
+def install_native_blocks(module):
+    """Opt-in: rebinds ``forward`` on every ConvBlock under ``module`` whose structure is the reference's (src/utils.py:416-474; the
+    check the native encoder makes) to the same dataflow on the project's kernels: each ``bn -> nl -> conv`` leg, the downsample leg
+    included, is torch.ops.kpnerf.group_norm(relu=True) followed by torch.ops.kpnerf.conv2d; ``torch.cat`` and the residual add
+    stay on torch.  A ConvBlock that fails the check is left alone.  CPU or non-fp32 input goes to the original forward.  The module
+    tree, the parameter names and the state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of
+    the ConvBlocks left alone."""
+    uninstall_native_blocks(module)
+    served, left = [], {}
+    for name, m in module.named_modules():
+        if type(m).__name__ != "ConvBlock":
+            continue
+        why = _block_ineligible(m, name)
+        if why is not None:
+            left[name] = why
+            continue
+        prev = m.forward
+        m._kpnerf_block_saved = m.__dict__.get("forward")
+
+        def forward(self, x, _prev=prev):
+            if not _native_input(x, *self.parameters()):
+                return _prev(x)
+            NativeTraining.block_calls += 1
+
+            def leg(bn, conv, t, pad):
+                t = torch.ops.kpnerf.group_norm(t, bn.weight, bn.bias, bn.num_groups, bn.eps, True)
+                return torch.ops.kpnerf.conv2d(t, conv.weight, None, pad)
+
+            o1 = leg(self.bn1, self.conv1, x, 1)
+            o2 = leg(self.bn2, self.conv2, o1, 1)
+            o3 = leg(self.bn3, self.conv3, o2, 1)
+            out = torch.cat((o1, o2, o3), 1)
+            out += x if self.downsample is None else leg(self.bn4, self.downsample[2], x, 0)
+            return out
+
+        m.forward = types.MethodType(forward, m)
+        served.append(name)
+    return served, left
+
+
+def uninstall_native_blocks(module):
+    """Restores what ``forward`` was on every ConvBlock ``install_native_blocks`` rebound."""
+    return _restore_forward(module, "_kpnerf_block_saved")

@@ -86,6 +86,11 @@ class Conv2dDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "cin", "cout", "k", "pad", "has_bias")]
 
 
+class GroupNormDesc(ctypes.Structure):
+    """struct kpn_group_norm_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "C", "G", "affine", "relu")] + [("eps", c_f)]
+
+
 # name -> (restype, argtypes); mirrors include/kpnerf.h one to one
 _SIGNATURES = {
     "kpn_abi_version": (ctypes.c_int, []),
@@ -187,8 +192,12 @@ _SIGNATURES = {
     "kpn_conv2d_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dDesc)]),
     "kpn_conv2d_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv2d_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_group_norm_stats_floats": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
+    "kpn_group_norm_workspace_bytes": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
+    "kpn_group_norm_forward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_group_norm_backward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class KpnError(RuntimeError):

@@ -998,3 +998,77 @@ def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want
         L.check(L.kpn_conv2d_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
                                       _p(db), _p(ws), nb, _stream()))
     return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+
+
+# ------------------------------------------------------------------------------------------------
+# GroupNorm / InstanceNorm2d [+ ReLU] and its gradients (kpn_group_norm_*; torch.nn.functional.group_norm [+ relu] and their autograd,
+# reference src/utils.py:416-474, 199-247).  Activations are channels_last tensors of logical shape (N, C, H, W).
+def _norm_desc(N, H, W, C, groups, affine, relu, eps):
+    d = kl.GroupNormDesc()
+    d.N, d.H, d.W, d.C, d.G, d.affine, d.relu, d.eps = int(N), int(H), int(W), int(C), int(groups), int(affine), int(relu), float(eps)
+    return d
+
+
+def group_norm_supported(C, groups):
+    """whether kpn_group_norm_* serves this channel count and grouping"""
+    return kl.get_library().kpn_group_norm_workspace_bytes(ctypes.byref(_norm_desc(1, 1, 1, C, groups, 0, 0, 1e-5))) > 0
+
+
+def _norm_workspace(L, d, device):
+    nb = L.kpn_group_norm_workspace_bytes(ctypes.byref(d))
+    if nb == 0:
+        L.kpn_group_norm_forward(ctypes.byref(d), None, None, None, None, None, None, 0, None)
+        raise ValueError(f"group_norm: unsupported normalisation: {L.kpn_last_error().decode()}")
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def _norm_vec(t, name, C):
+    t = _dev(t.detach(), name)
+    if tuple(t.shape) != (C,):
+        raise ValueError(f"{name} must be ({C},), got {tuple(t.shape)}")
+    return t
+
+
+def group_norm_forward(x, weight, bias, groups, eps, relu):
+    """[relu](group_norm(x, groups, weight, bias, eps)) (kpn_group_norm_forward).  x: (N, C, H, W) channels_last; weight and bias
+    both (C,) or both None (groups = C without them is InstanceNorm2d).  Returns (y channels_last, stats): stats holds the scale and
+    shift per (image, channel) and the mean and rstd per (image, group) that group_norm_backward reads."""
+    L = kl.get_library()
+    x = _conv_cl(x, "x")
+    N, C, H, W = x.shape
+    if (weight is None) != (bias is None):
+        raise ValueError("weight and bias must both be given or both be None")
+    d = _norm_desc(N, H, W, C, groups, weight is not None, relu, eps)
+    ws, nb = _norm_workspace(L, d, x.device)
+    w = None if weight is None else _norm_vec(weight, "weight", C)
+    b = None if bias is None else _norm_vec(bias, "bias", C)
+    # y is no view of another tensor: autograd refuses an in-place ReLU on a view that a two-output operator returned
+    y = torch.empty(N, C, H, W, dtype=_f32, device=x.device, memory_format=torch.channels_last)
+    stats = torch.empty(L.kpn_group_norm_stats_floats(ctypes.byref(d)), dtype=_f32, device=x.device)
+    L.check(L.kpn_group_norm_forward(ctypes.byref(d), _p(x), _p(w), _p(b), _p(y), _p(stats), _p(ws), nb, _stream()))
+    return y, stats
+
+
+def group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=True, want_dw=True, want_db=True):
+    """(dx, dweight, dbias) of group_norm_forward for the output gradient dy (N, C, H, W) channels_last (kpn_group_norm_backward);
+    stats is what the forward returned for this x and weight.  A gradient that is not wanted is None and nothing is computed for
+    it; dweight and dbias exist only with a weight.  dx is channels_last."""
+    L = kl.get_library()
+    x, dy = _conv_cl(x, "x"), _conv_cl(dy, "dy")
+    N, C, H, W = x.shape
+    if tuple(dy.shape) != tuple(x.shape):
+        raise ValueError(f"dy must be {tuple(x.shape)}, got {tuple(dy.shape)}")
+    affine = weight is not None
+    want_dw, want_db = bool(want_dw and affine), bool(want_db and affine)
+    d = _norm_desc(N, H, W, C, groups, affine, relu, eps)
+    ws, nb = _norm_workspace(L, d, x.device)
+    if stats.numel() != L.kpn_group_norm_stats_floats(ctypes.byref(d)) or stats.dtype != _f32 or stats.device != x.device:
+        raise ValueError("stats does not belong to this normalisation (group_norm_forward)")
+    w = _norm_vec(weight, "weight", C) if affine else None
+    dx = torch.empty(N, H, W, C, dtype=_f32, device=x.device) if want_dx else None
+    dw = torch.empty(C, dtype=_f32, device=x.device) if want_dw else None
+    db = torch.empty(C, dtype=_f32, device=x.device) if want_db else None
+    if want_dx or want_dw or want_db:
+        L.check(L.kpn_group_norm_backward(ctypes.byref(d), _p(x), _p(dy), _p(w), _p(stats.contiguous()), _p(dx), _p(dw), _p(db), _p(ws), nb,
+                                          _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db

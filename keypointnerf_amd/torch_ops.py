@@ -33,6 +33,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 
     torch.ops.kpnerf.conv2d(x, weight, bias?, padding) -> y   one stride-1 convolution (k in {1, 3, 5}, zero padding, channels multiples
                                  of 4), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_conv2d_forward / _backward)
+    torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
+                                 4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
+                                 _backward); y is not kept for the backward and may be overwritten in place
 
 ``rgba2out`` and ``render_rays_train`` carry ``register_autograd`` formulas whose backward is itself a registered op
 (``kpnerf::rgba2out_backward``, ``kpnerf::render_rays_train_backward`` = kpn_render_rays_train_backward): gradients reach
@@ -609,3 +612,72 @@ def _conv2d(x, weight, bias, padding):
 
 _fragment.define("conv2d(Tensor x, Tensor weight, Tensor? bias, int padding) -> Tensor")
 _fragment.impl("conv2d", _conv2d, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.group_norm: GroupNorm / InstanceNorm2d [+ ReLU], DIFFERENTIABLE w.r.t. x, weight and bias ----
+# The backward reads x, weight and the statistics the forward kept; it never reads y (the mask of a fused ReLU is recomputed from x and
+# the kept scale / shift), so the caller may overwrite y in place - the reference's nl is ReLU(inplace=True).
+@_lib.custom_op("kpnerf::group_norm_cl", mutates_args=(), device_types="cuda")
+def group_norm_cl(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], groups: int, eps: float,
+                  relu: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, stats) of [relu](group_norm(x, groups, weight, bias, eps)) for a channels_last x (kpn_group_norm_forward): what
+    torch.ops.kpnerf.group_norm runs after its memory-format conversion.  C a power of two in 4 .. 1024; weight and bias both (C,)
+    or both None.  y is (N, C, H, W) channels_last; stats is the side buffer of the backward."""
+    return ops.group_norm_forward(x, weight, bias, groups, eps, relu)
+
+
+@group_norm_cl.register_fake
+def _(x, weight, bias, groups, eps, relu):
+    N, C, H, W = x.shape
+    return torch.empty_like(x, memory_format=torch.channels_last), x.new_empty(2 * N * C + 2 * N * groups)
+
+
+@_lib.custom_op("kpnerf::group_norm_backward", mutates_args=(), device_types="cuda")
+def group_norm_backward(x: torch.Tensor, weight: Optional[torch.Tensor], stats: torch.Tensor, dy: torch.Tensor, groups: int, eps: float,
+                        relu: bool, mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of kpnerf::group_norm_cl for the output gradient dy (kpn_group_norm_backward); mask = [dx, dweight, dbias]
+    wanted: what is not wanted is not computed and its result is an empty tensor."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = ops.group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    none = lambda v: dy.new_empty(0) if v is None else v
+    return none(dx), none(dw), none(db)
+
+
+@group_norm_backward.register_fake
+def _(x, weight, stats, dy, groups, eps, relu, mask):
+    e, affine = x.new_empty(0), weight is not None
+    return (torch.empty_like(x) if mask[0] else e, x.new_empty(x.shape[1]) if mask[1] and affine else e,
+            x.new_empty(x.shape[1]) if mask[2] and affine else e)
+
+
+def _group_norm_setup(ctx, inputs, output):
+    x, weight, bias, groups, eps, relu = inputs
+    ctx.affine = weight is not None
+    ctx.save_for_backward(x, output[1], *([weight] if ctx.affine else []))       # never y
+    ctx.groups, ctx.eps, ctx.relu = groups, eps, relu
+    ctx.set_materialize_grads(False)
+
+
+def _group_norm_bwd(ctx, dy, _d_stats):
+    if dy is None:
+        return None, None, None, None, None, None
+    x, stats, *w = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    mask = [bool(need[0]), bool(ctx.affine and need[1]), bool(ctx.affine and need[2])]
+    if not any(mask):
+        return None, None, None, None, None, None
+    dx, dw, db = torch.ops.kpnerf.group_norm_backward(x, w[0] if w else None, stats, dy, ctx.groups, ctx.eps, ctx.relu, mask)
+    return (dx if mask[0] else None), (dw if mask[1] else None), (db if mask[2] else None), None, None, None
+
+
+group_norm_cl.register_autograd(_group_norm_bwd, setup_context=_group_norm_setup)
+
+
+# torch.ops.kpnerf.group_norm(x, weight, bias, groups, eps, relu): x in any memory format, converted to channels_last once (as
+# kpnerf::conv2d does); the result is channels_last.
+def _group_norm(x, weight, bias, groups, eps, relu):
+    return torch.ops.kpnerf.group_norm_cl(x.contiguous(memory_format=torch.channels_last), weight, bias, groups, eps, relu)[0]
+
+
+_fragment.define("group_norm(Tensor x, Tensor? weight, Tensor? bias, int groups, float eps, bool relu) -> Tensor")
+_fragment.impl("group_norm", _group_norm, "CompositeImplicitAutograd")
