@@ -320,9 +320,14 @@ __global__ __launch_bounds__(256) void k_rgba2out(int64_t R, int S, const float*
     }
 }
 
-// Backward of rgba2out: one thread per ray.  Forward sweep: transmittance T_i (parked in the output row) and the
-// sums; reverse sweep with the division-free recurrence Q_{i-1} = g_i a_i + (1-a_i) Q_i, where g_i = dL/dc_i and
-// dL/da_i = T_i (g_i - Q_i)  (the cumprod's 1/(1-a_i) never appears, so a_i == 1 is harmless).
+// Backward of rgba2out: one thread per ray.  Forward sweep: transmittance T_i (parked in the output row) and the sums; reverse sweep
+// with the suffix sum U_i = sum_{j>i} g_j c_j, where g_i = dL/dc_i and c_i = a_i T_i:
+//   d sigma_i = dist_i (T_{i+1} g_i - U_i)
+// (= T_i (g_i - Q_i) dist_i (1 - a_i) of the wavefront kernel below with Q_i = U_i / T_{i+1}; no division, so a_i == 1 is harmless).
+// Nothing here is a product over the samples: T_i = exp(-sum_{j<i} sigma_j dist_j) from the running optical depth, a_i from expm1,
+// the running sums in fp64.  Over 700 samples of a thin ray a running product of the (1 - a_j) drifts by 2e-6 relative (one rounding
+// per factor, and any bias of expf once per factor), 1 - expf(-x) carries expf's rounding whole into an a_i of 2e-3, and a sequential
+// fp32 sum is off by 1e-6, which d_depth's z_i - depth multiplies by depth / |z_i - depth| (tests/ray_stage_cases.py).
 __global__ void k_rgba2out_bwd(int64_t R, int S, const float* __restrict__ rgba, const float* __restrict__ z,
                                const float* __restrict__ d_color, const float* __restrict__ d_depth,
                                const float* __restrict__ d_alpha, const float* __restrict__ d_sdf, float* __restrict__ d_rgba) {
@@ -331,38 +336,43 @@ __global__ void k_rgba2out_bwd(int64_t R, int S, const float* __restrict__ rgba,
     const float* q = rgba + r * S * 5;
     const float* zz = z + r * S;
     float* dq = d_rgba + r * S * 5;
-    float T = 1.0f, A = 0.0f, Ssum = 0.0f, Dsum = 0.0f;
+    double P = 0.0, A64 = 0.0, S64 = 0.0, D64 = 0.0;   // P: the optical depth in front of sample i
     for (int i = 0; i < S; ++i) {
         const float dist = (i + 1 < S) ? (zz[i + 1] - zz[i]) : 1e10f;
-        const float a = 1.0f - expf(-q[i * 5 + 0] * dist);
+        const float tau = q[i * 5 + 0] * dist;
+        const float a = -expm1f(-tau);
+        const float T = expf(-(float)P);
         const float c = a * T;
         dq[i * 5 + 0] = T;
-        T *= (1.0f - a);
-        A += c; Ssum += q[i * 5 + 1] * c; Dsum += zz[i] * c;
+        P += (double)tau;
+        A64 += (double)c; S64 += (double)(q[i * 5 + 1] * c); D64 += (double)(zz[i] * c);
     }
+    const float A = (float)A64, Ssum = (float)S64, Dsum = (float)D64;
     const float dc0 = d_color ? d_color[r * 3 + 0] : 0.f, dc1 = d_color ? d_color[r * 3 + 1] : 0.f, dc2 = d_color ? d_color[r * 3 + 2] : 0.f;
     const float dA = d_alpha ? d_alpha[r] : 0.f, dS = d_sdf ? d_sdf[r] : 0.f, dD = d_depth ? d_depth[r] : 0.f;
     const float inv = 1.0f / (A + 1e-8f);
     const float gA = dA - (dS * Ssum + dD * Dsum) * inv * inv;  // sdf and depth also depend on every c_i through alpha
-    float Q = 0.0f;
+    double U = 0.0;
+    float Tn = expf(-(float)P);   // T_{i+1}: behind the last sample first
     for (int i = S - 1; i >= 0; --i) {
         const float dist = (i + 1 < S) ? (zz[i + 1] - zz[i]) : 1e10f;
-        const float e = expf(-q[i * 5 + 0] * dist);  // 1 - a_i
-        const float a = 1.0f - e;
+        const float a = -expm1f(-q[i * 5 + 0] * dist);
         const float Ti = dq[i * 5 + 0];
         const float c = a * Ti;
         const float g = dc0 * q[i * 5 + 2] + dc1 * q[i * 5 + 3] + dc2 * q[i * 5 + 4] + gA + dS * q[i * 5 + 1] * inv + dD * zz[i] * inv;
-        dq[i * 5 + 0] = Ti * (g - Q) * dist * e;     // d sigma_i = dL/da_i * da_i/dsigma_i
-        dq[i * 5 + 1] = c * dS * inv;                // d sdf_i
+        dq[i * 5 + 0] = (float)((double)Tn * (double)g - U) * dist;   // d sigma_i
+        dq[i * 5 + 1] = c * dS * inv;                                  // d sdf_i
         dq[i * 5 + 2] = c * dc0; dq[i * 5 + 3] = c * dc1; dq[i * 5 + 4] = c * dc2;
-        Q = g * a + e * Q;
+        U += (double)g * (double)c;
+        Tn = Ti;
     }
 }
 
 // The same backward with one wavefront per ray (S <= 512; a training patch is ~1,000 rays, far too few threads for the form above:
 // 16 workgroups on 256 CUs, 86 us per call).  Lane l owns the contiguous samples [l*per, (l+1)*per) as in k_rgba2out: the
-// transmittance is the same 64-lane product scan, and the reverse recurrence, being affine in Q (Q_{i-1} = e_i Q_i + g_i a_i),
-// is a 64-lane suffix scan of the per-lane maps (E, B): Q before the lane's first sample = E * (Q behind its last) + B.
+// optical depth in front of a lane is a 64-lane exclusive sum scan, and the reverse recurrence, being affine in Q
+// (Q_{i-1} = e_i Q_i + g_i a_i), is a 64-lane suffix scan of the per-lane maps (E, B): Q before the lane's first sample =
+// E * (Q behind its last) + B.
 template <int PER>
 __global__ __launch_bounds__(256) void k_rgba2out_bwd_w(int64_t R, int S, const float* __restrict__ rgba, const float* __restrict__ z,
                                                         const float* __restrict__ d_color, const float* __restrict__ d_depth,
@@ -373,37 +383,40 @@ __global__ __launch_bounds__(256) void k_rgba2out_bwd_w(int64_t R, int S, const 
     if (r >= R) return;   // a whole wavefront
     const int per = (S + 63) / 64;   // <= PER
     const float* zz = z + r * S;
-    float sd[PER], cr[PER], cg[PER], cb[PER], zv[PER], dist[PER], e[PER], a[PER], Tk[PER];
-    float tl = 1.0f;
+    float sd[PER], cr[PER], cg[PER], cb[PER], zv[PER], dist[PER], tau[PER], e[PER], a[PER], Tk[PER];
+    float tl = 0.0f;   // this lane's optical depth
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int i = lane * per + k;
         sd[k] = cr[k] = cg[k] = cb[k] = zv[k] = dist[k] = 0.0f;
-        e[k] = 1.0f; a[k] = 0.0f;
+        tau[k] = 0.0f; e[k] = 1.0f; a[k] = 0.0f;
         if (k < per && i < S) {
             const float* q = rgba + (r * S + i) * 5;
             sd[k] = q[1]; cr[k] = q[2]; cg[k] = q[3]; cb[k] = q[4];
             zv[k] = zz[i];
             dist[k] = (i + 1 < S) ? (zz[i + 1] - zz[i]) : 1e10f;
-            e[k] = expf(-q[0] * dist[k]);   // 1 - a_i
+            tau[k] = q[0] * dist[k];
+            e[k] = expf(-tau[k]);   // 1 - a_i
             a[k] = 1.0f - e[k];
-            tl *= (1.0f - a[k]);
+            tl += tau[k];
         }
     }
+    // exclusive sum scan of the lanes' optical depths; T_i = exp(-(optical depth in front of sample i)): a running product of the
+    // (1 - a_j) rounds once per factor at the size of T, and on a thin ray its error grows with the sample count
     float incl = tl;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const float o = __shfl_up(incl, d);
-        if (lane >= d) incl *= o;
+        if (lane >= d) incl += o;
     }
-    float T = __shfl_up(incl, 1);
-    if (lane == 0) T = 1.0f;
+    float P = __shfl_up(incl, 1);
+    if (lane == 0) P = 0.0f;
     float A = 0.0f, Ssum = 0.0f, Dsum = 0.0f;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
-        Tk[k] = T;
-        const float c = a[k] * T;
-        T *= (1.0f - a[k]);
+        Tk[k] = expf(-P);
+        const float c = a[k] * Tk[k];
+        P += tau[k];
         A += c; Ssum += sd[k] * c; Dsum += zv[k] * c;
     }
 #pragma unroll

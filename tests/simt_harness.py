@@ -139,8 +139,9 @@ def render(lib, hs, packed, cam_tar, bounds, grid, Sc, Sf, fine=True, chunk_rays
     return (o, st) if stages else o
 
 
-def render_train(lib, hs, packed, cam_tar, bounds, pix, Sc, Sf, u_c, noise_c, noise_f, u_f, keep_c, keep_f, noise_std, chunk_rays=0):
-    """kpn_render_rays_train on host buffers; returns (C,R)-planar outputs reshaped to (R,...)."""
+def render_train(lib, hs, packed, cam_tar, bounds, pix, Sc, Sf, u_c, noise_c, noise_f, u_f, keep_c, keep_f, noise_std, chunk_rays=0, stages=False):
+    """kpn_render_rays_train on host buffers; returns (C,R)-planar outputs reshaped to (R,...).  noise_c / noise_f may be None when
+    noise_std is 0.  stages: -> (outputs, kpn_render_stages arrays in ray order)."""
     K, RT, b = f32(cam_tar["K"]).reshape(4, 4), f32(cam_tar["RT"]).reshape(4, 4), f32(bounds).reshape(2, 3)
     pix = np.ascontiguousarray(pix, dtype=np.int32).reshape(-1, 2)
     R = pix.shape[0]
@@ -153,15 +154,25 @@ def render_train(lib, hs, packed, cam_tar, bounds, pix, Sc, Sf, u_c, noise_c, no
     a.n_coarse, a.n_fine, a.fine, a.chunk_rays = Sc, Sf, 1, chunk_rays
     for k, v in o.items():
         setattr(a, k, v.ctypes.data)
-    bufs = dict(u_c=f32(u_c).reshape(R, Sc), noise_c=f32(noise_c).reshape(-1), noise_f=f32(noise_f).reshape(-1), u_f=f32(u_f).reshape(R, Sf))
+    bufs = dict(u_c=f32(u_c).reshape(R, Sc), u_f=f32(u_f).reshape(R, Sf))
+    bufs.update({k: f32(v).reshape(-1) for k, v in (("noise_c", noise_c), ("noise_f", noise_f)) if v is not None})
     t = kl.TrainArgs()
-    t.pix, t.u_coarse, t.noise_coarse, t.noise_fine, t.u_fine = (pix.ctypes.data, bufs["u_c"].ctypes.data, bufs["noise_c"].ctypes.data,
-                                                                 bufs["noise_f"].ctypes.data, bufs["u_f"].ctypes.data)
+    t.pix, t.u_coarse, t.u_fine = pix.ctypes.data, bufs["u_c"].ctypes.data, bufs["u_f"].ctypes.data
+    t.noise_coarse, t.noise_fine = (bufs[k].ctypes.data if k in bufs else None for k in ("noise_c", "noise_f"))
     t.keep_coarse, t.keep_fine, t.rand_noise_std = keep_c, keep_f, float(noise_std)
+    st = None
+    if stages:
+        st = {"z_coarse": np.full((R, Sc), np.nan, np.float32), "rgba_coarse": np.full((R, Sc, 5), np.nan, np.float32),
+              "dirs": np.full((R, 3), np.nan, np.float32), "cam_pos": np.full(3, np.nan, np.float32),
+              "z_fine": np.full((R, Sc + Sf), np.nan, np.float32), "rgba_fine": np.full((R, Sc + Sf, 5), np.nan, np.float32)}
+        cst = kl.RenderStages()
+        for k, v in st.items():
+            setattr(cst, k, v.ctypes.data)
+        a.stages = ctypes.pointer(cst)
     nb = lib.kpn_render_workspace_bytes(ctypes.byref(hs.desc), ctypes.byref(a))
     ws = np.zeros(nb, np.uint8)
     lib.check(lib.kpn_render_rays_train(ctypes.byref(hs.desc), ptr(hs.ws), ptr(packed), ctypes.byref(a), ctypes.byref(t), ptr(ws), nb, None))
-    return o
+    return (o, st) if stages else o
 
 
 def geo_rows_backward(lib, hs, packed, pts, d_x, keep=0xFFFFFFFF):
