@@ -42,7 +42,9 @@ extern "C" {
  * kpn_conv2d_workspace_bytes, kpn_conv2d_wgrad_ranges, kpn_conv2d_forward, kpn_conv2d_backward (nothing of ABI 7 changed) */
 /* 9: additive - GroupNorm / InstanceNorm2d [+ ReLU] with its gradients: kpn_group_norm_desc, kpn_group_norm_stats_floats,
  * kpn_group_norm_workspace_bytes, kpn_group_norm_forward, kpn_group_norm_backward (nothing of ABI 8 changed) */
-#define KPN_ABI_VERSION 9
+/* 10: additive - the two resampling steps of an HourGlass with their gradients: kpn_resample2_desc, kpn_avg_pool2_forward,
+ * kpn_avg_pool2_backward, kpn_upsample2x_add_forward, kpn_upsample2x_add_backward (nothing of ABI 9 changed) */
+#define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
 
@@ -654,6 +656,33 @@ int kpn_group_norm_forward(const kpn_group_norm_desc* desc, const float* x, cons
                            float* stats, void* workspace, size_t workspace_bytes, void* stream);
 int kpn_group_norm_backward(const kpn_group_norm_desc* desc, const float* x, const float* dy, const float* gamma, const float* stats,
                             float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The two resampling steps between the ConvBlocks of an HourGlass, forward and backward: replace torch.nn.functional.avg_pool2d(x, 2,
+ * stride = 2) and skip + torch.nn.functional.interpolate(low, scale_factor = 2, mode = "bicubic", align_corners = True) with their
+ * autograd (HourGlass._forward, src/utils.py:287-306).
+ * Activations are NHWC (torch channels_last), dense, fp32: the low tensors (N, h, w, C), the high tensors (N, 2h, 2w, C).
+ * Scope: N, h, w >= 1, C a positive multiple of 4 (64-bit element indices), every pointer 16-byte aligned.  Anything else is refused with
+ * KPN_EINVAL, kpn_last_error() names the field, and nothing is launched.  No workspace.  Kernels: csrc/encoder_kernels.hip.
+ *   kpn_avg_pool2_forward:   y[n][i][j][c] = 0.25 (((x[n][2i][2j][c] + x[n][2i][2j+1][c]) + x[n][2i+1][2j][c]) + x[n][2i+1][2j+1][c])
+ *   kpn_avg_pool2_backward:  dx[n][y][x][c] = 0.25 dy[n][y / 2][x / 2][c] (exact)
+ *   kpn_upsample2x_add_forward:  y = skip + U low, or y = U low for skip = NULL; y_high may be skip itself (in place).  U is ATen's
+ *       bicubic x2 with align_corners: for output row y, fy = sy y with sy = (h - 1) / (2h - 1) (0 for h = 1), iy = floor(fy), the four
+ *       cubic convolution weights (A = -0.75) of fy - iy on rows clamp(iy - 1 .. iy + 2, 0, h - 1); the same in x; the columns are
+ *       added in an fmaf chain per row, the rows in a second chain, skip last
+ *   kpn_upsample2x_add_backward: d_low = U^T dy_high as a gather, one thread per four channels of a LOW pixel (r, c): the high rows
+ *       y whose taps land on r, found by evaluating the forward's own fy, iy and weights over a widened range of y, each with the
+ *       sum of its weights that clamp onto r; the same in x.  Fixed add order: for y ascending { for x ascending: row = fma(dy[y][x],
+ *       ax[x], row) }; acc = fma(row, ay[y], acc).  No atomics, no scratch.  The gradient with respect to skip is dy_high itself.
+ * Every result is bit-identical from run to run, and an image's results do not depend on its batch. */
+typedef struct kpn_resample2_desc {
+    int32_t N, h, w, C;               /* low (N, h, w, C), high (N, 2h, 2w, C) */
+} kpn_resample2_desc;
+int kpn_avg_pool2_forward(const kpn_resample2_desc* desc, const float* x_high, float* y_low, void* stream);
+int kpn_avg_pool2_backward(const kpn_resample2_desc* desc, const float* dy_low, float* dx_high, void* stream);
+int kpn_upsample2x_add_forward(const kpn_resample2_desc* desc, const float* low, const float* skip /* NULL or high */,
+                               float* y_high /* may alias skip */, void* stream);
+int kpn_upsample2x_add_backward(const kpn_resample2_desc* desc, const float* dy_high, float* d_low, void* stream);
 
 #ifdef __cplusplus
 }

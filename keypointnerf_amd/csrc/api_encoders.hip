@@ -204,7 +204,8 @@ struct Ctx {
     void upadd(const View& low, const View& up) {
         if (mode != RUN) return;
         const int64_t n = (int64_t)nimg * up.H * up.W * up.C / 4;
-        KPN_LAUNCH(k_enc_upadd, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, (const float*)ptr(low), ptr(up), nimg, low.H, low.W, low.C);
+        KPN_LAUNCH(k_enc_upadd, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, (const float*)ptr(low), (const float*)ptr(up), ptr(up), nimg,
+                   low.H, low.W, low.C);
     }
 };
 

@@ -19,8 +19,10 @@
 // Beside it: k_enc_stats_partial / k_enc_stats_final (GroupNorm / InstanceNorm statistics in fp64 partial sums, reduced in a
 // fixed order and folded with gamma / beta into the scale / shift the next loads use), k_enc_affine (normalise [+ ReLU]
 // [+ residual] where the value is needed as a tensor), k_enc_norm_bwd_partial / _final / _dx (the gradient of statistics +
-// affine, api_norm.hip), k_enc_pool2 (avg_pool2d(x, 2, 2)), k_enc_upadd (bicubic x2, align_corners = True, ATen's
-// coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of HourGlass._forward) and k_enc_pack.  No float
+// affine, api_norm.hip), k_enc_pool2 / k_enc_pool2_bwd (avg_pool2d(x, 2, 2) and its gradient), k_enc_upadd (bicubic x2,
+// align_corners = True, ATen's coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of HourGlass._forward;
+// out of place or in place, with or without the added tensor), k_enc_up2_bwd (its gradient with respect to the low tensor, a gather
+// with the forward's own weights; api_resample.hip) and k_enc_pack.  No float
 // atomics; every reduction has a fixed order, so results are bit-reproducible and independent of the position of an image in
 // the batch.
 
@@ -424,8 +426,10 @@ __device__ __forceinline__ void kpn_enc_cubic(float t, float (&w)[4]) {
     w[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
     w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
 }
-// up (n, 2h, 2w, C) += interpolate(low (n, h, w, C), scale_factor = 2, mode = 'bicubic', align_corners = True)
-__global__ __launch_bounds__(256) void k_enc_upadd(const float* low, float* up, int nimg, int h, int w, int C) {
+// out (n, 2h, 2w, C) = skip + interpolate(low (n, h, w, C), scale_factor = 2, mode = 'bicubic', align_corners = True); skip = NULL:
+// the interpolation alone.  out may be skip itself (the encoder walk's in-place up1 + up2): a thread reads its float4 of skip before
+// it writes the same float4 of out, and no other thread touches it
+__global__ __launch_bounds__(256) void k_enc_upadd(const float* low, const float* skip, float* out, int nimg, int h, int w, int C) {
     const int c4 = C / 4, Ho = 2 * h, Wo = 2 * w;
     const float sy = Ho > 1 ? (float)(h - 1) / (float)(Ho - 1) : 0.0f, sx = Wo > 1 ? (float)(w - 1) / (float)(Wo - 1) : 0.0f;
     const int64_t total = (int64_t)nimg * Ho * Wo * c4;
@@ -450,9 +454,97 @@ __global__ __launch_bounds__(256) void k_enc_upadd(const float* low, float* up, 
             }
             for (int e = 0; e < 4; ++e) acc[e] = fmaf(row[e], wy[j], acc[e]);
         }
-        kpn_f32x4 u = *KPN_GLOBAL4(up + i * 4);
-        for (int e = 0; e < 4; ++e) u[e] = KADD(u[e], acc[e]);
-        *reinterpret_cast<kpn_f32x4*>(up + i * 4) = u;
+        if (skip) {
+            kpn_f32x4 u = *KPN_GLOBAL4(skip + i * 4);
+            for (int e = 0; e < 4; ++e) u[e] = KADD(u[e], acc[e]);
+            acc = u;
+        }
+        *reinterpret_cast<kpn_f32x4*>(out + i * 4) = acc;
+    }
+}
+
+// gradient of k_enc_pool2: dx[n][y][x][c] = 0.25 dy[n][y / 2][x / 2][c], indexed over the high tensor (one float4 in, one out)
+__global__ __launch_bounds__(256) void k_enc_pool2_bwd(const float* dy, float* dx, int nimg, int Ho, int Wo, int C) {
+    const int c4 = C / 4, H = 2 * Ho, W = 2 * Wo;
+    const int64_t total = (int64_t)nimg * H * W * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int x = (int)((i / c4) % W), y = (int)((i / c4 / W) % H), n = (int)(i / c4 / W / H);
+        const kpn_f32x4 g = *KPN_GLOBAL4(dy + (((size_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * C + c);
+        kpn_f32x4 v;
+        for (int e = 0; e < 4; ++e) v[e] = KMUL(0.25f, g[e]);
+        *reinterpret_cast<kpn_f32x4*>(dx + i * 4) = v;
+    }
+}
+
+// The weight with which output coordinate o of k_enc_upadd reads source coordinate r along one axis (scale s, source size n): the
+// forward's own fy / iy / weights, the taps that clamp onto r added in tap order.  false: o does not read r.
+__device__ __forceinline__ bool kpn_enc_up2_weight(float s, int o, int r, int n, float& a) {
+    const float f = KMUL(s, (float)o);
+    const int i = (int)floorf(f);
+    if (i < r - 2 || i > r + 1) return false;
+    float wt[4];
+    kpn_enc_cubic(KSUB(f, (float)i), wt);
+    bool hit = false;
+    a = 0.0f;
+    for (int j = 0; j < 4; ++j) {
+        int q = i - 1 + j;
+        q = q < 0 ? 0 : (q >= n ? n - 1 : q);
+        if (q == r) { a = hit ? KADD(a, wt[j]) : wt[j]; hit = true; }
+    }
+    return hit;
+}
+// The outputs that can read source coordinate r: floor(s o) in [r - 2, r + 1] with s = (n - 1) / (no - 1), i.e. o in
+// [(r - 2) / s, (r + 2) / s), in integers and one coordinate wider on both sides (the rounding of s o moves floor(s o) only where
+// s o is within ~1e-6 relative of an integer; one step of o moves s o by about 0.5).  n = 1: every output.  At most
+// 4 (no - 1) / (n - 1) + 5 < 14 coordinates for n >= 5, and no <= 8 below that: KPN_ENC_UP2_SPAN covers every size.
+#define KPN_ENC_UP2_SPAN 16
+__device__ __forceinline__ void kpn_enc_up2_range(int r, int n, int no, int& lo, int& hi) {
+    lo = 0; hi = no - 1;
+    if (n > 1) {
+        if (r > 2) lo = (int)(((int64_t)(r - 2) * (no - 1)) / (n - 1)) - 1;
+        const int64_t t = ((int64_t)(r + 2) * (no - 1) + (n - 2)) / (n - 1) + 1;
+        if (t < hi) hi = (int)t;
+        if (lo < 0) lo = 0;
+    }
+}
+// gradient of k_enc_upadd with respect to low, in gather form: d_low = U^T dy, one thread per float4 of the LOW tensor.  Which high
+// pixels read a low pixel, and with which weight, is decided by the forward's own arithmetic (kpn_enc_up2_weight) over a widened
+// range - never by an inverse formula - so no contribution is lost or doubled and the weights are the forward's bits.  The adds run
+// in a fixed order: x ascending in an fmaf chain per high row, the rows ascending in a second chain.  No atomics, no LDS, no workspace.
+__global__ __launch_bounds__(256) void k_enc_up2_bwd(const float* dy, float* dlow, int nimg, int h, int w, int C) {
+    const int c4 = C / 4, Ho = 2 * h, Wo = 2 * w;
+    const float sy = Ho > 1 ? (float)(h - 1) / (float)(Ho - 1) : 0.0f, sx = Wo > 1 ? (float)(w - 1) / (float)(Wo - 1) : 0.0f;
+    const int64_t total = (int64_t)nimg * h * w * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int cx = (int)((i / c4) % w), r = (int)((i / c4 / w) % h), n = (int)(i / c4 / w / h);
+        int x0, x1, y0, y1;
+        kpn_enc_up2_range(cx, w, Wo, x0, x1);
+        kpn_enc_up2_range(r, h, Ho, y0, y1);
+        // the column weights do not depend on the row: once per thread, in registers (every index below is a compile-time constant)
+        float ax[KPN_ENC_UP2_SPAN];
+        bool on[KPN_ENC_UP2_SPAN];
+#pragma unroll
+        for (int k = 0; k < KPN_ENC_UP2_SPAN; ++k) {
+            ax[k] = 0.0f;
+            on[k] = x0 + k <= x1 && kpn_enc_up2_weight(sx, x0 + k, cx, w, ax[k]);
+        }
+        kpn_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int y = y0; y <= y1; ++y) {
+            float ay;
+            if (!kpn_enc_up2_weight(sy, y, r, h, ay)) continue;
+            const float* p = dy + (((size_t)n * Ho + y) * Wo + x0) * C + c;
+            kpn_f32x4 row = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int k = 0; k < KPN_ENC_UP2_SPAN; ++k) {
+                if (!on[k]) continue;
+                const kpn_f32x4 v = *KPN_GLOBAL4(p + (size_t)k * C);
+                for (int e = 0; e < 4; ++e) row[e] = fmaf(v[e], ax[k], row[e]);
+            }
+            for (int e = 0; e < 4; ++e) acc[e] = fmaf(row[e], ay, acc[e]);
+        }
+        *reinterpret_cast<kpn_f32x4*>(dlow + i * 4) = acc;
     }
 }
 

@@ -18,8 +18,10 @@ does not.  The texture encoder is off by default: on the 3 x 512^2 source set it
 ``install_native_convs(module)`` is a separate opt-in for training: it puts torch.ops.kpnerf.conv2d (HIP forward and backward of one
 stride-1 convolution) behind the eligible ``nn.Conv2d`` instances of a module tree; ``uninstall_native_convs`` undoes it.
 ``install_native_norms`` does the same for ``nn.GroupNorm`` / ``nn.InstanceNorm2d`` (torch.ops.kpnerf.group_norm), and
-``install_native_blocks`` rebinds whole ConvBlocks to ``group_norm(relu=True)`` + ``conv2d`` legs.  The three are independent:
-they rebind different modules, so they compose and uninstall in any order.
+``install_native_blocks`` rebinds whole ConvBlocks to ``group_norm(relu=True)`` + ``conv2d`` legs.  ``install_native_hourglass``
+rebinds a whole HourGlass to its own recursion with torch.ops.kpnerf.avg_pool2 and torch.ops.kpnerf.upsample2x_add between the
+blocks, whatever forward those have.  The four are independent: they rebind different modules, so they compose and uninstall in
+any order.
 """
 import types
 
@@ -377,9 +379,11 @@ def uninstall_native_convs(module):
 
 # ---- training normalisations natively: torch.ops.kpnerf.group_norm behind nn.GroupNorm / nn.InstanceNorm2d ----
 class NativeTraining:
-    """native forward calls served by the rebound norms and blocks of all modules (the tests assert that a call was served natively)"""
+    """native forward calls served by the rebound norms, blocks and hourglasses of all modules (the tests assert that a call was served
+    natively)"""
     norm_calls = 0
     block_calls = 0
+    hourglass_calls = 0
 
 
 def _pow2_channels(C):
@@ -514,3 +518,63 @@ def install_native_blocks(module):
 def uninstall_native_blocks(module):
     """Restores what ``forward`` was on every ConvBlock ``install_native_blocks`` rebound."""
     return _restore_forward(module, "_kpnerf_block_saved")
+
+
+# ---- a whole HourGlass natively: avg_pool2 and upsample2x_add between whatever forwards its ConvBlocks have ----
+def _hourglass_ineligible(m):
+    """None if this HourGlass has the reference's structure (src/utils.py:261-306) and a channel count the resampling kernels serve,
+    else the reason it is left on torch"""
+    depth, features = getattr(m, "depth", None), getattr(m, "features", None)
+    if not isinstance(depth, int) or isinstance(depth, bool) or depth < 1:
+        return f"depth={depth!r} (an integer >= 1)"
+    want = [f"b{j}_{k}" for k in range(1, depth + 1) for j in (1, 2, 3)] + ["b2_plus_1"]
+    missing = [n for n in want if not isinstance(m._modules.get(n), torch.nn.Module)]
+    if missing:
+        return f"missing children {', '.join(missing)}"
+    if not isinstance(features, int) or isinstance(features, bool) or features < 4 or features % 4:
+        return f"features={features!r} (a positive multiple of 4)"
+    return None
+
+
+def install_native_hourglass(module):
+    """Opt-in: rebinds ``forward`` on every HourGlass under ``module`` whose structure is the reference's (an integer ``depth`` >= 1,
+    children ``b1_k``, ``b2_k``, ``b3_k`` for k = 1 .. depth and ``b2_plus_1``, ``features`` a multiple of 4) to the same recursion
+    (src/utils.py:287-306) with torch.ops.kpnerf.avg_pool2 in place of ``avg_pool2d`` and torch.ops.kpnerf.upsample2x_add in place of
+    ``up1 + interpolate(...)``, forward and backward in HIP.  The blocks run whatever forward they have, so this composes with
+    ``install_native_blocks`` / ``install_native_norms`` / ``install_native_convs`` in any order.  Input that is not a CUDA fp32
+    (N, C, H, W) tensor with H and W divisible by 2^depth goes to the original forward.  The module tree, the parameter names and the
+    state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of the HourGlasses left alone."""
+    uninstall_native_hourglass(module)
+    served, left = [], {}
+    for name, m in module.named_modules():
+        if type(m).__name__ != "HourGlass":
+            continue
+        why = _hourglass_ineligible(m)
+        if why is not None:
+            left[name] = why
+            continue
+        prev = m.forward
+        m._kpnerf_hourglass_saved = m.__dict__.get("forward")
+
+        def forward(self, x, _prev=prev):
+            if not _native_input(x) or x.shape[2] % (1 << self.depth) or x.shape[3] % (1 << self.depth):
+                return _prev(x)
+            NativeTraining.hourglass_calls += 1
+
+            def run(level, inp):
+                up1 = self._modules[f"b1_{level}"](inp)
+                low = self._modules[f"b2_{level}"](torch.ops.kpnerf.avg_pool2(inp))
+                low = run(level - 1, low) if level > 1 else self._modules[f"b2_plus_{level}"](low)
+                low = self._modules[f"b3_{level}"](low)
+                return torch.ops.kpnerf.upsample2x_add(low, up1)
+
+            return run(self.depth, x)
+
+        m.forward = types.MethodType(forward, m)
+        served.append(name)
+    return served, left
+
+
+def uninstall_native_hourglass(module):
+    """Restores what ``forward`` was on every HourGlass ``install_native_hourglass`` rebound."""
+    return _restore_forward(module, "_kpnerf_hourglass_saved")

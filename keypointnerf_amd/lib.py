@@ -91,6 +91,11 @@ class GroupNormDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "C", "G", "affine", "relu")] + [("eps", c_f)]
 
 
+class ResampleDesc(ctypes.Structure):
+    """struct kpn_resample2_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "h", "w", "C")]
+
+
 # name -> (restype, argtypes); mirrors include/kpnerf.h one to one
 _SIGNATURES = {
     "kpn_abi_version": (ctypes.c_int, []),
@@ -196,8 +201,12 @@ _SIGNATURES = {
     "kpn_group_norm_workspace_bytes": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
     "kpn_group_norm_forward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_group_norm_backward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_avg_pool2_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
+    "kpn_avg_pool2_backward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
+    "kpn_upsample2x_add_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p, c_p]),
+    "kpn_upsample2x_add_backward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
 }
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class KpnError(RuntimeError):

@@ -1072,3 +1072,80 @@ def group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=True, w
         L.check(L.kpn_group_norm_backward(ctypes.byref(d), _p(x), _p(dy), _p(w), _p(stats.contiguous()), _p(dx), _p(dw), _p(db), _p(ws), nb,
                                           _stream()))
     return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+
+
+# ------------------------------------------------------------------------------------------------
+# The two resampling steps of an HourGlass and their gradients (kpn_avg_pool2_* / kpn_upsample2x_add_*; avg_pool2d(x, 2, stride=2)
+# and skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) with their autograd, reference
+# src/utils.py:287-306).  Activations are channels_last tensors of logical shape (N, C, H, W).
+def _resample_desc(N, h, w, C):
+    if C % 4:
+        raise ValueError(f"channels must be a multiple of 4, got {C}")
+    d = kl.ResampleDesc()
+    d.N, d.h, d.w, d.C = int(N), int(h), int(w), int(C)
+    return d
+
+
+def _resample_out(N, C, H, W, device):
+    return torch.empty(N, C, H, W, dtype=_f32, device=device, memory_format=torch.channels_last)
+
+
+def avg_pool2_forward(x):
+    """avg_pool2d(x, 2, stride=2) (kpn_avg_pool2_forward).  x: (N, C, 2h, 2w) channels_last; returns (N, C, h, w) channels_last."""
+    L = kl.get_library()
+    x = _conv_cl(x, "x")
+    N, C, H, W = x.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"x must have even, positive height and width, got {tuple(x.shape)}")
+    d = _resample_desc(N, H // 2, W // 2, C)
+    y = _resample_out(N, C, H // 2, W // 2, x.device)
+    L.check(L.kpn_avg_pool2_forward(ctypes.byref(d), _p(x), _p(y), _stream()))
+    return y
+
+
+def avg_pool2_backward(dy):
+    """dx of avg_pool2_forward for the output gradient dy (N, C, h, w) channels_last (kpn_avg_pool2_backward): (N, C, 2h, 2w)
+    channels_last, 0.25 dy under every pixel of a window."""
+    L = kl.get_library()
+    dy = _conv_cl(dy, "dy")
+    N, C, h, w = dy.shape
+    d = _resample_desc(N, h, w, C)
+    dx = _resample_out(N, C, 2 * h, 2 * w, dy.device)
+    L.check(L.kpn_avg_pool2_backward(ctypes.byref(d), _p(dy), _p(dx), _stream()))
+    return dx
+
+
+def upsample2x_add_forward(low, skip=None, out=None):
+    """skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True), or the interpolation alone for skip = None
+    (kpn_upsample2x_add_forward).  low: (N, C, h, w), skip: (N, C, 2h, 2w), both channels_last.  out: None (a new tensor) or a
+    channels_last (N, C, 2h, 2w) tensor to write, which may be skip itself.  Returns (N, C, 2h, 2w) channels_last."""
+    L = kl.get_library()
+    low = _conv_cl(low, "low")
+    N, C, h, w = low.shape
+    high = (N, C, 2 * h, 2 * w)
+    if skip is not None:
+        skip = _conv_cl(skip, "skip")
+        if tuple(skip.shape) != high:
+            raise ValueError(f"skip must be {high}, got {tuple(skip.shape)}")
+    if out is not None:
+        out = _conv_cl(out, "out")
+        if tuple(out.shape) != high:
+            raise ValueError(f"out must be {high}, got {tuple(out.shape)}")
+    d = _resample_desc(N, h, w, C)
+    y = _resample_out(N, C, 2 * h, 2 * w, low.device) if out is None else out
+    L.check(L.kpn_upsample2x_add_forward(ctypes.byref(d), _p(low), _p(skip), _p(y), _stream()))
+    return y
+
+
+def upsample2x_add_backward(dy):
+    """d_low of upsample2x_add_forward for the output gradient dy (N, C, 2h, 2w) channels_last (kpn_upsample2x_add_backward):
+    (N, C, h, w) channels_last, a gather in a fixed order - bit-identical from run to run.  The gradient of skip is dy itself."""
+    L = kl.get_library()
+    dy = _conv_cl(dy, "dy")
+    N, C, H, W = dy.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"dy must have even, positive height and width, got {tuple(dy.shape)}")
+    d = _resample_desc(N, H // 2, W // 2, C)
+    d_low = _resample_out(N, C, H // 2, W // 2, dy.device)
+    L.check(L.kpn_upsample2x_add_backward(ctypes.byref(d), _p(dy), _p(d_low), _stream()))
+    return d_low

@@ -36,6 +36,11 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
                                  4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
                                  _backward); y is not kept for the backward and may be overwritten in place
+    torch.ops.kpnerf.avg_pool2(x) -> y   avg_pool2d(x, 2, stride=2) (C a multiple of 4, even H and W), channels-last result,
+                                 DIFFERENTIABLE w.r.t. x (kpn_avg_pool2_forward / _backward)
+    torch.ops.kpnerf.upsample2x_add(low, skip?) -> y   skip + bicubic x2 of low (align_corners=True; C a multiple of 4), channels-last
+                                 result, DIFFERENTIABLE w.r.t. low and skip (kpn_upsample2x_add_forward / _backward); the backward is a
+                                 gather without atomics: bit-identical from run to run
 
 ``rgba2out`` and ``render_rays_train`` carry ``register_autograd`` formulas whose backward is itself a registered op
 (``kpnerf::rgba2out_backward``, ``kpnerf::render_rays_train_backward`` = kpn_render_rays_train_backward): gradients reach
@@ -681,3 +686,95 @@ def _group_norm(x, weight, bias, groups, eps, relu):
 
 _fragment.define("group_norm(Tensor x, Tensor? weight, Tensor? bias, int groups, float eps, bool relu) -> Tensor")
 _fragment.impl("group_norm", _group_norm, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.avg_pool2 / upsample2x_add: the two resampling steps of an HourGlass, DIFFERENTIABLE ----
+# Neither backward reads a forward tensor: the pool's gradient is 0.25 dy under each window, the upsample's is the transposed
+# interpolation of dy as a gather in a fixed order (no atomics: bit-identical from run to run) and dy itself for the skip.
+@_lib.custom_op("kpnerf::avg_pool2_cl", mutates_args=(), device_types="cuda")
+def avg_pool2_cl(x: torch.Tensor) -> torch.Tensor:
+    """avg_pool2d(x, 2, stride=2) for a channels_last x (N, C, 2h, 2w), C a multiple of 4 (kpn_avg_pool2_forward): what
+    torch.ops.kpnerf.avg_pool2 runs after its memory-format conversion.  Returns (N, C, h, w) channels_last."""
+    return ops.avg_pool2_forward(x)
+
+
+@avg_pool2_cl.register_fake
+def _(x):
+    N, C, H, W = x.shape
+    return x.new_empty(N, H // 2, W // 2, C).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::avg_pool2_backward", mutates_args=(), device_types="cuda")
+def avg_pool2_backward(dy: torch.Tensor) -> torch.Tensor:
+    """dx (N, C, 2h, 2w) channels_last of kpnerf::avg_pool2_cl for the output gradient dy (N, C, h, w) (kpn_avg_pool2_backward)"""
+    return ops.avg_pool2_backward(dy.contiguous(memory_format=torch.channels_last))
+
+
+@avg_pool2_backward.register_fake
+def _(dy):
+    N, C, h, w = dy.shape
+    return dy.new_empty(N, 2 * h, 2 * w, C).permute(0, 3, 1, 2)
+
+
+def _avg_pool2_bwd(ctx, dy):
+    if dy is None or not ctx.needs_input_grad[0]:
+        return None
+    return torch.ops.kpnerf.avg_pool2_backward(dy)
+
+
+avg_pool2_cl.register_autograd(_avg_pool2_bwd)
+
+
+@_lib.custom_op("kpnerf::upsample2x_add_cl", mutates_args=(), device_types="cuda")
+def upsample2x_add_cl(low: torch.Tensor, skip: Optional[torch.Tensor]) -> torch.Tensor:
+    """skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) for channels_last low (N, C, h, w) and skip
+    (N, C, 2h, 2w), or the interpolation alone for skip = None; C a multiple of 4 (kpn_upsample2x_add_forward): what
+    torch.ops.kpnerf.upsample2x_add runs after its memory-format conversion.  Returns (N, C, 2h, 2w) channels_last."""
+    return ops.upsample2x_add_forward(low, skip)
+
+
+@upsample2x_add_cl.register_fake
+def _(low, skip):
+    N, C, h, w = low.shape
+    return low.new_empty(N, 2 * h, 2 * w, C).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::upsample2x_add_backward", mutates_args=(), device_types="cuda")
+def upsample2x_add_backward(dy: torch.Tensor) -> torch.Tensor:
+    """d_low (N, C, h, w) channels_last of kpnerf::upsample2x_add_cl for the output gradient dy (N, C, 2h, 2w)
+    (kpn_upsample2x_add_backward)"""
+    return ops.upsample2x_add_backward(dy.contiguous(memory_format=torch.channels_last))
+
+
+@upsample2x_add_backward.register_fake
+def _(dy):
+    N, C, H, W = dy.shape
+    return dy.new_empty(N, H // 2, W // 2, C).permute(0, 3, 1, 2)
+
+
+def _upsample2x_add_bwd(ctx, dy):
+    if dy is None:
+        return None, None
+    need = ctx.needs_input_grad
+    d_low = torch.ops.kpnerf.upsample2x_add_backward(dy) if need[0] else None      # computed only if low needs it
+    return d_low, (dy if need[1] else None)                                        # the skip's gradient is dy itself
+
+
+upsample2x_add_cl.register_autograd(_upsample2x_add_bwd)
+
+
+# torch.ops.kpnerf.avg_pool2(x) / upsample2x_add(low, skip): tensors in any memory format, converted to channels_last once (as
+# kpnerf::conv2d does); the results are channels_last.
+def _avg_pool2(x):
+    return torch.ops.kpnerf.avg_pool2_cl(x.contiguous(memory_format=torch.channels_last))
+
+
+def _upsample2x_add(low, skip):
+    cl = torch.channels_last
+    return torch.ops.kpnerf.upsample2x_add_cl(low.contiguous(memory_format=cl), None if skip is None else skip.contiguous(memory_format=cl))
+
+
+_fragment.define("avg_pool2(Tensor x) -> Tensor")
+_fragment.impl("avg_pool2", _avg_pool2, "CompositeImplicitAutograd")
+_fragment.define("upsample2x_add(Tensor low, Tensor? skip) -> Tensor")
+_fragment.impl("upsample2x_add", _upsample2x_add, "CompositeImplicitAutograd")

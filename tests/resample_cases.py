@@ -1,0 +1,260 @@
+"""Test infrastructure of the native resampling steps of an HourGlass (kpn_avg_pool2_* / kpn_upsample2x_add_*): the cases, their fp64
+reference, the bar and one driver of the C ABI that runs on host arrays (the emulator build) and on device tensors (the product
+library) alike.
+
+Reference: seeded normal x, low, skip and seed gradients give y and the gradients of torch.nn.functional.avg_pool2d(x, 2, stride=2)
+and skip + torch.nn.functional.interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) through torch.autograd.grad on the
+CPU in fp64.  e_ref is the max deviation of the same computation in CPU fp32 from that, per tensor.  The bar, for every element:
+|native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) - the project's standing rule and factor (tests/conv_cases.py).
+"""
+import ctypes
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from keypointnerf_amd import lib as kl
+from tests.conv_cases import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
+
+# low sizes; what each case can catch:
+CASES = {
+    # scale 0: all 16 taps clamp to the one pixel
+    "one": dict(N=1, C=4, h=1, w=1),
+    # every tap range touches a border; not square: h / w swaps
+    "clamp": dict(N=2, C=8, h=2, w=3),
+    # low rows and columns whose contributors are all unclamped; odd width
+    "interior": dict(N=1, C=4, h=6, w=5),
+    # the hourglass's lowest level; batch
+    "hg": dict(N=2, C=16, h=4, w=4),
+    # a channel count that is no power of two
+    "c260": dict(N=1, C=260, h=2, w=2),
+}
+# the device only: a high tensor of 2.36 M float4 > 8192 * 256 threads - the second grid-stride iteration of every kernel indexed over
+# the high tensor
+GPU_CASES = dict(CASES, stride=dict(N=1, C=64, h=192, w=192))
+TENSORS = ("pool_y", "pool_dx", "up_y", "up_dlow")
+
+
+def desc(c, **over):
+    d = kl.ResampleDesc()
+    v = dict(c)
+    v.update(over)
+    for n in ("N", "h", "w", "C"):
+        setattr(d, n, int(v[n]))
+    return d
+
+
+def inputs(c):
+    """x (N, C, 2h, 2w), g_low (N, C, h, w): the pool's input and output gradient; low (N, C, h, w), skip and g_high (N, C, 2h, 2w): the
+    upsample's inputs and output gradient.  Seeded normal, fp32, NCHW, drawn in this order."""
+    gen = torch.Generator().manual_seed(1000)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float32)
+    lo, hi = (c["N"], c["C"], c["h"], c["w"]), (c["N"], c["C"], 2 * c["h"], 2 * c["w"])
+    return dict(x=r(*hi), g_low=r(*lo), low=r(*lo), skip=r(*hi), g_high=r(*hi))
+
+
+def _torch_run(t, dtype):
+    x, low, skip = (t[k].clone().to(dtype).requires_grad_(True) for k in ("x", "low", "skip"))
+    py = F.avg_pool2d(x, 2, stride=2)
+    uy = skip + F.interpolate(low, scale_factor=2, mode="bicubic", align_corners=True)
+    pdx, = torch.autograd.grad(py, x, t["g_low"].to(dtype))
+    dlow, dskip = torch.autograd.grad(uy, [low, skip], t["g_high"].to(dtype))
+    assert torch.equal(dskip, t["g_high"].to(dtype))                    # the skip's gradient is dy itself
+    return {"pool_y": py.detach().numpy(), "pool_dx": pdx.numpy(), "up_y": uy.detach().numpy(), "up_dlow": dlow.numpy()}
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """-> (inputs, {tensor: fp64 array (NCHW)}, {tensor: e_ref}); computed once per case and shared"""
+    t = inputs(GPU_CASES[name])
+    r64, r32 = _torch_run(t, torch.float64), _torch_run(t, torch.float32)
+    e_ref = {k: float(np.abs(r32[k].astype(np.float64) - r64[k]).max()) for k in r64}
+    for v in r64.values():
+        v.setflags(write=False)
+    return t, r64, e_ref
+
+
+def check(label, native, f64, e_ref):
+    assert np.isfinite(np.asarray(native)).all(), label
+    r = ratio(native, f64, e_ref)
+    print(f"[resample parity] {label}: ratio {r:.3f} (e_ref {e_ref:.3e}, bar {FACTOR:g})")
+    assert r <= FACTOR, (label, r, e_ref)
+    return r
+
+
+def _low(c):
+    return (c["N"], c["h"], c["w"], c["C"])
+
+
+def _high(c):
+    return (c["N"], 2 * c["h"], 2 * c["w"], c["C"])
+
+
+def pool_forward(L, B, c, x_nhwc):
+    """kpn_avg_pool2_forward -> y NHWC (numpy)"""
+    y, x_dev = B.full(_low(c), np.nan), B.put(x_nhwc)
+    L.check(L.kpn_avg_pool2_forward(ctypes.byref(desc(c)), B.ptr(x_dev), B.ptr(y), B.stream))
+    return B.get(y)
+
+
+def pool_backward(L, B, c, dy_nhwc):
+    """kpn_avg_pool2_backward -> dx NHWC (numpy)"""
+    dx, dy_dev = B.full(_high(c), np.nan), B.put(dy_nhwc)
+    L.check(L.kpn_avg_pool2_backward(ctypes.byref(desc(c)), B.ptr(dy_dev), B.ptr(dx), B.stream))
+    return B.get(dx)
+
+
+def up_forward(L, B, c, low_nhwc, skip_nhwc=None, in_place=False):
+    """kpn_upsample2x_add_forward -> y NHWC (numpy); in_place: y is the skip buffer itself"""
+    low_dev = B.put(low_nhwc)
+    skip_dev = None if skip_nhwc is None else B.put(skip_nhwc)
+    y = skip_dev if in_place else B.full(_high(c), np.nan)
+    L.check(L.kpn_upsample2x_add_forward(ctypes.byref(desc(c)), B.ptr(low_dev), B.ptr(skip_dev), B.ptr(y), B.stream))
+    return B.get(y)
+
+
+def up_backward(L, B, c, dy_nhwc):
+    """kpn_upsample2x_add_backward -> d_low NHWC (numpy)"""
+    d_low, dy_dev = B.full(_low(c), np.nan), B.put(dy_nhwc)
+    L.check(L.kpn_upsample2x_add_backward(ctypes.byref(desc(c)), B.ptr(dy_dev), B.ptr(d_low), B.stream))
+    return B.get(d_low)
+
+
+def run(L, B, name, c=None, t=None):
+    """the four calls of one case through the C ABI -> {tensor: NHWC numpy}"""
+    c = GPU_CASES[name] if c is None else c
+    t = reference(name)[0] if t is None else t
+    return {"pool_y": pool_forward(L, B, c, nhwc(t["x"])), "pool_dx": pool_backward(L, B, c, nhwc(t["g_low"])),
+            "up_y": up_forward(L, B, c, nhwc(t["low"]), nhwc(t["skip"])), "up_dlow": up_backward(L, B, c, nhwc(t["g_high"]))}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- the properties both builds are held to (tests/test_resample_cpu.py on the emulator, tests/test_gpu_resample.py on the device) ----
+def check_case(L, B, name):
+    """y and the gradients of both operators against the fp64 reference, each within the bar; -> {tensor: ratio}"""
+    _, r64, e_ref = reference(name)
+    out = run(L, B, name)
+    return {k: check(f"{name} {k}", nchw(out[k]), r64[k], e_ref[k]) for k in TENSORS}
+
+
+def check_pool_backward_is_exact(L, B, name):
+    c = GPU_CASES[name]
+    g = nhwc(reference(name)[0]["g_low"])
+    want = np.repeat(np.repeat(np.float32(0.25) * g, 2, axis=1), 2, axis=2)
+    assert want.dtype == np.float32
+    assert np.array_equal(bits(pool_backward(L, B, c, g)), bits(want))
+
+
+def check_skip_forms_agree(L, B, name):
+    """with skip = float32(skip + without skip), and y written over skip has the same bits"""
+    c = GPU_CASES[name]
+    t = reference(name)[0]
+    low, skip = nhwc(t["low"]), nhwc(t["skip"])
+    alone, added = up_forward(L, B, c, low), up_forward(L, B, c, low, skip)
+    assert np.array_equal(bits(added), bits(skip + alone))
+    assert np.array_equal(bits(up_forward(L, B, c, low, skip, in_place=True)), bits(added))
+
+
+def check_two_calls_equal_bits(L, B, name):
+    a, b = run(L, B, name), run(L, B, name)
+    for k in TENSORS:
+        assert np.array_equal(bits(a[k]), bits(b[k])), k
+
+
+def check_an_image_does_not_depend_on_its_batch(L, B, name="clamp"):
+    """image 0 of the case alone and inside its batch: equal bits in every output"""
+    c = GPU_CASES[name]
+    assert c["N"] > 1
+    t = reference(name)[0]
+    both = run(L, B, name)
+    alone = run(L, B, name, c=dict(c, N=1), t={k: v[:1] for k, v in t.items()})
+    for k in TENSORS:
+        assert np.array_equal(bits(alone[k]), bits(both[k][:1])), k
+
+
+def check_zero_dy_gives_zeros(L, B, name):
+    c = GPU_CASES[name]
+    assert (pool_backward(L, B, c, np.zeros(_low(c), np.float32)) == 0.0).all()
+    assert (up_backward(L, B, c, np.zeros(_high(c), np.float32)) == 0.0).all()
+
+
+def check_refusals(L, B):
+    """every bad descriptor, NULL pointer and misaligned pointer of the four entries: -1, the word in the message, nothing launched"""
+    c = GPU_CASES["clamp"]
+    t = reference("clamp")[0]
+    lo_in, hi_in = B.put(nhwc(t["low"])), B.put(nhwc(t["skip"]))
+    lo_out, hi_out = B.full(_low(c), CANARY), B.full(_high(c), CANARY)
+
+    def off4(a):
+        """the buffer's address 4 bytes on: misaligned"""
+        return ctypes.c_void_p(B.ptr(a).value + 4)
+
+    # entry -> its call with (descriptor, input pointer, output pointer)
+    calls = {
+        "pool_fwd": (lambda d, i, o: L.kpn_avg_pool2_forward(ctypes.byref(d), i, o, B.stream), hi_in, lo_out),
+        "pool_bwd": (lambda d, i, o: L.kpn_avg_pool2_backward(ctypes.byref(d), i, o, B.stream), lo_in, hi_out),
+        "up_fwd": (lambda d, i, o: L.kpn_upsample2x_add_forward(ctypes.byref(d), i, None, o, B.stream), lo_in, hi_out),
+        "up_bwd": (lambda d, i, o: L.kpn_upsample2x_add_backward(ctypes.byref(d), i, o, B.stream), hi_in, lo_out),
+    }
+    for entry, (call, src, dst) in calls.items():
+        for over, word in ((dict(N=0), b"N, h, w"), (dict(h=0), b"N, h, w"), (dict(w=-1), b"N, h, w"), (dict(C=6), b"C must"),
+                           (dict(C=0), b"C must")):
+            assert call(desc(c, **over), B.ptr(src), B.ptr(dst)) == -1, (entry, over)
+            assert word in L.kpn_last_error(), (entry, over, L.kpn_last_error())
+        d = desc(c)
+        assert call(d, None, B.ptr(dst)) == -1 and b"null" in L.kpn_last_error(), entry
+        assert call(d, B.ptr(src), None) == -1 and b"null" in L.kpn_last_error(), entry
+        assert call(d, off4(src), B.ptr(dst)) == -1 and b"aligned" in L.kpn_last_error(), entry
+        assert call(d, B.ptr(src), off4(dst)) == -1 and b"aligned" in L.kpn_last_error(), entry
+    d = desc(c)
+    assert L.kpn_upsample2x_add_forward(ctypes.byref(d), B.ptr(lo_in), off4(hi_in), B.ptr(hi_out), B.stream) == -1     # a misaligned skip
+    assert b"aligned" in L.kpn_last_error()
+    assert L.kpn_avg_pool2_forward(None, B.ptr(hi_in), B.ptr(lo_out), B.stream) == -1 and b"desc" in L.kpn_last_error()
+    # a refused call launches nothing
+    assert (B.get(lo_out) == CANARY).all() and (B.get(hi_out) == CANARY).all()
+    for entry, (call, src, dst) in calls.items():
+        assert call(d, B.ptr(src), B.ptr(dst)) == 0, entry
+    assert not (B.get(lo_out) == CANARY).any() and not (B.get(hi_out) == CANARY).any()
+
+
+# ---- the stand-ins of the installer tests ----
+class HourGlass(torch.nn.Module):
+    """the reference's recursion (src/utils.py:261-306) around 1x1 convolutions instead of ConvBlocks: no ReLU whose mask a rounding
+    could flip, so the wiring of install_native_hourglass is held to the plain bar"""
+
+    def __init__(self, depth, features, block=None):
+        super().__init__()
+        self.depth, self.features = depth, features
+        self._block = block or (lambda: torch.nn.Conv2d(features, features, 1))
+        self._make(depth)
+
+    def _make(self, level):
+        self.add_module(f"b1_{level}", self._block())
+        self.add_module(f"b2_{level}", self._block())
+        if level > 1:
+            self._make(level - 1)
+        else:
+            self.add_module(f"b2_plus_{level}", self._block())
+        self.add_module(f"b3_{level}", self._block())
+
+    def _run(self, level, x):
+        up1 = self._modules[f"b1_{level}"](x)
+        low = self._modules[f"b2_{level}"](F.avg_pool2d(x, 2, stride=2))
+        low = self._run(level - 1, low) if level > 1 else self._modules[f"b2_plus_{level}"](low)
+        low = self._modules[f"b3_{level}"](low)
+        return up1 + F.interpolate(low, scale_factor=2, mode="bicubic", align_corners=True)
+
+    def forward(self, x):
+        return self._run(self.depth, x)
+
+
+def seed_parameters(net, seed):
+    """the seeding of tests/test_norm_cpu.py::_block_net"""
+    with torch.no_grad():
+        for i, p in enumerate(net.parameters()):
+            p.copy_(torch.randn(p.shape, generator=torch.Generator().manual_seed(100 * seed + i)) * (0.3 if p.dim() > 1 else 1.0))
+    return net
