@@ -1,26 +1,10 @@
 // ---------------------------------------------------------------------------------------------
 // One stride-1 convolution, forward and its three gradients (torch.nn.functional.conv2d and its autograd, as the encoders use
 // them: reference src/utils.py:416-474, 261-309, 322-414).  Kernels: encoder_kernels.hip.  The forward and the input gradient
-// are k_enc_conv over two packed copies of the weight (tile choice and split-K rule of the encoder walk, enc::Ctx); the weight
-// gradient is k_enc_wgrad / k_enc_wgrad_combine, the bias gradient k_enc_dbias_partial / k_enc_dbias_final.
+// are k_enc_conv over two packed copies of the weight, sized and launched by the launch layer at the head of api_encoders.hip
+// (enc::conv_geom / enc::launch_conv: the walk's own tiles and split K); the weight gradient is k_enc_wgrad / k_enc_wgrad_combine
+// on the forward's tile, the bias gradient k_enc_dbias_partial / k_enc_dbias_final.
 namespace conv {
-// one k_enc_conv GEMM: cin -> cout over (H, W) -> (Ho, Wo)
-struct Gemm {
-    int cin, cout, bn, bm, cout_p, nk, ksplit;
-    int64_t packed;        // floats of its packed weight
-    int64_t partial;       // floats of its split-K scratch
-};
-Gemm gemm(int N, int Ho, int Wo, int cin, int cout, int k) {
-    Gemm g{};
-    g.cin = cin; g.cout = cout;
-    g.bn = enc::Ctx::tile_n(cout); g.bm = g.bn == 64 ? 64 : 128;
-    g.cout_p = (cout + g.bn - 1) / g.bn * g.bn;
-    g.nk = (k * k * cin + 15) / 16;
-    g.ksplit = enc::Ctx::ksplit_of(Ho, Wo, g.bm, g.bn, g.cout_p, 1, g.nk);
-    g.packed = (int64_t)g.nk * g.cout_p * 16;
-    g.partial = g.ksplit > 1 ? (int64_t)g.ksplit * N * Ho * Wo * g.cout_p : 0;
-    return g;
-}
 // what the packed copies depend on
 const char* weight_error(const kpn_conv2d_desc* d) {
     if (!d) return "desc is null";
@@ -42,19 +26,18 @@ const char* desc_error(const kpn_conv2d_desc* d) {
 // and combine are worth) and otherwise as many as leave about 1024 workgroups, at most 64 ranges.  From the shape alone.
 struct Plan {
     int Ho, Wo;
-    Gemm fwd, dx;
-    int wg_bn, wg_bm, wg_tiles, krows, nchunks, cpr, nranges, db_chunks;
+    enc::ConvGeom fwd, dx;
+    int wg_tiles, krows, nchunks, cpr, nranges, db_chunks;
     size_t o_fwd, o_dx, o_wg, o_db, bytes;
 };
 Plan plan(const kpn_conv2d_desc* d) {
     Plan p{};
     p.Ho = d->H + 2 * d->pad - d->k + 1; p.Wo = d->W + 2 * d->pad - d->k + 1;
-    p.fwd = gemm(d->N, p.Ho, p.Wo, d->cin, d->cout, d->k);
-    p.dx = gemm(d->N, d->H, d->W, d->cout, d->cin, d->k);
-    const int64_t M = (int64_t)d->N * p.Ho * p.Wo;
-    p.wg_bn = enc::Ctx::tile_n(d->cout); p.wg_bm = p.wg_bn == 64 ? 64 : 128;
+    p.fwd = enc::conv_geom(d->N, p.Ho, p.Wo, d->cin, d->cout, d->k, d->k, 0);
+    p.dx = enc::conv_geom(d->N, d->H, d->W, d->cout, d->cin, d->k, d->k, 0);
+    const int64_t M = p.fwd.M;
     p.krows = d->k * d->k * d->cin;
-    p.wg_tiles = (p.krows + p.wg_bm - 1) / p.wg_bm * ((d->cout + p.wg_bn - 1) / p.wg_bn);
+    p.wg_tiles = (p.krows + p.fwd.bm - 1) / p.fwd.bm * (p.fwd.a.cout_p / p.fwd.bn);      // the forward's tile over (K rows, cout)
     p.nchunks = (int)((M + 15) / 16);
     const int rmax = std::max(1, std::min(64, 1024 / p.wg_tiles));
     p.cpr = std::max(20, (p.nchunks + rmax - 1) / rmax);
@@ -69,27 +52,16 @@ Plan plan(const kpn_conv2d_desc* d) {
     p.bytes = std::max<size_t>(std::max(f.o, b.o), 256);
     return p;
 }
-void pack(const Gemm& g, int k, int tflip, const float* w, float* out, void* stream) {
-    kpn_enc_pack_args pa{w, out, g.cin, g.cin, g.cout, g.cout_p, k, k, g.nk, 0, 0, tflip};
-    KPN_LAUNCH(k_enc_pack, dim3((unsigned)std::min<int64_t>((g.packed + 255) / 256, 4096)), dim3(256), stream, pa);
-}
 // dst (N, Ho, Wo, cout) = conv(src (N, Hs, Ws, cin), wp, pad) [+ bias]
-void run(const Gemm& g, int N, int Hs, int Ws, int Ho, int Wo, int k, int pad, const float* src, const float* wp, const float* bias,
-         float* dst, float* partial, void* stream) {
-    kpn_enc_conv_args a{};
-    a.nimg = N; a.Ho = Ho; a.Wo = Wo; a.Hs = Hs; a.Ws = Ws;
-    a.cin = g.cin; a.cin_p = g.cin;
-    a.kh = k; a.kw = k; a.stride = 1; a.pad = pad;
-    a.nk[0] = g.nk; a.ksplit = g.ksplit;
-    a.src = src; a.src_cs = g.cin;
-    a.wp = wp; a.cout = g.cout; a.cout_p = g.cout_p; a.bias = bias;
-    a.dst = dst; a.dst_cs = g.cout;
-    a.partial = g.ksplit > 1 ? partial : nullptr;
-    const int64_t M = (int64_t)N * Ho * Wo;
-    const dim3 grid((unsigned)((M + g.bm - 1) / g.bm * (g.cout_p / g.bn)), (unsigned)g.ksplit);
-    if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, false>), grid, dim3(256), stream, a);
-    else KPN_LAUNCH((k_enc_conv<128, 32, false, false>), grid, dim3(256), stream, a);
-    if (g.ksplit > 1) KPN_LAUNCH(k_enc_combine, dim3((unsigned)std::min<int64_t>((M * g.cout + 255) / 256, 8192)), dim3(256), stream, a, 0);
+void run(const enc::ConvGeom& g, int Hs, int Ws, int pad, const float* src, const float* wp, const float* bias, float* dst, float* partial,
+         void* stream) {
+    kpn_enc_conv_args a = g.a;
+    a.Hs = Hs; a.Ws = Ws; a.stride = 1; a.pad = pad;
+    a.src = src; a.src_cs = a.cin;
+    a.wp = wp; a.bias = bias;
+    a.dst = dst; a.dst_cs = a.cout;
+    a.partial = g.partial ? partial : nullptr;
+    enc::launch_conv(a, g, 0, stream);
 }
 }  // namespace conv
 
@@ -97,15 +69,17 @@ void run(const Gemm& g, int N, int Hs, int Ws, int Ho, int Wo, int k, int pad, c
 
 extern "C" size_t kpn_conv2d_packed_floats(const kpn_conv2d_desc* desc) {
     if (conv::weight_error(desc)) return 0;
-    return (size_t)(conv::gemm(1, 1, 1, desc->cin, desc->cout, desc->k).packed + conv::gemm(1, 1, 1, desc->cout, desc->cin, desc->k).packed);
+    const int k = desc->k;
+    return (size_t)(enc::conv_geom(1, 1, 1, desc->cin, desc->cout, k, k, 0).packed + enc::conv_geom(1, 1, 1, desc->cout, desc->cin, k, k, 0).packed);
 }
 extern "C" int kpn_conv2d_pack_device(const kpn_conv2d_desc* desc, const float* w_oihw, float* packed, void* stream) {
     if (const char* e = conv::weight_error(desc)) return fail(KPN_EINVAL, std::string("kpn_conv2d_desc: ") + e);
     KPN_REQUIRE(w_oihw && packed, "null pointer");
     KPN_REQUIRE(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
-    const conv::Gemm f = conv::gemm(1, 1, 1, desc->cin, desc->cout, desc->k), b = conv::gemm(1, 1, 1, desc->cout, desc->cin, desc->k);
-    conv::pack(f, desc->k, 0, w_oihw, packed, stream);
-    conv::pack(b, desc->k, 1, w_oihw, packed + f.packed, stream);
+    const int k = desc->k;
+    const enc::ConvGeom f = enc::conv_geom(1, 1, 1, desc->cin, desc->cout, k, k, 0), b = enc::conv_geom(1, 1, 1, desc->cout, desc->cin, k, k, 0);
+    enc::launch_pack(f, 0, w_oihw, packed, stream);
+    enc::launch_pack(b, 1, w_oihw, packed + f.packed, stream);
     return check_launch("kpn_conv2d_pack_device");
 }
 extern "C" size_t kpn_conv2d_workspace_bytes(const kpn_conv2d_desc* desc) {
@@ -123,7 +97,7 @@ extern "C" int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, c
     const conv::Plan p = conv::plan(desc);
     KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv2d_workspace_bytes)");
     char* ws = static_cast<char*>(workspace);
-    conv::run(p.fwd, desc->N, desc->H, desc->W, p.Ho, p.Wo, desc->k, desc->pad, x, packed, bias, y, reinterpret_cast<float*>(ws + p.o_fwd), stream);
+    conv::run(p.fwd, desc->H, desc->W, desc->pad, x, packed, bias, y, reinterpret_cast<float*>(ws + p.o_fwd), stream);
     return check_launch("kpn_conv2d_forward");
 }
 extern "C" int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, const float* dy, const float* packed, float* dx,
@@ -139,22 +113,18 @@ extern "C" int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, 
     char* ws = static_cast<char*>(workspace);
     const int k = desc->k;
     if (dx)     // dX = conv(dY, w'[ci][co][k - 1 - ky][k - 1 - kx], pad k - 1 - p)
-        conv::run(p.dx, desc->N, p.Ho, p.Wo, desc->H, desc->W, k, k - 1 - desc->pad, dy, packed + p.fwd.packed, nullptr, dx,
-                  reinterpret_cast<float*>(ws + p.o_dx), stream);
+        conv::run(p.dx, p.Ho, p.Wo, k - 1 - desc->pad, dy, packed + p.fwd.packed, nullptr, dx, reinterpret_cast<float*>(ws + p.o_dx), stream);
     if (dw) {
         kpn_enc_wgrad_args a{};
-        a.c.nimg = desc->N; a.c.Ho = p.Ho; a.c.Wo = p.Wo; a.c.Hs = desc->H; a.c.Ws = desc->W;
-        a.c.cin = desc->cin; a.c.cin_p = desc->cin;
-        a.c.kh = k; a.c.kw = k; a.c.stride = 1; a.c.pad = desc->pad;
+        a.c = p.fwd.a;
+        a.c.Hs = desc->H; a.c.Ws = desc->W; a.c.stride = 1; a.c.pad = desc->pad;
         a.c.src = x; a.c.src_cs = desc->cin;
-        a.c.cout = desc->cout; a.c.cout_p = (desc->cout + p.wg_bn - 1) / p.wg_bn * p.wg_bn;
         a.dy = dy; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
         a.partial = reinterpret_cast<float*>(ws + p.o_wg); a.dw = dw;
         const dim3 grid((unsigned)p.wg_tiles, (unsigned)p.nranges);
-        if (p.wg_bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64>), grid, dim3(256), stream, a);
+        if (p.fwd.bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64>), grid, dim3(256), stream, a);
         else KPN_LAUNCH((k_enc_wgrad<128, 32>), grid, dim3(256), stream, a);
-        const int64_t n = (int64_t)p.krows * desc->cout;
-        KPN_LAUNCH(k_enc_wgrad_combine, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, a);
+        KPN_LAUNCH(k_enc_wgrad_combine, enc::grid4((int64_t)p.krows * desc->cout), dim3(256), stream, a);
     }
     if (db) {
         kpn_enc_dbias_args a{dy, (int64_t)desc->N * p.Ho * p.Wo, desc->cout, p.db_chunks, reinterpret_cast<double*>(ws + p.o_db), db};

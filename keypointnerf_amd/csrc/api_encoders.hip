@@ -4,7 +4,96 @@
 // three modes: COUNT (sizes of the plain and packed parameter vectors, the workspace and the stage buffer), PACK (launch the
 // packers) and RUN (launch the forward).  The order in which a walk asks for parameters defines the plain layout
 // (keypointnerf_amd/encoders.py builds it from the caller's module in the same order).
+//
+// In front of the walks, the launch layer of encoder_kernels.hip: every launch policy of the kernels that the walks share with
+// the differentiable layers (api_conv.hip, api_norm.hip, api_resample.hip) - tiles, split K, chunk counts, grids - is written
+// there once, and all four files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
+// so a walk and a layer agree bit for bit only while they share this code.
 namespace enc {
+
+// the grid of the elementwise kernels (grid-stride loops over n items): blocks of 256 threads, at most 8192 of them
+inline dim3 grid4(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)); }
+
+// one k_enc_conv GEMM: cin -> cout over nimg * Ho * Wo rows (DECONV: (Ho, Wo) is the source grid, one GEMM per parity class)
+struct ConvGeom {
+    kpn_enc_conv_args a;   // what the geometry decides (sizes, cin_p, cout_p, nk, wofs, ksplit); the caller adds tensors, padding, epilogue
+    int bn, bm;            // tile: 64 x 64, or 128 x 32 for at most 32 output channels
+    int deconv, ncls;      // parity classes: 4 or 1
+    int64_t packed;        // floats: the packed weight, every class
+    int64_t M;             // GEMM rows
+    int64_t partial;       // floats: the split-K scratch, 0 without a split
+};
+inline ConvGeom conv_geom(int nimg, int Ho, int Wo, int cin, int cout, int kh, int kw, int deconv) {
+    ConvGeom g{};
+    kpn_enc_conv_args& a = g.a;
+    a.nimg = nimg; a.Ho = Ho; a.Wo = Wo; a.cin = cin; a.cout = cout; a.kh = kh; a.kw = kw;
+    g.bn = cout > 32 ? 64 : 32; g.bm = g.bn == 64 ? 64 : 128;
+    // the 3-channel stems pad to 4; api_conv.hip admits only cin % 4 == 0, for which cin_p == cin: one formula serves both
+    a.cin_p = (cin + 3) / 4 * 4;
+    a.cout_p = (cout + g.bn - 1) / g.bn * g.bn;
+    g.deconv = deconv; g.ncls = deconv ? 4 : 1;
+    int nkmin = 1 << 30;
+    for (int c = 0; c < g.ncls; ++c) {
+        const int taps = deconv ? (1 + (c >> 1)) * (1 + (c & 1)) : kh * kw;
+        a.nk[c] = (taps * a.cin_p + 15) / 16;
+        a.wofs[c] = g.packed;
+        g.packed += (int64_t)a.nk[c] * a.cout_p * 16;
+        nkmin = std::min(nkmin, a.nk[c]);
+    }
+    // split K by the per-image geometry only: an image's result must not depend on how many images are encoded with it
+    const int64_t tiles_img = ((int64_t)Ho * Wo + g.bm - 1) / g.bm * (a.cout_p / g.bn) * g.ncls;
+    a.ksplit = 1;
+    if (tiles_img < 128) a.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nkmin, 16), (256 + tiles_img - 1) / tiles_img));
+    g.M = (int64_t)nimg * Ho * Wo;
+    g.partial = a.ksplit > 1 ? (int64_t)g.ncls * a.ksplit * g.M * a.cout_p : 0;
+    return g;
+}
+// `a`: g.a with the caller's fields filled in
+inline void launch_conv(const kpn_enc_conv_args& a, const ConvGeom& g, int stem, void* stream) {
+    const dim3 grid((unsigned)((g.M + g.bm - 1) / g.bm * (a.cout_p / g.bn)), (unsigned)a.ksplit, (unsigned)g.ncls);
+    if (stem) {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, true, false>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_conv<128, 32, true, false>), grid, dim3(256), stream, a);
+    } else if (g.deconv) {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, true>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_conv<128, 32, false, true>), grid, dim3(256), stream, a);
+    } else {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, false>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_conv<128, 32, false, false>), grid, dim3(256), stream, a);
+    }
+    if (a.ksplit > 1) KPN_LAUNCH(k_enc_combine, grid4((int64_t)g.ncls * g.M * a.cout), dim3(256), stream, a, g.deconv);
+}
+// plain OIHW (DECONV: IOHW) weight `w` -> the packed weight `wp`, every class.  tflip: the operand of the input gradient
+inline void launch_pack(const ConvGeom& g, int tflip, const float* w, float* wp, void* stream) {
+    for (int c = 0; c < g.ncls; ++c) {
+        kpn_enc_pack_args pa{w, wp + g.a.wofs[c], g.a.cin, g.a.cin_p, g.a.cout, g.a.cout_p, g.a.kh, g.a.kw, g.a.nk[c], g.deconv, c, tflip};
+        const int64_t n = (int64_t)g.a.nk[c] * g.a.cout_p * 16;
+        KPN_LAUNCH(k_enc_pack, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), stream, pa);
+    }
+}
+// statistics: pixel chunks per image (from the shape alone; the forward and the backward of a norm share it) and the doubles of
+// the partials [image][chunk][channel][2]
+inline int stats_chunks(int nimg, int HW, int C, int64_t* partial_doubles) {
+    const int nchunks = std::max(1, std::min(64, HW / 256));
+    *partial_doubles = (int64_t)nimg * nchunks * C * 2;
+    return nchunks;
+}
+inline void launch_stats(const kpn_enc_stats_args& a, void* stream) {
+    KPN_LAUNCH(k_enc_stats_partial, dim3((unsigned)a.nchunks, (unsigned)a.nimg), dim3(256), stream, a);
+    KPN_LAUNCH(k_enc_stats_final, dim3((unsigned)((a.nimg * a.G + 63) / 64)), dim3(64), stream, a);
+}
+inline void launch_affine(const float* src, const float* ss, int relu, const float* res, float* dst, int nimg, int HW, int C, void* stream) {
+    KPN_LAUNCH(k_enc_affine, grid4((int64_t)nimg * HW * C / 4), dim3(256), stream, src, ss, relu, res, dst, nimg, HW, C);
+}
+// (h, w) is the low grid of both; a thread writes one float4 (C % 4 == 0) of the output, the high one having 4 h w C / 4 of them
+inline void launch_pool2(const float* high, float* low, int nimg, int h, int w, int C, void* stream) {
+    KPN_LAUNCH(k_enc_pool2, grid4((int64_t)nimg * h * w * C / 4), dim3(256), stream, high, low, nimg, h, w, C);
+}
+inline void launch_upadd(const float* low, const float* skip, float* high, int nimg, int h, int w, int C, void* stream) {
+    KPN_LAUNCH(k_enc_upadd, grid4((int64_t)nimg * h * w * C), dim3(256), stream, low, skip, high, nimg, h, w, C);
+}
+
+// ---- The walks.
 enum Mode { COUNT, PACK, RUN };
 struct View {              // NHWC activations (or a channel slice of them): workspace offset or caller memory
     int64_t off;
@@ -90,55 +179,20 @@ struct Ctx {
         stage_off += n;
     }
 
-    static int tile_n(int cout) { return cout > 32 ? 64 : 32; }
-    // split K by the per-image geometry only: an image's result must not depend on how many images are encoded with it
-    // (api_conv.hip splits its single layers by the same rule)
-    static int ksplit_of(int Ho, int Wo, int bm, int bn, int cout_p, int ncls, int nkmin) {
-        const int64_t tiles_img = ((int64_t)Ho * Wo + bm - 1) / bm * (cout_p / bn) * ncls;
-        int ksplit = 1;
-        if (tiles_img < 128) ksplit = (int)std::min<int64_t>(std::min(nkmin, 16), (256 + tiles_img - 1) / tiles_img);
-        return ksplit < 1 ? 1 : ksplit;
-    }
-    static int taps_of(const ConvSpec& s, int cls) { return s.deconv ? (1 + (cls >> 1)) * (1 + (cls & 1)) : s.kh * s.kw; }
-
     // src: the stem reads `img` instead (stem != 0).  ss: offset of scale / shift in the workspace or -1
     void conv(const ConvSpec& s, const View& src, int64_t ss, int relu_in, const View& dst, const View* res, int relu_out, int stem = 0) {
-        const int bn = tile_n(s.cout), bm = bn == 64 ? 64 : 128;
-        kpn_enc_conv_args a{};
-        a.cin = s.cin; a.cin_p = (s.cin + 3) / 4 * 4;
-        a.cout = s.cout; a.cout_p = (s.cout + bn - 1) / bn * bn;
-        const int ncls = s.deconv ? 4 : 1;
-        int64_t wtotal = 0;
-        int nkmin = 1 << 30;
-        for (int c = 0; c < ncls; ++c) {
-            a.nk[c] = (taps_of(s, c) * a.cin_p + 15) / 16;
-            a.wofs[c] = wtotal;
-            wtotal += (int64_t)a.nk[c] * a.cout_p * 16;
-            if (a.nk[c] < nkmin) nkmin = a.nk[c];
-        }
+        const ConvGeom g = conv_geom(nimg, s.deconv ? src.H : dst.H, s.deconv ? src.W : dst.W, s.cin, s.cout, s.kh, s.kw, s.deconv);
         // parameters: weight, then bias
         const float* wp = packed ? packed + packed_off : nullptr;
-        if (mode == PACK)
-            for (int c = 0; c < ncls; ++c) {
-                kpn_enc_pack_args pa{plain + plain_off, packed + packed_off + a.wofs[c], s.cin, a.cin_p, s.cout, a.cout_p, s.kh, s.kw, a.nk[c], s.deconv, c};
-                const int64_t n = (int64_t)a.nk[c] * a.cout_p * 16;
-                KPN_LAUNCH(k_enc_pack, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), stream, pa);
-            }
+        if (mode == PACK) launch_pack(g, 0, plain + plain_off, packed + packed_off, stream);
         plain_off += (int64_t)s.cout * s.cin * s.kh * s.kw;
-        packed_off += wtotal;
+        packed_off += g.packed;
         const float* bias = s.bias ? vec(s.cout) : nullptr;
-        // geometry
-        a.nimg = nimg;
-        a.Hs = src.H; a.Ws = src.W;
-        if (s.deconv) { a.Ho = src.H; a.Wo = src.W; }
-        else { a.Ho = dst.H; a.Wo = dst.W; }
-        a.kh = s.kh; a.kw = s.kw; a.stride = s.stride; a.pad = s.pad; a.replicate = s.replicate;
-        const int ksplit = ksplit_of(a.Ho, a.Wo, bm, bn, a.cout_p, ncls, nkmin);
-        a.ksplit = ksplit;
-        const int64_t M = (int64_t)nimg * a.Ho * a.Wo;
-        const int64_t part = ksplit > 1 ? (int64_t)ncls * ksplit * M * a.cout_p : 0;
-        const int64_t poff = part ? alloc_raw(part) : 0;
+        const int64_t poff = g.partial ? alloc_raw(g.partial) : 0;
         if (mode == RUN) {
+            kpn_enc_conv_args a = g.a;
+            a.Hs = src.H; a.Ws = src.W;
+            a.stride = s.stride; a.pad = s.pad; a.replicate = s.replicate;
             a.src = stem ? img : ptr(src);
             a.src_cs = src.cs; a.Hraw = Hraw; a.Wraw = Wraw; a.ds = ds;
             a.ss = ss >= 0 ? ws + ss : nullptr;
@@ -147,41 +201,26 @@ struct Ctx {
             a.dst = ptr(dst); a.dst_cs = dst.cs;
             a.res = res ? ptr(*res) : nullptr; a.res_cs = res ? res->cs : 0;
             a.relu_out = relu_out;
-            a.partial = part ? ws + poff : nullptr;
-            const dim3 grid((unsigned)((M + bm - 1) / bm * (a.cout_p / bn)), (unsigned)ksplit, (unsigned)ncls);
-            if (stem) {
-                if (bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, true, false>), grid, dim3(256), stream, a);
-                else KPN_LAUNCH((k_enc_conv<128, 32, true, false>), grid, dim3(256), stream, a);
-            } else if (s.deconv) {
-                if (bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, true>), grid, dim3(256), stream, a);
-                else KPN_LAUNCH((k_enc_conv<128, 32, false, true>), grid, dim3(256), stream, a);
-            } else {
-                if (bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, false>), grid, dim3(256), stream, a);
-                else KPN_LAUNCH((k_enc_conv<128, 32, false, false>), grid, dim3(256), stream, a);
-            }
-            if (ksplit > 1) {
-                const int64_t n = (int64_t)ncls * M * a.cout;
-                KPN_LAUNCH(k_enc_combine, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, a, (int)s.deconv);
-            }
+            a.partial = g.partial ? ws + poff : nullptr;
+            launch_conv(a, g, stem, stream);
         }
-        if (part) release_raw(poff, part);
+        if (g.partial) release_raw(poff, g.partial);
     }
     // GroupNorm(G, C) (affine) or InstanceNorm2d (G = C, no affine) statistics of x -> offset of scale / shift
     int64_t stats(const View& x, int G, int affine) {
         const float* gamma = affine ? vec(x.C) : nullptr;
         const float* beta = affine ? vec(x.C) : nullptr;
-        const int HW = x.H * x.W;
-        const int nchunks = std::max(1, std::min(64, HW / 256));
+        int64_t pd;
+        const int nchunks = stats_chunks(nimg, x.H * x.W, x.C, &pd);
         const int64_t ss = alloc_raw((int64_t)2 * nimg * x.C);
-        const int64_t pn = (int64_t)nimg * nchunks * x.C * 2 * 2;        // doubles, counted in floats
+        const int64_t pn = pd * 2;                                       // doubles, counted in floats
         const int64_t po = alloc_raw(pn);
         if (mode == RUN) {
             kpn_enc_stats_args a{};
-            a.src = ptr(x); a.cs = x.cs; a.C = x.C; a.HW = HW; a.nchunks = nchunks; a.nimg = nimg;
+            a.src = ptr(x); a.cs = x.cs; a.C = x.C; a.HW = x.H * x.W; a.nchunks = nchunks; a.nimg = nimg;
             a.partial = reinterpret_cast<double*>(ws + po);
             a.G = G; a.gamma = gamma; a.beta = beta; a.eps = eps; a.ss = ws + ss;
-            KPN_LAUNCH(k_enc_stats_partial, dim3((unsigned)nchunks, (unsigned)nimg), dim3(256), stream, a);
-            KPN_LAUNCH(k_enc_stats_final, dim3((unsigned)((nimg * G + 63) / 64)), dim3(64), stream, a);
+            launch_stats(a, stream);
         }
         release_raw(po, pn);
         return ss;
@@ -189,23 +228,15 @@ struct Ctx {
     void free_ss(int64_t ss, int C) { release_raw(ss, (int64_t)2 * nimg * C); }
     void affine(const View& src, int64_t ss, int relu, const View* res, const View& dst) {
         if (mode != RUN) return;
-        const int64_t n = (int64_t)nimg * src.H * src.W * src.C / 4;
-        KPN_LAUNCH(k_enc_affine, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, (const float*)ptr(src),
-                   (const float*)(ss >= 0 ? ws + ss : nullptr), relu, (const float*)(res ? ptr(*res) : nullptr), ptr(dst), nimg, src.H * src.W, src.C);
+        launch_affine(ptr(src), ss >= 0 ? ws + ss : nullptr, relu, res ? ptr(*res) : nullptr, ptr(dst), nimg, src.H * src.W, src.C, stream);
     }
     View pool(const View& x) {
         View o = alloc(x.H / 2, x.W / 2, x.C);
-        if (mode == RUN) {
-            const int64_t n = (int64_t)nimg * o.H * o.W * o.C / 4;
-            KPN_LAUNCH(k_enc_pool2, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, (const float*)ptr(x), ptr(o), nimg, o.H, o.W, o.C);
-        }
+        if (mode == RUN) launch_pool2(ptr(x), ptr(o), nimg, o.H, o.W, o.C, stream);
         return o;
     }
     void upadd(const View& low, const View& up) {
-        if (mode != RUN) return;
-        const int64_t n = (int64_t)nimg * up.H * up.W * up.C / 4;
-        KPN_LAUNCH(k_enc_upadd, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, (const float*)ptr(low), (const float*)ptr(up), ptr(up), nimg,
-                   low.H, low.W, low.C);
+        if (mode == RUN) launch_upadd(ptr(low), ptr(up), ptr(up), nimg, low.H, low.W, low.C, stream);
     }
 };
 

@@ -1,8 +1,9 @@
 // ---------------------------------------------------------------------------------------------
 // GroupNorm / InstanceNorm2d [+ ReLU] of the image encoders, forward and backward (torch.nn.functional.group_norm [+ relu] and
 // their autograd as the legs of ConvBlock and ResBlkEncoder call them: reference src/utils.py:416-474, 199-247).  Kernels:
-// encoder_kernels.hip.  The forward is the encoder walk's own k_enc_stats_partial / k_enc_stats_final / k_enc_affine (chunk rule
-// of enc::Ctx::stats), with the statistics kept for the backward; the backward is k_enc_norm_bwd_partial / _final / _dx.
+// encoder_kernels.hip.  The forward is the encoder walk's own statistics and affine kernels, launched through the launch layer at
+// the head of api_encoders.hip (enc::stats_chunks / enc::launch_stats / enc::launch_affine), with the statistics kept for the
+// backward; the backward is k_enc_norm_bwd_partial / _final / _dx over the same chunks.
 namespace gnorm {
 const char* desc_error(const kpn_group_norm_desc* d) {
     if (!d) return "desc is null";
@@ -23,10 +24,11 @@ struct Plan {
 Plan plan(const kpn_group_norm_desc* d) {
     Plan p{};
     p.HW = d->H * d->W;
-    p.nchunks = std::max(1, std::min(64, p.HW / 256));        // the forward's rule (enc::Ctx::stats): from the shape alone
+    int64_t pd;
+    p.nchunks = enc::stats_chunks(d->N, p.HW, d->C, &pd);
     // the forward's (sum, sum of squares) and the backward's (A, B) partials have one size and never live at once
     Carver c;
-    p.o_partial = c.take((size_t)d->N * p.nchunks * d->C * 2 * sizeof(double));
+    p.o_partial = c.take((size_t)pd * sizeof(double));
     p.o_coef = c.take((size_t)3 * d->N * d->C * sizeof(float));
     p.bytes = c.o;
     return p;
@@ -56,11 +58,8 @@ extern "C" int kpn_group_norm_forward(const kpn_group_norm_desc* desc, const flo
     a.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + p.o_partial);
     a.G = desc->G; a.gamma = gamma; a.beta = beta; a.eps = desc->eps;
     a.ss = stats; a.mr = stats + (size_t)2 * desc->N * desc->C;
-    KPN_LAUNCH(k_enc_stats_partial, dim3((unsigned)p.nchunks, (unsigned)desc->N), dim3(256), stream, a);
-    KPN_LAUNCH(k_enc_stats_final, dim3((unsigned)((desc->N * desc->G + 63) / 64)), dim3(64), stream, a);
-    const int64_t n = (int64_t)desc->N * p.HW * desc->C / 4;
-    KPN_LAUNCH(k_enc_affine, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, x, (const float*)stats, (int)desc->relu,
-               (const float*)nullptr, y, (int)desc->N, p.HW, (int)desc->C);
+    enc::launch_stats(a, stream);
+    enc::launch_affine(x, stats, desc->relu, nullptr, y, desc->N, p.HW, desc->C, stream);
     return check_launch("kpn_group_norm_forward");
 }
 extern "C" int kpn_group_norm_backward(const kpn_group_norm_desc* desc, const float* x, const float* dy, const float* gamma, const float* stats,
@@ -83,9 +82,6 @@ extern "C" int kpn_group_norm_backward(const kpn_group_norm_desc* desc, const fl
     a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
     KPN_LAUNCH(k_enc_norm_bwd_partial, dim3((unsigned)p.nchunks, (unsigned)desc->N), dim3(256), stream, a);
     KPN_LAUNCH(k_enc_norm_bwd_final, dim3((unsigned)((desc->N * desc->G + desc->C + 63) / 64)), dim3(64), stream, a);
-    if (dx) {
-        const int64_t n = (int64_t)desc->N * p.HW * desc->C / 4;
-        KPN_LAUNCH(k_enc_norm_bwd_dx, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), stream, a);
-    }
+    if (dx) KPN_LAUNCH(k_enc_norm_bwd_dx, enc::grid4((int64_t)desc->N * p.HW * desc->C / 4), dim3(256), stream, a);
     return check_launch("kpn_group_norm_backward");
 }

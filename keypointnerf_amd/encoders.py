@@ -315,6 +315,39 @@ def uninstall_encoders(net):
     return net
 
 
+# ---- the opt-in installers below rebind ``forward`` on single module instances; this is their one scaffold ----
+def _restore_forward(module, key):
+    for m in module.modules():
+        if key in m.__dict__:
+            saved = m.__dict__.pop(key)
+            if saved is None:
+                m.__dict__.pop("forward", None)
+            else:
+                m.__dict__["forward"] = saved
+    return module
+
+
+def _rebind_forward(module, key, candidate, ineligible, make_forward):
+    """Undoes an earlier install under ``key`` (what that installer's uninstaller does), then rebinds ``forward`` on every module
+    under ``module`` that ``candidate(m)`` selects and for which ``ineligible(m, name)`` gives no reason, to ``make_forward(prev)``,
+    ``prev`` being the forward the instance had.  What the instance's own ``forward`` attribute was (None when the class's forward
+    was in place) is kept under ``key`` for ``_restore_forward``.  Returns (served, left): the names served and {name: reason}."""
+    _restore_forward(module, key)
+    served, left = [], {}
+    for name, m in module.named_modules():
+        if not candidate(m):
+            continue
+        why = ineligible(m, name)
+        if why is not None:
+            left[name] = why
+            continue
+        prev = m.forward
+        setattr(m, key, m.__dict__.get("forward"))
+        m.forward = types.MethodType(make_forward(prev), m)
+        served.append(name)
+    return served, left
+
+
 # ---- training convolutions natively: torch.ops.kpnerf.conv2d behind the nn.Conv2d instances of a module tree ----
 def _conv_ineligible(m):
     """None if kpn_conv2d_* serves this nn.Conv2d, else the reason it is left on torch"""
@@ -348,27 +381,16 @@ def install_native_convs(module):
     state_dict are untouched.  Independent of ``install_encoders``: both may be installed on one ``net`` (the whole-network
     native forward still wins where it is served).  Returns (served, left): the names served, and {name: reason} of the
     nn.Conv2d layers left alone."""
-    uninstall_native_convs(module)
-    served, left = [], {}
-    for name, m in module.named_modules():
-        if type(m) is not torch.nn.Conv2d:
-            continue
-        why = _conv_ineligible(m)
-        if why is not None:
-            left[name] = why
-            continue
-        prev = m.forward
-        m._kpnerf_conv_saved = m.__dict__.get("forward")
-
-        def forward(self, x, _prev=prev):
+    def make_forward(_prev):
+        def forward(self, x):
             if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
                     and self.weight.is_cuda and self.weight.dtype == torch.float32):
                 return _prev(x)
             return torch.ops.kpnerf.conv2d(x, self.weight, self.bias, _pair(self.padding)[0])
+        return forward
 
-        m.forward = types.MethodType(forward, m)
-        served.append(name)
-    return served, left
+    return _rebind_forward(module, "_kpnerf_conv_saved", lambda m: type(m) is torch.nn.Conv2d, lambda m, name: _conv_ineligible(m),
+                           make_forward)
 
 
 def uninstall_native_convs(module):
@@ -418,40 +440,18 @@ def install_native_norms(module):
     (N, C, H, W) input and calls the module's own forward for anything else; its result is channels_last.  The module tree, the
     parameter names and the state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of the layers
     left alone."""
-    uninstall_native_norms(module)
-    served, left = [], {}
-    for name, m in module.named_modules():
-        if type(m) not in (torch.nn.GroupNorm, torch.nn.InstanceNorm2d):
-            continue
-        why = _norm_ineligible(m)
-        if why is not None:
-            left[name] = why
-            continue
-        prev = m.forward
-        m._kpnerf_norm_saved = m.__dict__.get("forward")
-
-        def forward(self, x, _prev=prev):
+    def make_forward(_prev):
+        def forward(self, x):
             w, b = getattr(self, "weight", None), getattr(self, "bias", None)
             if not _native_input(x, w, b):
                 return _prev(x)
             NativeTraining.norm_calls += 1
             groups = self.num_groups if isinstance(self, torch.nn.GroupNorm) else self.num_features
             return torch.ops.kpnerf.group_norm(x, w, b, groups, self.eps, False)
+        return forward
 
-        m.forward = types.MethodType(forward, m)
-        served.append(name)
-    return served, left
-
-
-def _restore_forward(module, key):
-    for m in module.modules():
-        if key in m.__dict__:
-            saved = m.__dict__.pop(key)
-            if saved is None:
-                m.__dict__.pop("forward", None)
-            else:
-                m.__dict__["forward"] = saved
-    return module
+    return _rebind_forward(module, "_kpnerf_norm_saved", lambda m: type(m) in (torch.nn.GroupNorm, torch.nn.InstanceNorm2d),
+                           lambda m, name: _norm_ineligible(m), make_forward)
 
 
 def uninstall_native_norms(module):
@@ -482,19 +482,8 @@ def install_native_blocks(module):
     stay on torch.  A ConvBlock that fails the check is left alone.  CPU or non-fp32 input goes to the original forward.  The module
     tree, the parameter names and the state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of
     the ConvBlocks left alone."""
-    uninstall_native_blocks(module)
-    served, left = [], {}
-    for name, m in module.named_modules():
-        if type(m).__name__ != "ConvBlock":
-            continue
-        why = _block_ineligible(m, name)
-        if why is not None:
-            left[name] = why
-            continue
-        prev = m.forward
-        m._kpnerf_block_saved = m.__dict__.get("forward")
-
-        def forward(self, x, _prev=prev):
+    def make_forward(_prev):
+        def forward(self, x):
             if not _native_input(x, *self.parameters()):
                 return _prev(x)
             NativeTraining.block_calls += 1
@@ -509,10 +498,9 @@ def install_native_blocks(module):
             out = torch.cat((o1, o2, o3), 1)
             out += x if self.downsample is None else leg(self.bn4, self.downsample[2], x, 0)
             return out
+        return forward
 
-        m.forward = types.MethodType(forward, m)
-        served.append(name)
-    return served, left
+    return _rebind_forward(module, "_kpnerf_block_saved", lambda m: type(m).__name__ == "ConvBlock", _block_ineligible, make_forward)
 
 
 def uninstall_native_blocks(module):
@@ -544,19 +532,8 @@ def install_native_hourglass(module):
     ``install_native_blocks`` / ``install_native_norms`` / ``install_native_convs`` in any order.  Input that is not a CUDA fp32
     (N, C, H, W) tensor with H and W divisible by 2^depth goes to the original forward.  The module tree, the parameter names and the
     state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of the HourGlasses left alone."""
-    uninstall_native_hourglass(module)
-    served, left = [], {}
-    for name, m in module.named_modules():
-        if type(m).__name__ != "HourGlass":
-            continue
-        why = _hourglass_ineligible(m)
-        if why is not None:
-            left[name] = why
-            continue
-        prev = m.forward
-        m._kpnerf_hourglass_saved = m.__dict__.get("forward")
-
-        def forward(self, x, _prev=prev):
+    def make_forward(_prev):
+        def forward(self, x):
             if not _native_input(x) or x.shape[2] % (1 << self.depth) or x.shape[3] % (1 << self.depth):
                 return _prev(x)
             NativeTraining.hourglass_calls += 1
@@ -569,10 +546,10 @@ def install_native_hourglass(module):
                 return torch.ops.kpnerf.upsample2x_add(low, up1)
 
             return run(self.depth, x)
+        return forward
 
-        m.forward = types.MethodType(forward, m)
-        served.append(name)
-    return served, left
+    return _rebind_forward(module, "_kpnerf_hourglass_saved", lambda m: type(m).__name__ == "HourGlass",
+                           lambda m, name: _hourglass_ineligible(m), make_forward)
 
 
 def uninstall_native_hourglass(module):

@@ -896,15 +896,9 @@ def tex_encode(img, packed, ds=1, ngf=64, n_downsample=3, n_blocks=4, n_upsample
 
 
 # ------------------------------------------------------------------------------------------------
-# One stride-1 convolution and its gradients (kpn_conv2d_*; torch.nn.functional.conv2d and its autograd, reference
-# src/utils.py:416-474, 261-309, 322-414).  Activations are channels_last tensors of logical shape (N, C, H, W).
-def _conv_desc(N, H, W, cin, cout, k, padding, has_bias):
-    d = kl.Conv2dDesc()
-    d.N, d.H, d.W, d.cin, d.cout, d.k, d.pad, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(k), int(padding), int(has_bias)
-    return d
-
-
-def _conv_cl(t, name, channels=None):
+# Shared by the three families of differentiable layers below (kpn_conv2d_*, kpn_group_norm_*, the resampling steps): the check of
+# their activations and the error path of a descriptor the library does not serve.
+def _channels_last(t, name, channels=None):
     """a CUDA fp32 (N, C, H, W) tensor that is dense in channels_last (NHWC) memory, as it is"""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -917,6 +911,35 @@ def _conv_cl(t, name, channels=None):
     if not t.permute(0, 2, 3, 1).is_contiguous():
         raise ValueError(f"{name} must be dense in channels_last memory (x.contiguous(memory_format=torch.channels_last))")
     return t
+
+
+def _desc_size(L, d, size_fn, probe_fn, label):
+    """getattr(L, size_fn)(d): floats or bytes.  0 means the library does not serve the descriptor: its reason is fetched by calling
+    ``probe_fn`` with nothing but the descriptor (validation fails before anything is read) and raised behind ``label``."""
+    n = getattr(L, size_fn)(ctypes.byref(d))
+    if n == 0:
+        probe = getattr(L, probe_fn)
+        probe(ctypes.byref(d), *(0 if t is kl.c_sz else None for t in probe.argtypes[1:]))
+        raise ValueError(f"{label}: {L.kpn_last_error().decode()}")
+    return n
+
+
+def _desc_workspace(L, d, device, size_fn, probe_fn, label):
+    nb = _desc_size(L, d, size_fn, probe_fn, label)
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+_CONV_WORKSPACE = ("kpn_conv2d_workspace_bytes", "kpn_conv2d_forward", "conv2d: unsupported convolution")
+_NORM_WORKSPACE = ("kpn_group_norm_workspace_bytes", "kpn_group_norm_forward", "group_norm: unsupported normalisation")
+
+
+# ------------------------------------------------------------------------------------------------
+# One stride-1 convolution and its gradients (kpn_conv2d_*; torch.nn.functional.conv2d and its autograd, reference
+# src/utils.py:416-474, 261-309, 322-414).  Activations are channels_last tensors of logical shape (N, C, H, W).
+def _conv_desc(N, H, W, cin, cout, k, padding, has_bias):
+    d = kl.Conv2dDesc()
+    d.N, d.H, d.W, d.cin, d.cout, d.k, d.pad, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(k), int(padding), int(has_bias)
+    return d
 
 
 def _conv_weight(w):
@@ -938,31 +961,20 @@ def conv2d_pack(weight):
     L = kl.get_library()
     w = _conv_weight(weight.detach())
     d = _conv_desc(1, 1, 1, w.shape[1], w.shape[0], w.shape[2], 0, 0)
-    n = L.kpn_conv2d_packed_floats(ctypes.byref(d))
-    if n == 0:
-        L.kpn_conv2d_pack_device(ctypes.byref(d), None, None, None)
-        raise ValueError(f"conv2d: unsupported weight {tuple(w.shape)}: {L.kpn_last_error().decode()}")
+    n = _desc_size(L, d, "kpn_conv2d_packed_floats", "kpn_conv2d_pack_device", f"conv2d: unsupported weight {tuple(w.shape)}")
     packed = torch.empty(n, dtype=_f32, device=w.device)
     L.check(L.kpn_conv2d_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
     return packed
-
-
-def _conv_workspace(L, d, device):
-    nb = L.kpn_conv2d_workspace_bytes(ctypes.byref(d))
-    if nb == 0:
-        L.kpn_conv2d_forward(ctypes.byref(d), None, None, None, None, None, 0, None)
-        raise ValueError(f"conv2d: unsupported convolution: {L.kpn_last_error().decode()}")
-    return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
 
 def conv2d_forward(x, packed, bias, cout, k, padding):
     """conv2d(x, w, bias, stride=1, padding=padding) for packed = conv2d_pack(w) (kpn_conv2d_forward).  x: (N, cin, H, W)
     channels_last; returns (N, cout, Ho, Wo) channels_last."""
     L = kl.get_library()
-    x = _conv_cl(x, "x")
+    x = _channels_last(x, "x")
     N, cin, H, W = x.shape
     d = _conv_desc(N, H, W, cin, cout, k, padding, bias is not None)
-    ws, nb = _conv_workspace(L, d, x.device)
+    ws, nb = _desc_workspace(L, d, x.device, *_CONV_WORKSPACE)
     if packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
         raise ValueError("packed does not belong to this convolution (conv2d_pack)")
     b = None if bias is None else _dev(bias.detach(), "bias")
@@ -979,14 +991,14 @@ def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want
     gradient that is not wanted is None and its leg is not launched.  x (channels_last) is read for dw only and packed for dx
     only: either may be None when its leg is off.  dx is channels_last, dw OIHW."""
     L = kl.get_library()
-    dy = _conv_cl(dy, "dy")
+    dy = _channels_last(dy, "dy")
     N, cout, Ho, Wo = dy.shape
     H, W = Ho - 2 * padding + k - 1, Wo - 2 * padding + k - 1
     want_db = bool(want_db and has_bias)
     d = _conv_desc(N, H, W, cin, cout, k, padding, has_bias)
-    ws, nb = _conv_workspace(L, d, dy.device)
+    ws, nb = _desc_workspace(L, d, dy.device, *_CONV_WORKSPACE)
     if want_dw:
-        x = _conv_cl(x, "x", cin)
+        x = _channels_last(x, "x", cin)
         if tuple(x.shape) != (N, cin, H, W):
             raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
     if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
@@ -1014,14 +1026,6 @@ def group_norm_supported(C, groups):
     return kl.get_library().kpn_group_norm_workspace_bytes(ctypes.byref(_norm_desc(1, 1, 1, C, groups, 0, 0, 1e-5))) > 0
 
 
-def _norm_workspace(L, d, device):
-    nb = L.kpn_group_norm_workspace_bytes(ctypes.byref(d))
-    if nb == 0:
-        L.kpn_group_norm_forward(ctypes.byref(d), None, None, None, None, None, None, 0, None)
-        raise ValueError(f"group_norm: unsupported normalisation: {L.kpn_last_error().decode()}")
-    return torch.empty(nb, dtype=torch.uint8, device=device), nb
-
-
 def _norm_vec(t, name, C):
     t = _dev(t.detach(), name)
     if tuple(t.shape) != (C,):
@@ -1034,12 +1038,12 @@ def group_norm_forward(x, weight, bias, groups, eps, relu):
     both (C,) or both None (groups = C without them is InstanceNorm2d).  Returns (y channels_last, stats): stats holds the scale and
     shift per (image, channel) and the mean and rstd per (image, group) that group_norm_backward reads."""
     L = kl.get_library()
-    x = _conv_cl(x, "x")
+    x = _channels_last(x, "x")
     N, C, H, W = x.shape
     if (weight is None) != (bias is None):
         raise ValueError("weight and bias must both be given or both be None")
     d = _norm_desc(N, H, W, C, groups, weight is not None, relu, eps)
-    ws, nb = _norm_workspace(L, d, x.device)
+    ws, nb = _desc_workspace(L, d, x.device, *_NORM_WORKSPACE)
     w = None if weight is None else _norm_vec(weight, "weight", C)
     b = None if bias is None else _norm_vec(bias, "bias", C)
     # y is no view of another tensor: autograd refuses an in-place ReLU on a view that a two-output operator returned
@@ -1054,14 +1058,14 @@ def group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=True, w
     stats is what the forward returned for this x and weight.  A gradient that is not wanted is None and nothing is computed for
     it; dweight and dbias exist only with a weight.  dx is channels_last."""
     L = kl.get_library()
-    x, dy = _conv_cl(x, "x"), _conv_cl(dy, "dy")
+    x, dy = _channels_last(x, "x"), _channels_last(dy, "dy")
     N, C, H, W = x.shape
     if tuple(dy.shape) != tuple(x.shape):
         raise ValueError(f"dy must be {tuple(x.shape)}, got {tuple(dy.shape)}")
     affine = weight is not None
     want_dw, want_db = bool(want_dw and affine), bool(want_db and affine)
     d = _norm_desc(N, H, W, C, groups, affine, relu, eps)
-    ws, nb = _norm_workspace(L, d, x.device)
+    ws, nb = _desc_workspace(L, d, x.device, *_NORM_WORKSPACE)
     if stats.numel() != L.kpn_group_norm_stats_floats(ctypes.byref(d)) or stats.dtype != _f32 or stats.device != x.device:
         raise ValueError("stats does not belong to this normalisation (group_norm_forward)")
     w = _norm_vec(weight, "weight", C) if affine else None
@@ -1093,7 +1097,7 @@ def _resample_out(N, C, H, W, device):
 def avg_pool2_forward(x):
     """avg_pool2d(x, 2, stride=2) (kpn_avg_pool2_forward).  x: (N, C, 2h, 2w) channels_last; returns (N, C, h, w) channels_last."""
     L = kl.get_library()
-    x = _conv_cl(x, "x")
+    x = _channels_last(x, "x")
     N, C, H, W = x.shape
     if H % 2 or W % 2 or H < 2 or W < 2:
         raise ValueError(f"x must have even, positive height and width, got {tuple(x.shape)}")
@@ -1107,7 +1111,7 @@ def avg_pool2_backward(dy):
     """dx of avg_pool2_forward for the output gradient dy (N, C, h, w) channels_last (kpn_avg_pool2_backward): (N, C, 2h, 2w)
     channels_last, 0.25 dy under every pixel of a window."""
     L = kl.get_library()
-    dy = _conv_cl(dy, "dy")
+    dy = _channels_last(dy, "dy")
     N, C, h, w = dy.shape
     d = _resample_desc(N, h, w, C)
     dx = _resample_out(N, C, 2 * h, 2 * w, dy.device)
@@ -1120,15 +1124,15 @@ def upsample2x_add_forward(low, skip=None, out=None):
     (kpn_upsample2x_add_forward).  low: (N, C, h, w), skip: (N, C, 2h, 2w), both channels_last.  out: None (a new tensor) or a
     channels_last (N, C, 2h, 2w) tensor to write, which may be skip itself.  Returns (N, C, 2h, 2w) channels_last."""
     L = kl.get_library()
-    low = _conv_cl(low, "low")
+    low = _channels_last(low, "low")
     N, C, h, w = low.shape
     high = (N, C, 2 * h, 2 * w)
     if skip is not None:
-        skip = _conv_cl(skip, "skip")
+        skip = _channels_last(skip, "skip")
         if tuple(skip.shape) != high:
             raise ValueError(f"skip must be {high}, got {tuple(skip.shape)}")
     if out is not None:
-        out = _conv_cl(out, "out")
+        out = _channels_last(out, "out")
         if tuple(out.shape) != high:
             raise ValueError(f"out must be {high}, got {tuple(out.shape)}")
     d = _resample_desc(N, h, w, C)
@@ -1141,7 +1145,7 @@ def upsample2x_add_backward(dy):
     """d_low of upsample2x_add_forward for the output gradient dy (N, C, 2h, 2w) channels_last (kpn_upsample2x_add_backward):
     (N, C, h, w) channels_last, a gather in a fixed order - bit-identical from run to run.  The gradient of skip is dy itself."""
     L = kl.get_library()
-    dy = _conv_cl(dy, "dy")
+    dy = _channels_last(dy, "dy")
     N, C, H, W = dy.shape
     if H % 2 or W % 2 or H < 2 or W < 2:
         raise ValueError(f"dy must have even, positive height and width, got {tuple(dy.shape)}")

@@ -47,6 +47,7 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 the flat effective-parameter vector ``plain`` (and from there ``weight_g`` / ``weight_v`` / ``bias`` / ``ani_al`` through
 ``weights.plain_tensor_from_module``) and the three encoder feature maps.  This is the op the training drop-in calls.
 """
+import collections
 from typing import List, Optional, Tuple
 
 import torch
@@ -55,6 +56,16 @@ from . import lib as kl
 from . import ops
 
 _lib = torch.library
+
+
+# An operator returns tensors only: a gradient that is not wanted (or lacks its input) travels as an empty tensor, and the autograd
+# formula turns what its mask did not ask for back into None.
+def _empty_for_none(like, *grads):
+    return tuple(like.new_empty(0) if g is None else g for g in grads)
+
+
+def _none_unless(mask, *grads):
+    return tuple(g if m else None for g, m in zip(grads, mask))
 
 
 @_lib.custom_op("kpnerf::rgba2out", mutates_args=(), device_types="cuda")
@@ -353,8 +364,7 @@ def train_loss(tex: Optional[torch.Tensor], tex_fine: Optional[torch.Tensor], ta
     (3, ...: l1 / l2 / lp apart), d_alpha, d_alpha_fine; an absent input's gradient is an empty tensor, a skipped term's part is
     uninitialised.  Differentiable w.r.t. tex, tex_fine, alpha, alpha_fine; the backward launches no kernel of the library."""
     terms, d_x, d_xf, d_a, d_af = ops.train_loss(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights, want_grad=True)
-    none = lambda v: terms.new_empty(0) if v is None else v
-    return terms, none(d_x), none(d_xf), none(d_a), none(d_af)
+    return (terms,) + _empty_for_none(terms, d_x, d_xf, d_a, d_af)
 
 
 @train_loss.register_fake
@@ -515,9 +525,6 @@ tex_encode.register_autograd(_encoder_bwd, setup_context=_encoder_no_autograd)
 # address means the same storage and an in-place update (an optimizer step) moves the version: a miss and a re-pack, never a stale
 # hit.  Inference tensors have no version counter: they are packed on every call and not kept.  At most _ConvPackCache.limit
 # weights stay resident (least recently used first out); conv2d_cache_clear() drops them all.
-import collections
-
-
 class _ConvPackCache:
     lock = threading.Lock()
     entries = collections.OrderedDict()     # data_ptr -> (key, weight, packed)
@@ -575,8 +582,7 @@ def conv2d_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, pad
     dy = dy.contiguous(memory_format=torch.channels_last)
     dx, dw, db = ops.conv2d_backward(x, dy, _conv_packed(weight) if mask[0] else None, cin, k, padding, has_bias,
                                      want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
-    none = lambda v: dy.new_empty(0) if v is None else v
-    return none(dx), none(dw), none(db)
+    return _empty_for_none(dy, dx, dw, db)
 
 
 @conv2d_backward.register_fake
@@ -602,7 +608,7 @@ def _conv2d_bwd(ctx, dy):
     if not any(mask):
         return None, None, None, None
     dx, dw, db = torch.ops.kpnerf.conv2d_backward(x, weight, dy, ctx.padding, ctx.has_bias, mask)
-    return (dx if mask[0] else None), (dw if mask[1] else None), (db if mask[2] else None), None
+    return _none_unless(mask, dx, dw, db) + (None,)
 
 
 conv2d_cl.register_autograd(_conv2d_bwd, setup_context=_conv2d_setup)
@@ -644,8 +650,7 @@ def group_norm_backward(x: torch.Tensor, weight: Optional[torch.Tensor], stats: 
     wanted: what is not wanted is not computed and its result is an empty tensor."""
     dy = dy.contiguous(memory_format=torch.channels_last)
     dx, dw, db = ops.group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
-    none = lambda v: dy.new_empty(0) if v is None else v
-    return none(dx), none(dw), none(db)
+    return _empty_for_none(dy, dx, dw, db)
 
 
 @group_norm_backward.register_fake
@@ -672,7 +677,7 @@ def _group_norm_bwd(ctx, dy, _d_stats):
     if not any(mask):
         return None, None, None, None, None, None
     dx, dw, db = torch.ops.kpnerf.group_norm_backward(x, w[0] if w else None, stats, dy, ctx.groups, ctx.eps, ctx.relu, mask)
-    return (dx if mask[0] else None), (dw if mask[1] else None), (db if mask[2] else None), None, None, None
+    return _none_unless(mask, dx, dw, db) + (None, None, None)
 
 
 group_norm_cl.register_autograd(_group_norm_bwd, setup_context=_group_norm_setup)
