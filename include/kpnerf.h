@@ -44,6 +44,8 @@ extern "C" {
  * kpn_group_norm_workspace_bytes, kpn_group_norm_forward, kpn_group_norm_backward (nothing of ABI 8 changed) */
 /* 10: additive - the two resampling steps of an HourGlass with their gradients: kpn_resample2_desc, kpn_avg_pool2_forward,
  * kpn_avg_pool2_backward, kpn_upsample2x_add_forward, kpn_upsample2x_add_backward (nothing of ABI 9 changed) */
+/* still 10: kpn_scene_layout (where kpn_scene_prepare puts each prepared map in the scene workspace) is one more export and changes
+ * nothing that a caller built against 10 uses, so the number stays; a binding that wants it looks the symbol up */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -99,6 +101,10 @@ size_t kpn_scene_workspace_bytes(const kpn_scene_desc* desc);
  * interleaved, keypoints moved to every camera frame (src/spatial.py:85), source camera centres
  * (inverse(KRT)[:3,3], src/model.py:823-824). */
 int kpn_scene_prepare(const kpn_scene_desc* desc, void* scene_ws, void* stream);
+/* Where kpn_scene_prepare puts its results: the offsets, in floats from the start of the workspace, of the per-view tables
+ * (V x 112), rgbm (V,H,W,4), geo0 (V,h,w,64), geo1 (V,h,w,8), tex (V,h,w,8) and the flags ([0] = max |value| of the
+ * images and maps, as a float; a NaN input makes it NaN), in this order.  For tests and tools that read the prepared maps. */
+int kpn_scene_layout(const kpn_scene_desc* desc, size_t offsets[6]);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage ops = the reference's per-stage callables. */

@@ -108,8 +108,10 @@ extern "C" size_t kpn_render_workspace_bytes(const kpn_scene_desc* d, const kpn_
 // importance samples of the fine pass + the merged depth list (k_fine_samples_w), Sc, Sf <= 128
 static void launch_fine_samples(void* stream, int64_t n, int Sc, int Sf, const float* zc, const float* contrib,
                                 const float* u, float* zf, float* znew, int16_t* src) {
-    const dim3 grid((unsigned)(n + 3 < 4 * 8192 ? (n + 3) / 4 : 8192));
-    if (Sc <= 64 && Sf <= 64)
+    const bool small = Sc <= 64 && Sf <= 64;
+    const int64_t per = 4 * KPN_FINE_GROUP(small);   // rays of a workgroup: four wavefronts, a group each
+    const dim3 grid((unsigned)((n + per - 1) / per < 8192 ? (n + per - 1) / per : 8192));
+    if (small)
         KPN_LAUNCH(k_fine_samples_w<true>, grid, dim3(256), stream, n, Sc, Sf, zc, contrib, u, zf, znew, src);
     else
         KPN_LAUNCH(k_fine_samples_w<false>, grid, dim3(256), stream, n, Sc, Sf, zc, contrib, u, zf, znew, src);

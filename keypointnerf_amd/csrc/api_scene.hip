@@ -19,6 +19,8 @@ int check_desc(const kpn_scene_desc* d) {
     KPN_REQUIRE(d->n_views >= 1 && d->n_views <= KPN_MAX_VIEWS, "n_views out of range");
     KPN_REQUIRE(d->src_h > 1 && d->src_w > 1 && d->geo0_h > 1 && d->geo0_w > 1 && d->geo1_h > 1 && d->geo1_w > 1 &&
                 d->tex_h > 1 && d->tex_w > 1, "map sizes must be > 1");
+    KPN_REQUIRE((int64_t)d->src_h * d->src_w <= INT32_MAX && (int64_t)d->geo0_h * d->geo0_w <= INT32_MAX &&
+                (int64_t)d->geo1_h * d->geo1_w <= INT32_MAX && (int64_t)d->tex_h * d->tex_w <= INT32_MAX, "map too large");
     KPN_REQUIRE(d->zfar > d->znear && d->nml_scale > 0.0f && d->sigma > 0.0f, "bad scalar parameters");
     KPN_REQUIRE(d->KRT && d->extrin && d->kpt3d && d->img && d->geo0 && d->geo1 && d->tex, "null scene tensor");
     KPN_REQUIRE(d->disable_fg_mask || d->fg_mask, "fg_mask is null");
@@ -45,6 +47,14 @@ extern "C" size_t kpn_scene_workspace_bytes(const kpn_scene_desc* d) {
     return scene_layout(d).total * sizeof(float);
 }
 
+extern "C" int kpn_scene_layout(const kpn_scene_desc* d, size_t offsets[6]) {
+    if (int e = check_desc(d)) return e;
+    KPN_REQUIRE(offsets != nullptr, "offsets is null");
+    const SceneLayout L = scene_layout(d);
+    offsets[0] = L.table; offsets[1] = L.rgbm; offsets[2] = L.geo0; offsets[3] = L.geo1; offsets[4] = L.tex; offsets[5] = L.flags;
+    return KPN_OK;
+}
+
 extern "C" int kpn_scene_prepare(const kpn_scene_desc* d, void* scene_ws, void* stream) {
     if (int e = check_desc(d)) return e;
     KPN_REQUIRE(scene_ws != nullptr, "scene workspace is null");
@@ -52,14 +62,19 @@ extern "C" int kpn_scene_prepare(const kpn_scene_desc* d, void* scene_ws, void* 
     float* base = static_cast<float*>(scene_ws);
     const int V = d->n_views;
     float* flags = base + L.flags;   // zeroed by k_scene_table (first on the stream), raised by the copies behind it
-    KPN_LAUNCH(k_scene_table, dim3(1), dim3(64), stream, V, d->KRT, d->extrin, d->kpt3d, base + L.table, flags);
-    const int64_t HW = (int64_t)d->src_h * d->src_w;
-    KPN_LAUNCH(k_pack_rgbm, grid1d(V * HW, 256), dim3(256), stream, (int64_t)(V * HW), HW, d->img,
+    KPN_LAUNCH(k_scene_table, dim3(V), dim3(128), stream, V, d->KRT, d->extrin, d->kpt3d, base + L.table, flags);
+    const int HW = d->src_h * d->src_w;
+    const int ptiles = (HW + KPN_PACK_PIX - 1) / KPN_PACK_PIX;
+    KPN_LAUNCH(k_pack_rgbm, dim3(V * ptiles), dim3(256), stream, HW, ptiles, d->img,
                d->disable_fg_mask ? (const uint8_t*)nullptr : d->fg_mask, base + L.rgbm, flags);
-    const int64_t hw0 = (int64_t)d->geo0_h * d->geo0_w, hw1 = (int64_t)d->geo1_h * d->geo1_w, hwt = (int64_t)d->tex_h * d->tex_w;
-    KPN_LAUNCH(k_nchw_to_nhwc, grid1d(V * hw0 * 64, 256), dim3(256), stream, (int64_t)(V * hw0 * 64), 64, hw0, d->geo0, base + L.geo0, flags);
-    KPN_LAUNCH(k_nchw_to_nhwc, grid1d(V * hw1 * 8, 256), dim3(256), stream, (int64_t)(V * hw1 * 8), 8, hw1, d->geo1, base + L.geo1, flags);
-    KPN_LAUNCH(k_nchw_to_nhwc, grid1d(V * hwt * 8, 256), dim3(256), stream, (int64_t)(V * hwt * 8), 8, hwt, d->tex, base + L.tex, flags);
+    // float4 loads of a channel's run: every run starts 16-byte aligned
+    auto vec = [](const float* p, int hw) { return (hw % 4 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0) ? 1 : 0; };
+    const int hw0 = d->geo0_h * d->geo0_w, hw1 = d->geo1_h * d->geo1_w, hwt = d->tex_h * d->tex_w;
+    const int t0 = (hw0 + KPN_NHWC_TILE / 64 - 1) / (KPN_NHWC_TILE / 64), t1 = (hw1 + KPN_NHWC_TILE / 8 - 1) / (KPN_NHWC_TILE / 8),
+              tt = (hwt + KPN_NHWC_TILE / 8 - 1) / (KPN_NHWC_TILE / 8);
+    KPN_LAUNCH(k_nchw_to_nhwc<64>, dim3(V * t0), dim3(256), stream, hw0, t0, vec(d->geo0, hw0), d->geo0, base + L.geo0, flags);
+    KPN_LAUNCH(k_nchw_to_nhwc<8>, dim3(V * t1), dim3(256), stream, hw1, t1, vec(d->geo1, hw1), d->geo1, base + L.geo1, flags);
+    KPN_LAUNCH(k_nchw_to_nhwc<8>, dim3(V * tt), dim3(256), stream, hwt, tt, vec(d->tex, hwt), d->tex, base + L.tex, flags);
     return check_launch("kpn_scene_prepare");
 }
 

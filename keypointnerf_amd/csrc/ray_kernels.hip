@@ -10,87 +10,141 @@
 #include "kpn_device.h"
 
 // ---------------------------------------------------------------------------------------------
-// per-view table: KRT rows, extrinsic rows, camera centre = inverse(KRT)[:3,3] (model.py:823-824),
-// keypoints in the camera frame (spatial.py:85).  One thread per view; double Gauss-Jordan.
 // The running max |value| of everything kpn_scene_prepare copies (scene flags[0], zeroed by k_scene_table, which runs first on
-// the stream): as int bit patterns |x| orders like the floats, and a NaN sits above +inf.  One atomic per wavefront, and only while
-// the wave's maximum is above what is already there (a few per launch).  Every thread of the wave must call it.
-__device__ __forceinline__ void kpn_note_absmax(float* __restrict__ flags, float a) {
-    int u = __float_as_int(a) & 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(u, o); u = w > u ? w : u; }
-    int* f = reinterpret_cast<int*>(flags);
-    if ((threadIdx.x & 63) == 0 && u > *reinterpret_cast<volatile int*>(f)) atomicMax(f, u);
+// the stream): as int bit patterns |x| orders like the floats, and a NaN sits above +inf.  The copy kernels keep the maximum of
+// the patterns per thread, reduce it in the workgroup and issue at most ONE atomic per workgroup, and only while the workgroup's
+// maximum is above what is already there (a few per launch).  Every thread of the 256-thread workgroup must call it.
+__device__ __forceinline__ int kpn_abs_bits(float a) { return __float_as_int(a) & 0x7fffffff; }
+__device__ __forceinline__ int kpn_abs_bits4(int u, const float4& x) {
+    const int a = max(kpn_abs_bits(x.x), kpn_abs_bits(x.y)), b = max(kpn_abs_bits(x.z), kpn_abs_bits(x.w));
+    return max(u, max(a, b));
 }
-__device__ __forceinline__ float kpn_absmax2(float a, float b) {   // max(|a|, |b|) that keeps a NaN (fmaxf would drop it)
-    const int x = __float_as_int(a) & 0x7fffffff, y = __float_as_int(b) & 0x7fffffff;
-    return __int_as_float(x > y ? x : y);
+__device__ __forceinline__ void kpn_note_absmax(float* __restrict__ flags, int u) {
+    __shared__ int wmax_s[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) u = max(u, __shfl_xor(u, o));
+    if ((threadIdx.x & 63) == 0) wmax_s[threadIdx.x >> 6] = u;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u = max(max(wmax_s[0], wmax_s[1]), max(wmax_s[2], wmax_s[3]));
+        int* f = reinterpret_cast<int*>(flags);
+        if (u > *reinterpret_cast<volatile int*>(f)) atomicMax(f, u);
+    }
 }
 
-__global__ void k_scene_table(int V, const float* __restrict__ KRT, const float* __restrict__ extrin,
-                              const float* __restrict__ kpt3d, float* __restrict__ table, float* __restrict__ flags) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < KPN_SCENE_FLAG_FLOATS) flags[v] = 0.0f;
-    if (v >= V) return;
+// per-view table: KRT rows, extrinsic rows, camera centre = inverse(KRT)[:3,3] (model.py:823-824), keypoints in the camera
+// frame (spatial.py:85).  One workgroup of two wavefronts per view: the first lane of the second wavefront runs the double
+// Gauss-Jordan while the lanes of the first copy the rows, transform the 24 keypoints and zero the tail of the table row.
+__global__ __launch_bounds__(128) void k_scene_table(int V, const float* __restrict__ KRT, const float* __restrict__ extrin,
+                                                     const float* __restrict__ kpt3d, float* __restrict__ table,
+                                                     float* __restrict__ flags) {
+    const int v = blockIdx.x, t = threadIdx.x;
+    if (v == 0 && t < KPN_SCENE_FLAG_FLOATS) flags[t] = 0.0f;
     float* tb = table + (size_t)v * KPN_TBL_STRIDE;
     const float* M = KRT + v * 16;
     const float* E = extrin + v * 16;
-    for (int i = 0; i < 12; ++i) { tb[KPN_TBL_KRT + i] = M[i]; tb[KPN_TBL_EXT + i] = E[i]; }
-    double a[4][8];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) { a[i][j] = (double)M[i * 4 + j]; a[i][4 + j] = (i == j) ? 1.0 : 0.0; }
-    for (int c = 0; c < 4; ++c) {
-        int p = c;
-        for (int r = c + 1; r < 4; ++r) if (fabs(a[r][c]) > fabs(a[p][c])) p = r;
-        if (p != c) for (int j = 0; j < 8; ++j) { double t = a[c][j]; a[c][j] = a[p][j]; a[p][j] = t; }
-        const double d = a[c][c];
-        for (int j = 0; j < 8; ++j) a[c][j] /= d;
-        for (int r = 0; r < 4; ++r) if (r != c) {
-            const double f = a[r][c];
-            for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
+    if (t == 64) {
+        double a[4][8];
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) { a[i][j] = (double)M[i * 4 + j]; a[i][4 + j] = (i == j) ? 1.0 : 0.0; }
+        for (int c = 0; c < 4; ++c) {
+            int p = c;
+            for (int r = c + 1; r < 4; ++r) if (fabs(a[r][c]) > fabs(a[p][c])) p = r;
+            if (p != c) for (int j = 0; j < 8; ++j) { double s = a[c][j]; a[c][j] = a[p][j]; a[p][j] = s; }
+            const double d = a[c][c];
+            for (int j = 0; j < 8; ++j) a[c][j] /= d;
+            for (int r = 0; r < 4; ++r) if (r != c) {
+                const double f = a[r][c];
+                for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j];
+            }
         }
+        for (int i = 0; i < 3; ++i) tb[KPN_TBL_CPOS + i] = (float)a[i][7];
+        tb[KPN_TBL_CPOS + 3] = 0.0f;
     }
-    for (int i = 0; i < 3; ++i) tb[KPN_TBL_CPOS + i] = (float)a[i][7];
-    tb[KPN_TBL_CPOS + 3] = 0.0f;
-    for (int k = 0; k < KPN_NKPT; ++k)
-        for (int i = 0; i < 3; ++i)
-            tb[KPN_TBL_KCAM + k * 3 + i] =
-                KADD(kpn_dot3(kpt3d[k * 3 + 0], kpt3d[k * 3 + 1], kpt3d[k * 3 + 2], E[i * 4 + 0], E[i * 4 + 1], E[i * 4 + 2]),
-                     E[i * 4 + 3]);
-    for (int i = KPN_TBL_KCAM + KPN_NKPT * 3; i < KPN_TBL_STRIDE; ++i) tb[i] = 0.0f;
+    if (t >= 64) return;
+    if (t < 12) { tb[KPN_TBL_KRT + t] = M[t]; tb[KPN_TBL_EXT + t] = E[t]; }
+    for (int e = t; e < KPN_NKPT * 3; e += 64) {
+        const int k = e / 3, i = e - k * 3;
+        tb[KPN_TBL_KCAM + e] =
+            KADD(kpn_dot3(kpt3d[k * 3 + 0], kpt3d[k * 3 + 1], kpt3d[k * 3 + 2], E[i * 4 + 0], E[i * 4 + 1], E[i * 4 + 2]),
+                 E[i * 4 + 3]);
+    }
+    for (int i = KPN_TBL_KCAM + KPN_NKPT * 3 + t; i < KPN_TBL_STRIDE; i += 64) tb[i] = 0.0f;
 }
 
-// (V,3,H,W) image + (V,H,W) mask bytes -> (V,H,W,4) [r,g,b,fg]
-__global__ void k_pack_rgbm(int64_t npix_total, int64_t HW, const float* __restrict__ img,
-                            const uint8_t* __restrict__ mask, float* __restrict__ out, float* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    float amax = 0.0f;
-    if (i < npix_total) {
-        const int64_t v = i / HW, p = i - v * HW;
-        float4 o;
-        o.x = img[(v * 3 + 0) * HW + p];
-        o.y = img[(v * 3 + 1) * HW + p];
-        o.z = img[(v * 3 + 2) * HW + p];
-        o.w = mask ? (mask[i] ? 1.0f : 0.0f) : 1.0f;
-        reinterpret_cast<float4*>(out)[i] = o;
-        amax = kpn_absmax2(kpn_absmax2(o.x, o.y), o.z);
+// (V,3,H,W) image + (V,H,W) mask bytes -> (V,H,W,4) [r,g,b,fg].  A workgroup packs KPN_PACK_PIX pixels of one view, four per
+// thread, a wavefront's lanes on consecutive pixels: every load instruction reads one run of a channel and every store
+// instruction writes 1 KB of consecutive float4.
+#define KPN_PACK_PIX 1024
+__global__ __launch_bounds__(256) void k_pack_rgbm(int HW, int tiles, const float* __restrict__ img,
+                                                   const uint8_t* __restrict__ mask, float* __restrict__ out,
+                                                   float* __restrict__ flags) {
+    const int v = blockIdx.x / tiles;
+    const int p0 = (blockIdx.x - v * tiles) * KPN_PACK_PIX + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
+    const float* src = img + (size_t)v * 3 * HW;
+    const uint8_t* m = mask ? mask + (size_t)v * HW : nullptr;
+    float4* dst = reinterpret_cast<float4*>(out) + (size_t)v * HW;
+    int amax = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = p0 + 64 * j;
+        if (p < HW) {
+            float4 o;
+            o.x = src[p];
+            o.y = src[(size_t)HW + p];
+            o.z = src[2 * (size_t)HW + p];
+            o.w = m ? (m[p] ? 1.0f : 0.0f) : 1.0f;
+            dst[p] = o;
+            amax = max(amax, max(max(kpn_abs_bits(o.x), kpn_abs_bits(o.y)), kpn_abs_bits(o.z)));
+        }
     }
     kpn_note_absmax(flags, amax);
 }
 
-// (V,C,h,w) -> (V,h,w,C); one thread per output element (writes coalesced)
-__global__ void k_nchw_to_nhwc(int64_t total, int C, int64_t hw, const float* __restrict__ in, float* __restrict__ out,
-                               float* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    float x = 0.0f;
-    if (i < total) {
-        const int c = (int)(i % C);
-        const int64_t vp = i / C;
-        const int64_t v = vp / hw, p = vp - v * hw;
-        x = in[(v * C + c) * hw + p];
-        out[i] = x;
+// (V,C,h,w) -> (V,h,w,C) through an LDS tile of KPN_NHWC_TILE floats: TP = tile / C pixels of one view x C channels.  Each
+// channel's run of TP pixels is read coalesced (float4 when `vec`: h*w a multiple of 4 and `in` 16-byte aligned) into
+// tile[c][p]; the channels-last block of the tile is one contiguous run of the output, written as consecutive float4 (the
+// scene workspace is 16-byte aligned, and a tile starts at a multiple of C floats).  The row pitch TP + 1 keeps the lanes
+// of either phase on different banks (or two on one, which a 4-byte LDS access absorbs).  The last tile of a view is partial.
+#define KPN_NHWC_TILE 4096
+template <int C>
+__global__ __launch_bounds__(256) void k_nchw_to_nhwc(int hw, int tiles, int vec, const float* __restrict__ in,
+                                                      float* __restrict__ out, float* __restrict__ flags) {
+    constexpr int TP = KPN_NHWC_TILE / C, PITCH = TP + 1;
+    __shared__ float tile_s[C * PITCH];
+    const int v = blockIdx.x / tiles;
+    const int p0 = (blockIdx.x - v * tiles) * TP;
+    const int np = hw - p0 < TP ? hw - p0 : TP;
+    const float* src = in + (size_t)v * C * hw + p0;
+    int amax = 0;
+    if (vec) {
+        for (int e = threadIdx.x; e < C * (TP / 4); e += 256) {
+            const int c = e / (TP / 4), p = (e % (TP / 4)) * 4;
+            if (p < np) {   // np is a multiple of 4 here
+                const float4 x = *reinterpret_cast<const float4*>(src + (size_t)c * hw + p);
+                float* d = tile_s + c * PITCH + p;
+                d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
+                amax = kpn_abs_bits4(amax, x);
+            }
+        }
+    } else {
+        for (int e = threadIdx.x; e < C * TP; e += 256) {
+            const int c = e / TP, p = e % TP;
+            if (p < np) {
+                const float x = src[(size_t)c * hw + p];
+                tile_s[c * PITCH + p] = x;
+                amax = max(amax, kpn_abs_bits(x));
+            }
+        }
     }
-    kpn_note_absmax(flags, x);
+    __syncthreads();
+    float4* dst = reinterpret_cast<float4*>(out + ((size_t)v * hw + p0) * C);
+    for (int o4 = threadIdx.x; o4 < np * (C / 4); o4 += 256) {
+        const int p = o4 / (C / 4), c = (o4 % (C / 4)) * 4;
+        const float* t = tile_s + c * PITCH + p;
+        dst[o4] = make_float4(t[0], t[PITCH], t[2 * PITCH], t[3 * PITCH]);
+    }
+    kpn_note_absmax(flags, amax);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -493,19 +547,18 @@ __global__ __launch_bounds__(64) void k_importance(int64_t R, int Dm2, int n, co
     }
 }
 
-// z_mid (:1074) and contrib[...,1:-1] (:1075) followed by importance sampling and z_fine = sort(cat[z, z_new]) (:1076),
-// one wavefront per ray (ties between equal depths are ordered coarse-first, which changes nothing — equal depths on a
-// ray are the same point).  Lane k draws sample k.  The two cumsums of the reference stay sequential (torch.cumsum order on the CPU, which the
-// oracle is pinned to): with SMALL (Sc, Sf <= 64) lane i holds element i and the running value walks the lanes through
-// v_readlane; otherwise lane 0 walks LDS.  The new samples are ordered by rank counting unless they already are
-// (uniform u: nearly always); the merged order of two sorted lists is two binary searches per element, with rank
-// counting over the whole list as the fall-back when the coarse depths are not sorted.  Sc, Sf <= 128.
-// One workgroup = 4 wavefronts = 4 rays per iteration.
-#ifndef KPN_SIMT_EMU
-#define KPN_READLANE_F(v, i) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (i)))
-#else
-#define KPN_READLANE_F(v, i) __shfl((v), (i))
-#endif
+// z_mid (:1074) and contrib[...,1:-1] (:1075) followed by importance sampling and z_fine = sort(cat[z, z_new]) (:1076)
+// (ties between equal depths are ordered coarse-first, which changes nothing — equal depths on a ray are the same point).
+// A wavefront takes a group of KPN_FINE_GROUP consecutive rays.
+// Phase A, one lane per ray: the group's contrib rows are staged in LDS (coalesced, odd pitch: the lanes' walks hit different
+// banks), then each lane walks its own row — the two cumsums of the reference stay sequential (torch.cumsum order on the CPU,
+// which the oracle is pinned to), with the additions and the IEEE division of k_importance — and leaves the cdf in the row's place.
+// Phase B, one ray at a time, lane k draws sample k from the ray's cdf row.  The new samples are ordered by rank counting unless
+// they already are (uniform u: nearly always); the merged order of two sorted lists is two binary searches per element, with
+// rank counting over the whole list as the fall-back when the coarse depths are not sorted.  The next ray's coarse depths are
+// loaded while the current ray is worked on.  SMALL: Sc, Sf <= 64, one element of each list per lane; otherwise two (<= 128).
+// One workgroup = 4 wavefronts; the group sizes keep its LDS at 20 / 23 KB, seven or eight workgroups per CU.
+#define KPN_FINE_GROUP(SMALL) ((SMALL) ? 16 : 8)
 template <bool SMALL>
 __global__ __launch_bounds__(256) void k_fine_samples_w(int64_t R, int Sc, int Sf, const float* __restrict__ zc,
                                                         const float* __restrict__ contrib, const float* __restrict__ u,
@@ -513,116 +566,113 @@ __global__ __launch_bounds__(256) void k_fine_samples_w(int64_t R, int Sc, int S
                                                         int16_t* __restrict__ src) {
     constexpr int NE = SMALL ? 1 : 2;   // elements of one list per lane
     constexpr int W = 64 * NE;
-    __shared__ float q_s[SMALL ? 1 : 4][SMALL ? 1 : W];   // (c_i + 1e-5), then / sum (LDS walk only)
-    __shared__ float cdf_s[4][W + 1];
-    __shared__ float zn_s[4][W];       // new samples as drawn
-    __shared__ float ev_s[4][2 * W];   // all Sc + Sf depths: coarse, then new (sorted)
+    constexpr int G = KPN_FINE_GROUP(SMALL);
+    __shared__ float row_s[4][G][W + 1];   // a ray's contrib row (Sc values), then its cdf (Sc - 1)
+    __shared__ float zn_s[4][W];           // new samples as drawn
+    __shared__ float ev_s[4][2 * W];       // all Sc + Sf depths: coarse, then new (sorted)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int Dm2 = Sc - 2, C = Sc - 1, Sfull = Sc + Sf;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < R; r += (int64_t)gridDim.x * 4) {
-        const float* c = contrib + r * Sc + 1;
-        const float* z = zc + r * Sc;
-        for (int i = lane; i < Sc; i += 64) ev_s[w][i] = z[i];
-        if constexpr (SMALL) {
-            float q = lane < Dm2 ? KADD(c[lane], 1e-5f) : 0.0f;
+    for (int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * G; r0 < R; r0 += (int64_t)gridDim.x * 4 * G) {
+        const int ng = R - r0 < G ? (int)(R - r0) : G;
+        float zr[NE];   // the coarse depths of the ray that phase B takes next
+        for (int e = 0; e < NE; ++e) zr[e] = lane + 64 * e < Sc ? zc[r0 * Sc + lane + 64 * e] : 0.0f;
+        for (int g = 0; g < ng; ++g)
+            for (int i = lane; i < Sc; i += 64) row_s[w][g][i] = contrib[(r0 + g) * Sc + i];
+        KPN_WAVE_SYNC();
+        if (lane < ng) {
+            float* q = row_s[w][lane];   // q[i + 1] = contrib[..., 1:-1][i]
             float sum = 0.0f;
-            for (int i = 0; i < Dm2; ++i) sum = KADD(sum, KPN_READLANE_F(q, i));   // :1120-1121, sequential
-            q = q / sum;
-            float run = 0.0f, mine = 0.0f;
+            for (int i = 0; i < Dm2; ++i) sum = KADD(sum, KADD(q[i + 1], 1e-5f));   // :1120-1121, sequential
+            float run = 0.0f;
+            q[0] = 0.0f;
             for (int i = 0; i < Dm2; ++i) {                                        // :1122-1123, sequential
-                run = KADD(run, KPN_READLANE_F(q, i));
-                mine = lane == i + 1 ? run : mine;
-            }
-            if (lane < C) cdf_s[w][lane] = mine;
-        } else {
-            for (int i = lane; i < Dm2; i += 64) q_s[w][i] = KADD(c[i], 1e-5f);
-            KPN_WAVE_SYNC();
-            float sum = 0.0f;
-            if (lane == 0)
-                for (int i = 0; i < Dm2; ++i) sum = KADD(sum, q_s[w][i]);
-            sum = __shfl(sum, 0);
-            for (int i = lane; i < Dm2; i += 64) q_s[w][i] = q_s[w][i] / sum;
-            KPN_WAVE_SYNC();
-            if (lane == 0) {
-                float run = 0.0f;
-                cdf_s[w][0] = 0.0f;
-                for (int i = 0; i < Dm2; ++i) { run = KADD(run, q_s[w][i]); cdf_s[w][i + 1] = run; }
+                run = KADD(run, KADD(q[i + 1], 1e-5f) / sum);
+                q[i + 1] = run;
             }
         }
         KPN_WAVE_SYNC();
-        // inverse-CDF samples (:1125-1147)
-        float v[NE];
-        for (int e = 0; e < NE; ++e) {
-            const int k = lane + 64 * e;
-            v[e] = 0.0f;
-            if (k < Sf) {
-                const float sv = u ? u[r * Sf + k] : kpn_linspace01(k, Sf);
-                int lo = 0, hi = C;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (cdf_s[w][mid] <= sv) lo = mid + 1; else hi = mid;
+        for (int g = 0; g < ng; ++g) {
+            const int64_t r = r0 + g;
+            const float* cdf = row_s[w][g];
+            for (int e = 0; e < NE; ++e)
+                if (lane + 64 * e < Sc) ev_s[w][lane + 64 * e] = zr[e];
+            if (g + 1 < ng)
+                for (int e = 0; e < NE; ++e) zr[e] = lane + 64 * e < Sc ? zc[(r + 1) * Sc + lane + 64 * e] : 0.0f;
+            KPN_WAVE_SYNC();
+            // inverse-CDF samples (:1125-1147)
+            float v[NE];
+            for (int e = 0; e < NE; ++e) {
+                const int k = lane + 64 * e;
+                v[e] = 0.0f;
+                if (k < Sf) {
+                    const float sv = u ? u[r * Sf + k] : kpn_linspace01(k, Sf);
+                    int lo = 0, hi = C;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (cdf[mid] <= sv) lo = mid + 1; else hi = mid;
+                    }
+                    const int ip = lo - 1 < 0 ? 0 : lo - 1;
+                    const int in = lo > C - 1 ? C - 1 : lo;
+                    const float num = KSUB(sv, cdf[ip]);
+                    float den = KSUB(cdf[in], cdf[ip]);
+                    if (den < 1e-5f) den = 1.0f;
+                    const float zp = KMUL(0.5f, KADD(ev_s[w][ip + 1], ev_s[w][ip]));
+                    const float zq = KMUL(0.5f, KADD(ev_s[w][in + 1], ev_s[w][in]));
+                    v[e] = KADD(zp, KMUL(num / den, KSUB(zq, zp)));
+                    zn_s[w][k] = v[e];
                 }
-                const int ip = lo - 1 < 0 ? 0 : lo - 1;
-                const int in = lo > C - 1 ? C - 1 : lo;
-                const float num = KSUB(sv, cdf_s[w][ip]);
-                float den = KSUB(cdf_s[w][in], cdf_s[w][ip]);
-                if (den < 1e-5f) den = 1.0f;
-                const float zp = KMUL(0.5f, KADD(ev_s[w][ip + 1], ev_s[w][ip]));
-                const float zq = KMUL(0.5f, KADD(ev_s[w][in + 1], ev_s[w][in]));
-                v[e] = KADD(zp, KMUL(num / den, KSUB(zq, zp)));
-                zn_s[w][k] = v[e];
             }
+            KPN_WAVE_SYNC();
+            // order the new samples
+            int rk[NE];
+            int unsorted = 0;
+            for (int e = 0; e < NE; ++e) {
+                const int k = lane + 64 * e;
+                rk[e] = k;
+                unsorted |= (k + 1 < Sf) && !(v[e] <= zn_s[w][k + 1 < W ? k + 1 : k]);
+            }
+            if (__any(unsorted)) {
+                for (int e = 0; e < NE; ++e) rk[e] = 0;
+                for (int j = 0; j < Sf; ++j) {
+                    const float o = zn_s[w][j];
+                    for (int e = 0; e < NE; ++e) rk[e] += (o < v[e]) || (o == v[e] && j < lane + 64 * e);
+                }
+            }
+            for (int e = 0; e < NE; ++e)
+                if (lane + 64 * e < Sf) ev_s[w][Sc + rk[e]] = v[e];
+            KPN_WAVE_SYNC();
+            if (znew)
+                for (int k = lane; k < Sf; k += 64) znew[r * Sf + k] = ev_s[w][Sc + k];
+            // merged order
+            int csorted = 1;
+            for (int i = lane; i + 1 < Sc; i += 64) csorted &= ev_s[w][i] <= ev_s[w][i + 1];
+            if (__all(csorted)) {
+                // coarse i goes to i + #{new < it}, new k (sorted position) to k + #{coarse <= it}: a permutation of 0..Sfull-1
+                for (int i = lane; i < Sc; i += 64) {
+                    const float a = ev_s[w][i];
+                    int lo = 0, hi = Sf;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ev_s[w][Sc + mid] < a) lo = mid + 1; else hi = mid; }
+                    zf[r * Sfull + i + lo] = a;
+                    if (src) src[r * Sfull + i + lo] = (int16_t)i;
+                }
+                for (int k = lane; k < Sf; k += 64) {
+                    const float b = ev_s[w][Sc + k];
+                    int lo = 0, hi = Sc;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ev_s[w][mid] <= b) lo = mid + 1; else hi = mid; }
+                    zf[r * Sfull + k + lo] = b;
+                    if (src) src[r * Sfull + k + lo] = (int16_t)(Sc + k);
+                }
+            } else {
+                for (int id = lane; id < Sfull; id += 64) {
+                    const float a = ev_s[w][id];
+                    int rank = 0;
+                    for (int j = 0; j < Sfull; ++j) { const float o = ev_s[w][j]; rank += (o < a) || (o == a && j < id); }
+                    zf[r * Sfull + rank] = a;
+                    if (src) src[r * Sfull + rank] = (int16_t)id;
+                }
+            }
+            KPN_WAVE_SYNC();
         }
-        KPN_WAVE_SYNC();
-        // order the new samples
-        int rk[NE];
-        int unsorted = 0;
-        for (int e = 0; e < NE; ++e) {
-            const int k = lane + 64 * e;
-            rk[e] = k;
-            unsorted |= (k + 1 < Sf) && !(v[e] <= zn_s[w][k + 1 < W ? k + 1 : k]);
-        }
-        if (__any(unsorted)) {
-            for (int e = 0; e < NE; ++e) rk[e] = 0;
-            for (int j = 0; j < Sf; ++j) {
-                const float o = zn_s[w][j];
-                for (int e = 0; e < NE; ++e) rk[e] += (o < v[e]) || (o == v[e] && j < lane + 64 * e);
-            }
-        }
-        for (int e = 0; e < NE; ++e)
-            if (lane + 64 * e < Sf) ev_s[w][Sc + rk[e]] = v[e];
-        KPN_WAVE_SYNC();
-        if (znew)
-            for (int k = lane; k < Sf; k += 64) znew[r * Sf + k] = ev_s[w][Sc + k];
-        // merged order
-        int csorted = 1;
-        for (int i = lane; i + 1 < Sc; i += 64) csorted &= ev_s[w][i] <= ev_s[w][i + 1];
-        if (__all(csorted)) {
-            // coarse i goes to i + #{new < it}, new k (sorted position) to k + #{coarse <= it}: a permutation of 0..Sfull-1
-            for (int i = lane; i < Sc; i += 64) {
-                const float a = ev_s[w][i];
-                int lo = 0, hi = Sf;
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (ev_s[w][Sc + mid] < a) lo = mid + 1; else hi = mid; }
-                zf[r * Sfull + i + lo] = a;
-                if (src) src[r * Sfull + i + lo] = (int16_t)i;
-            }
-            for (int k = lane; k < Sf; k += 64) {
-                const float b = ev_s[w][Sc + k];
-                int lo = 0, hi = Sc;
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (ev_s[w][mid] <= b) lo = mid + 1; else hi = mid; }
-                zf[r * Sfull + k + lo] = b;
-                if (src) src[r * Sfull + k + lo] = (int16_t)(Sc + k);
-            }
-        } else {
-            for (int id = lane; id < Sfull; id += 64) {
-                const float a = ev_s[w][id];
-                int rank = 0;
-                for (int j = 0; j < Sfull; ++j) { const float o = ev_s[w][j]; rank += (o < a) || (o == a && j < id); }
-                zf[r * Sfull + rank] = a;
-                if (src) src[r * Sfull + rank] = (int16_t)id;
-            }
-        }
-        KPN_WAVE_SYNC();
     }
 }
 

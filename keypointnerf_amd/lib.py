@@ -107,6 +107,7 @@ _SIGNATURES = {
     "kpn_pack_weights_device": (ctypes.c_int, [c_p, c_p, c_p]),
     "kpn_scene_workspace_bytes": (c_sz, [ctypes.POINTER(SceneDesc)]),
     "kpn_scene_prepare": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p]),
+    "kpn_scene_layout": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(c_sz)]),
     "kpn_ray_bbox_intersection": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "kpn_make_rays": (ctypes.c_int, [c_p, c_p, c_f, c_f, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     "kpn_importance_sample": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i32, c_p, c_p]),
