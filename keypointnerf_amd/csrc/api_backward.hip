@@ -3,52 +3,105 @@
 namespace {
 const int64_t kBwdChunk = 262144;  // points per pass: V=3 -> 786432 rows x 4.3 KB of dumps = 3.4 GB
 static_assert(kBwdChunk <= 262144, "kUncappedPoints (query_layout) must cover a backward pass");
-#ifdef KPN_SIMT_EMU
-const int kGradWorkers = 3;     // row workers (one workgroup each; its waves are the column groups)
-#else
 #ifndef KPN_GRAD_WORKERS
 #define KPN_GRAD_WORKERS 512    // 2 workgroups per CU
 #endif
-const int kGradWorkers = KPN_GRAD_WORKERS;
-#endif
+const int kGradWorkers = kEmu ? 3 : KPN_GRAD_WORKERS;   // row workers (one workgroup each; its waves are the column groups)
 const int kPartialUnits = 72;   // capacity of the partial-tile scratch in units of (workers x 2048 floats)
-// full = 1: the whole-query reverse (adds the forward row scratch, the per-point dumps and the d x_view rows)
-// colour-head dumps, floats per (point, view) row, in kpn_color_bufs order (X buffers then dA buffers)
-const int kColorLd[25] = {4, 16, KPN_LD_XDIR, KPN_LD_XBL, 64, 32, 32, 32, 2, 32, 32, KPN_LD_XO0, 16, 8,
-                          2, 8, 16, 2, 32, KPN_LD_DV11, 32, 32, 64, KPN_LD_XDIR, 16};
-struct BwdLayout { size_t count, list, X0, X1, X2, X3, D0, D1, D2, D3, partial, dbp, xscr, Xp, Xh0, Xh1, D20, D21, D22, dxrows,
-                   color, color_bytes, Dcmp, total; int64_t chunk; };
-// full: 0 = geometry rows only; 1 = whole query, geometry outputs; 2 = whole query incl. the colour head
+// ---- the buffers one kernel of the backward dumps for another, and the weight-gradient jobs that read them: two tables ----
+struct BwdBufs { kpn_bwd_bufs B; kpn_fuse_bwd_bufs F; kpn_color_bufs C; };   // what the kernels take by value
+// the part of the workspace a dump is carved in, and the `full` (bwd_layout) from which a pass has it
+enum { PART_GEO = 0, PART_FUSE, PART_DXROWS, PART_COLOR, PART_CMP };
+const int kPartFull[5] = {0, 1, 1, 2, 2};
+enum { U_X0 = 0, U_X1, U_X2, U_X3, U_D0, U_D1, U_D2, U_D3, U_XP, U_XH0, U_XH1, U_D20, U_D21, U_D22, U_DXROWS,
+       U_XRD, U_XE1, U_XDIR, U_XBL, U_XB1, U_XA, U_XV10, U_XV11, U_XT33, U_XV20, U_XV21, U_XO0, U_XO1, U_XO2,
+       U_DO2, U_DO1, U_DO0, U_DV21, U_DV20, U_DV11, U_DV10, U_DBL1, U_DBL0, U_DRE1, U_DRE0, U_DCMP, U_COUNT };
+// ld: floats per row, one row per (point, view) or (FUSE, CMP) per point.  The only place a leading dimension is written.
+struct Dump { int id; size_t member; int ld; int part; };
+#define D(id, member, ld, part) {U_##id, offsetof(BwdBufs, member), ld, PART_##part}
+constexpr Dump kDumps[U_COUNT] = {
+    // k_geo_rows_bwd: the inputs X and the dA of layers1
+    D(X0, B.X0, KPN_LDX0, GEO), D(X1, B.X1, 128, GEO), D(X2, B.X2, KPN_LDX2, GEO), D(X3, B.X3, 128, GEO),
+    D(D0, B.D0, 128, GEO), D(D1, B.D1, 128, GEO), D(D2, B.D2, 128, GEO), D(D3, B.D3, 64, GEO),
+    // k_fuse_bwd: layers2 per point, and the d x_view rows k_geo_rows_bwd starts from
+    D(XP, F.Xp, 128, FUSE), D(XH0, F.Xh0, 64, FUSE), D(XH1, F.Xh1, 64, FUSE), D(D20, F.D20, 64, FUSE), D(D21, F.D21, 64, FUSE), D(D22, F.D22, 2, FUSE),
+    D(DXROWS, F.dxrows, 64, DXROWS),
+    // k_color_bwd: the colour head, in kpn_color_bufs order (X buffers then dA buffers); one block of the workspace
+    D(XRD, C.Xrd, 4, COLOR), D(XE1, C.Xe1, 16, COLOR), D(XDIR, C.Xdir, KPN_LD_XDIR, COLOR), D(XBL, C.Xbl, KPN_LD_XBL, COLOR), D(XB1, C.Xb1, 64, COLOR),
+    D(XA, C.Xa, 32, COLOR), D(XV10, C.Xv10, 32, COLOR), D(XV11, C.Xv11, 32, COLOR), D(XT33, C.Xt33, 2, COLOR), D(XV20, C.Xv20, 32, COLOR),
+    D(XV21, C.Xv21, 32, COLOR), D(XO0, C.Xo0, KPN_LD_XO0, COLOR), D(XO1, C.Xo1, 16, COLOR), D(XO2, C.Xo2, 8, COLOR),
+    D(DO2, C.Do2, 2, COLOR), D(DO1, C.Do1, 8, COLOR), D(DO0, C.Do0, 16, COLOR), D(DV21, C.Dv21, 2, COLOR), D(DV20, C.Dv20, 32, COLOR),
+    D(DV11, C.Dv11, KPN_LD_DV11, COLOR), D(DV10, C.Dv10, 32, COLOR), D(DBL1, C.Dbl1, 32, COLOR), D(DBL0, C.Dbl0, 64, COLOR),
+    D(DRE1, C.Dre1, KPN_LD_XDIR, COLOR), D(DRE0, C.Dre0, 16, COLOR),
+    D(DCMP, C.Dcmp, 24, CMP),   // d lat per point
+};
+#undef D
+constexpr bool dumps_in_order() { for (int i = 0; i < U_COUNT; ++i) if (kDumps[i].id != i) return false; return true; }
+static_assert(dumps_in_order(), "kDumps is indexed by the U_* enumerators");
+constexpr bool per_point(const Dump& m) { return m.part == PART_FUSE || m.part == PART_CMP; }
+float*& dump_slot(BwdBufs& u, const Dump& m) { return *reinterpret_cast<float**>(reinterpret_cast<char*>(&u) + m.member); }
+
+// dW[layer] += dY^T X over the (point, view) rows or the points of a pass (whichever X is dumped per); ldy / ldx are the dumps'.
+// M: outputs; Kc: columns of the X dump read (even); Kt: real input features.  In the order the jobs are queued, which fixes
+// their shares of the partial / bias scratch.
+enum { ST_COLOR = 0, ST_LAYERS2, ST_COMPRESS, ST_LAYERS1 };
+struct WgradRow { int stage, dY, X, M, Kc, Kt, layer, mv, cmap, omap; };
+const WgradRow kWgrad[19] = {
+    {ST_COLOR, U_DO2, U_XO2, 1, 8, 8, P_O_2, 1, 0, 0},
+    {ST_COLOR, U_DO1, U_XO1, 8, 16, 16, P_O_1, 1, 0, 0},
+    {ST_COLOR, U_DO0, U_XO0, 16, KPN_LD_XO0, 37, P_O_0, 1, 0, 0},
+    {ST_COLOR, U_DV21, U_XV21, 1, 32, 32, P_V2_1, 1, 0, 0},
+    {ST_COLOR, U_DV20, U_XV20, 32, 32, 32, P_V2_0, 1, 0, 0},
+    {ST_COLOR, U_DV11, U_XV11, 33, 32, 32, P_V1_1, 2, 0, 0},
+    {ST_COLOR, U_DV10, U_XV10, 32, 32, 32, P_V1_0, 1, 0, 0},
+    {ST_COLOR, U_DBL1, U_XB1, 32, 64, 64, P_BL_1, 1, 0, 0},
+    {ST_COLOR, U_DBL0, U_XBL, 64, KPN_LD_XBL, KPN_LD_XBL, P_BL_0, 2, 2, 0},
+    {ST_COLOR, U_DRE1, U_XE1, 35, 16, 16, P_RE_1, 2, 0, 1},
+    {ST_COLOR, U_DRE0, U_XRD, 16, 4, 4, P_RE_0, 1, 0, 0},
+    {ST_LAYERS2, U_D20, U_XP, 64, 128, 128, P_G2_0, 2, 0, 0},
+    {ST_LAYERS2, U_D21, U_XH0, 64, 64, 64, P_G2_1, 2, 0, 0},
+    {ST_LAYERS2, U_D22, U_XH1, 2, 64, 64, P_G2_2, 1, 0, 0},
+    {ST_COMPRESS, U_DCMP, U_XP, 24, 128, 128, P_CMP, 1, 0, 0},
+    {ST_LAYERS1, U_D0, U_X0, 128, 232, 232, P_G1_0, 4, 1, 0},
+    {ST_LAYERS1, U_D1, U_X1, 128, 128, 128, P_G1_1, 4, 0, 0},
+    {ST_LAYERS1, U_D2, U_X2, 120, 136, 136, P_G1_2, 4, 0, 0},
+    {ST_LAYERS1, U_D3, U_X3, 64, 120, 120, P_G1_3, 2, 0, 0},
+};
+static_assert(sizeof(kWgrad) / sizeof(kWgrad[0]) <= KPN_WGRAD_MAX_JOBS, "a pass queues every job");
+
+struct BwdLayout { size_t count, list, partial, dbp, xscr, dump[U_COUNT], total; int64_t chunk; };
+// full: 0 = geometry rows only; 1 = whole query (adds the forward row scratch, the per-point dumps and the d x_view rows), geometry
+// outputs; 2 = whole query incl. the colour head
 BwdLayout bwd_layout(int64_t N, int V, int full) {
     BwdLayout L{};
     L.chunk = N < kBwdChunk ? N : kBwdChunk;
     const size_t ntiles = (size_t)((L.chunk + KPN_TILE - 1) / KPN_TILE);
     const size_t npts = ntiles * KPN_TILE, rows = npts * V;
     Carver c;
+    auto dump_bytes = [&](const Dump& m) { return (per_point(m) ? npts : rows) * m.ld * 4; };
+    auto take_part = [&](int part) { for (const Dump& m : kDumps) if (m.part == part) L.dump[m.id] = c.take(dump_bytes(m)); };
     L.count = c.take(256);
     L.list = c.take((size_t)L.chunk * sizeof(int));
-    L.X0 = c.take(rows * KPN_LDX0 * 4); L.X1 = c.take(rows * 128 * 4); L.X2 = c.take(rows * KPN_LDX2 * 4); L.X3 = c.take(rows * 128 * 4);
-    L.D0 = c.take(rows * 128 * 4); L.D1 = c.take(rows * 128 * 4); L.D2 = c.take(rows * 128 * 4); L.D3 = c.take(rows * 64 * 4);
+    take_part(PART_GEO);
     // partial tile blocks of all weight-gradient jobs of a pass (they run in shared launches): sum over the 19 layers of
     // column groups x MV = 65 -> 72 x workers x 8 KB (checked when the jobs are queued); bias partials per job
     L.partial = c.take((size_t)kPartialUnits * kGradWorkers * (2 * 16 * 64) * 4);
     L.dbp = c.take((size_t)KPN_WGRAD_MAX_JOBS * kGradWorkers * 4 * 64 * 4);
     if (full) {
         L.xscr = c.take(ntiles * (size_t)V * KPN_ROW_SLABS * 64 * sizeof(float4));
-        L.Xp = c.take(npts * 128 * 4); L.Xh0 = c.take(npts * 64 * 4); L.Xh1 = c.take(npts * 64 * 4);
-        L.D20 = c.take(npts * 64 * 4); L.D21 = c.take(npts * 64 * 4); L.D22 = c.take(npts * 2 * 4);
-        L.dxrows = c.take(rows * 64 * 4);
+        take_part(PART_FUSE);
+        take_part(PART_DXROWS);
     }
     if (full == 2) {
-        size_t per_row = 0;
-        for (int i = 0; i < 25; ++i) per_row += kColorLd[i];
-        L.color_bytes = rows * per_row * 4;
-        L.color = c.take(L.color_bytes);
-        L.Dcmp = c.take(npts * 24 * 4);
+        size_t color_bytes = 0;   // the colour head's dumps follow each other in one block
+        for (const Dump& m : kDumps) if (m.part == PART_COLOR) { L.dump[m.id] = c.o + color_bytes; color_bytes += dump_bytes(m); }
+        c.take(color_bytes);
+        take_part(PART_CMP);
     }
     L.total = c.o;
     return L;
 }
+size_t bwd_workspace_bytes(int64_t N, int V, int full) { return (N <= 0 || V <= 0) ? 0 : bwd_layout(N, V, full).total; }
 }  // namespace
 
 // rows[0] = (point, view) rows of the current pass, rows[1] = points, both padded to whole tiles
@@ -59,82 +112,69 @@ __global__ void k_bwd_rows(const int* __restrict__ count, int V, int64_t* __rest
 }
 
 namespace {
-// d_x != nullptr: geometry rows only, upstream gradient given per (point, view).  Otherwise the whole-query reverse from
-// d_out (N,5): its geometry columns only (d_tex == nullptr) or all five incl. the colour head (d_tex != nullptr).
-int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N, const float* pts, const float* view,
-                 int mode, uint32_t keep_mask, const float* noise, float noise_std, const float* d_x, const float* d_out,
-                 float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, void* ws, size_t ws_bytes, void* stream,
-                 const kpn_points* marched = nullptr, void* fwd_query_ws = nullptr) {
-    // fwd_query_ws: the workspace a run_field() call on the SAME points just used: its valid list and row scratch are
-    // reused instead of being recomputed (the train-branch backward runs the forward anyway to get rgba)
-    // marched: the points are ray-marched (cam_pos + dirs * z, as kpn_render_rays evaluates them) instead of explicit;
-    // one pass only (N <= kBwdChunk)
+// One backward pass over N points, as its callers name it: explicit points (with their view and noise) or ray-marched ones (cam_pos +
+// dirs * z, as kpn_render_rays evaluates them; one pass only, N <= kBwdChunk).  d_x: geometry rows only, upstream gradient per (point,
+// view); otherwise the whole-query reverse from d_out (N,5): its geometry columns only (d_tex == nullptr) or all five incl. the colour
+// head.  fwd_query_ws: the workspace a run_field() call on the SAME points just used: its valid list and row scratch are reused.
+struct BackwardPass {
+    int64_t N = 0; int mode = 0; uint32_t keep_mask = 0xFFFFFFFFu;
+    const float *pts = nullptr, *view = nullptr, *noise = nullptr; float noise_std = 0.0f; const kpn_points* marched = nullptr;
+    const float *d_x = nullptr, *d_out = nullptr; float *d_plain = nullptr, *d_geo0 = nullptr, *d_geo1 = nullptr, *d_tex = nullptr;
+    void* ws = nullptr; size_t ws_bytes = 0; void* fwd_query_ws = nullptr;
+};
+int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp, const BackwardPass& p, void* stream) {
     const int V = d->n_views;
-    const int full = d_x != nullptr ? 0 : (d_tex ? 2 : 1);
-    const BwdLayout L = bwd_layout(N, V, full);
-    if (ws_bytes < L.total) return fail(KPN_EWORKSPACE, "backward workspace too small");
-    if (marched && N > L.chunk) return fail(KPN_EINVAL, "ray-marched backward pass too large");
+    const int full = p.d_x != nullptr ? 0 : (p.d_tex ? 2 : 1);
+    const BwdLayout L = bwd_layout(p.N, V, full);
+    if (p.ws_bytes < L.total) return fail(KPN_EWORKSPACE, "backward workspace too small");
+    if (p.marched && p.N > L.chunk) return fail(KPN_EINVAL, "ray-marched backward pass too large");
     kpn_scene_dev sc = scene_dev(d, scene_ws);
-    sc.keep = keep_mask;
-    char* base = static_cast<char*>(ws);
+    sc.keep = p.keep_mask;
+    char* base = static_cast<char*>(p.ws);
     auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     int* count = reinterpret_cast<int*>(base + L.count);  // [0] valid count, [1..3] work tickets of the three persistent kernels
     int64_t* rows_dev = reinterpret_cast<int64_t*>(base + L.count + 64);
     int* list = reinterpret_cast<int*>(base + L.list);
-    kpn_bwd_bufs B;
-    B.X0 = fp(L.X0); B.X1 = fp(L.X1); B.X2 = fp(L.X2); B.X3 = fp(L.X3);
-    B.D0 = fp(L.D0); B.D1 = fp(L.D1); B.D2 = fp(L.D2); B.D3 = fp(L.D3);
-    B.dgeo0 = d_geo0; B.dgeo1 = d_geo1;
-    kpn_fuse_bwd_bufs F{};
-    if (full) {
-        F.Xp = fp(L.Xp); F.Xh0 = fp(L.Xh0); F.Xh1 = fp(L.Xh1); F.D20 = fp(L.D20); F.D21 = fp(L.D21); F.D22 = fp(L.D22);
-        F.dxrows = fp(L.dxrows);
-    }
-    kpn_color_bufs C{};
+    BwdBufs u{};   // the dumps this pass has; the others stay null
+    for (const Dump& m : kDumps) if (full >= kPartFull[m.part]) dump_slot(u, m) = fp(L.dump[m.id]);
+    u.B.dgeo0 = p.d_geo0; u.B.dgeo1 = p.d_geo1;
     if (full == 2) {
-        const size_t rows = (size_t)((L.chunk + KPN_TILE - 1) / KPN_TILE) * KPN_TILE * V;
-        float* q = fp(L.color);
-        float** slots[25] = {&C.Xrd, &C.Xe1, &C.Xdir, &C.Xbl, &C.Xb1, &C.Xa, &C.Xv10, &C.Xv11, &C.Xt33, &C.Xv20, &C.Xv21, &C.Xo0,
-                             &C.Xo1, &C.Xo2, &C.Do2, &C.Do1, &C.Do0, &C.Dv21, &C.Dv20, &C.Dv11, &C.Dv10, &C.Dbl1, &C.Dbl0,
-                             &C.Dre1, &C.Dre0};
-        for (int i = 0; i < 25; ++i) { *slots[i] = q; q += rows * kColorLd[i]; }
-        C.Dcmp = fp(L.Dcmp);
-        C.dtex = d_tex;
-        C.dani = d_plain + kpn_plain_weight_floats() - 1;
-        F.Dcmp = C.Dcmp;
+        u.C.dtex = p.d_tex;
+        u.C.dani = p.d_plain + kpn_plain_weight_floats() - 1;
+        u.F.Dcmp = u.C.Dcmp;
     }
-    float* partial = fp(L.partial);
-    float* dbp = fp(L.dbp);
     const int blocks = field_grid_blocks();
     // rows of views switched off by the train-time dropout are skipped by k_color_bwd (their dumps are never written) and carry a
     // zero upstream gradient in k_geo_rows_bwd: k_weight_grad reads them as zeros by the same mask (no memset of the dumps)
-    const uint32_t wgrad_keep = keep_mask | ~((V >= 32) ? 0xFFFFFFFFu : ((1u << V) - 1u));
-    // dW[layer] += dY^T X over the rows (which = 0) or points (which = 1) of this pass
-    // weight-gradient jobs of a pass: queued while the producers are launched, then run in one launch per MV class
+    const uint32_t wgrad_keep = p.keep_mask | ~((V >= 32) ? 0xFFFFFFFFu : ((1u << V) - 1u));
+    // weight-gradient jobs of a pass: queued stage by stage while the producers are launched, then run in one launch per MV class
     // and one reduce launch
     kpn_wgrad_jobs jobs[3], all;  // MV = 1, 2, 4
     int gzmax[3];
     size_t partial_used = 0;
     bool overflow = false;
-    auto reset_jobs = [&]() { jobs[0].n = jobs[1].n = jobs[2].n = all.n = 0; gzmax[0] = gzmax[1] = gzmax[2] = 0; partial_used = 0; };
-    // which: 0 = (point, view) rows, 1 = points.  Kc: columns of the X dump read (even); Kt: real input features
-    auto wgrad = [&](int mv, int which, const float* dY, int ldy, int M, const float* X, int ldx, int Kc, int Kt, int layer,
-                     int cmap, int omap) {
-        const int cls = mv == 1 ? 0 : (mv == 2 ? 1 : 2);
-        const int gz = (Kc + 63) / 64;
-        kpn_wgrad_job j;
-        j.dY = dY; j.X = X; j.ldy = ldy; j.M = M; j.ldx = ldx; j.Kc = Kc; j.Kt = Kt; j.cmap = cmap; j.omap = omap; j.mv = mv; j.which = which;
-        j.V = which == 0 ? V : 1; j.keep = which == 0 ? wgrad_keep : 0xFFFFFFFFu;
-        j.partial = partial + partial_used;
-        partial_used += (size_t)gz * kGradWorkers * mv * 2048;
-        if (partial_used > (size_t)kPartialUnits * kGradWorkers * 2048 || all.n >= KPN_WGRAD_MAX_JOBS) { overflow = true; return; }
-        j.dbp = dbp + (size_t)all.n * kGradWorkers * 4 * 64;
-        j.dW = d_plain + plain_w_off(layer);
-        j.dB = d_plain + plain_b_off(layer);
-        j.in_dim = plain_dims[layer][1];
-        jobs[cls].j[jobs[cls].n++] = j;
-        all.j[all.n++] = j;
-        if (gz > gzmax[cls]) gzmax[cls] = gz;
+    auto queue_jobs = [&](int stage) {
+        for (const WgradRow& r : kWgrad) {
+            if (r.stage != stage) continue;
+            const Dump &dy = kDumps[r.dY], &x = kDumps[r.X];
+            const int cls = r.mv == 1 ? 0 : (r.mv == 2 ? 1 : 2);
+            const int gz = (r.Kc + 63) / 64;
+            kpn_wgrad_job j;
+            j.dY = dump_slot(u, dy); j.X = dump_slot(u, x); j.ldy = dy.ld; j.M = r.M; j.ldx = x.ld; j.Kc = r.Kc; j.Kt = r.Kt;
+            j.cmap = r.cmap; j.omap = r.omap; j.mv = r.mv;
+            j.which = per_point(x) ? 1 : 0;   // rows[which] (k_bwd_rows) = the job's row count
+            j.V = per_point(x) ? 1 : V; j.keep = per_point(x) ? 0xFFFFFFFFu : wgrad_keep;
+            j.partial = fp(L.partial) + partial_used;
+            partial_used += (size_t)gz * kGradWorkers * r.mv * 2048;
+            if (partial_used > (size_t)kPartialUnits * kGradWorkers * 2048 || all.n >= KPN_WGRAD_MAX_JOBS) { overflow = true; continue; }
+            j.dbp = fp(L.dbp) + (size_t)all.n * kGradWorkers * 4 * 64;
+            j.dW = p.d_plain + plain_w_off(r.layer);
+            j.dB = p.d_plain + plain_b_off(r.layer);
+            j.in_dim = plain_dims[r.layer][1];
+            jobs[cls].j[jobs[cls].n++] = j;
+            all.j[all.n++] = j;
+            if (gz > gzmax[cls]) gzmax[cls] = gz;
+        }
     };
     auto run_jobs = [&]() {
         if (jobs[0].n) KPN_LAUNCH(k_weight_grad<1>, dim3(kGradWorkers, jobs[0].n), dim3(64 * gzmax[0]), stream, jobs[0], (const int64_t*)rows_dev);
@@ -146,18 +186,18 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
         if (all.n) KPN_LAUNCH(k_weight_grad_reduce, dim3((mv_all * 2048 + mv_all * 32 + 31) / 32, gz_all, all.n), dim3(256), stream, all,
                               (int)kGradWorkers);
     };
-    for (int64_t c0 = 0; c0 < N; c0 += L.chunk) {
-        const int64_t n = (N - c0 < L.chunk) ? (N - c0) : L.chunk;
-        const kpn_points ps = marched ? *marched
-                                      : kpn_points{pts + c0 * 3, (view ? view : pts) + c0 * 3, nullptr, nullptr, nullptr, 1,
-                                                   noise ? noise + c0 : nullptr, noise_std};
-        reset_jobs();
+    for (int64_t c0 = 0; c0 < p.N; c0 += L.chunk) {
+        const int64_t n = (p.N - c0 < L.chunk) ? (p.N - c0) : L.chunk;
+        const kpn_points ps = p.marched ? *p.marched
+                                        : kpn_points{p.pts + c0 * 3, (p.view ? p.view : p.pts) + c0 * 3, nullptr, nullptr, nullptr, 1,
+                                                     p.noise ? p.noise + c0 : nullptr, p.noise_std};
+        jobs[0].n = jobs[1].n = jobs[2].n = all.n = 0; gzmax[0] = gzmax[1] = gzmax[2] = 0; partial_used = 0;
         hipMemsetAsync(count, 0, 8 * sizeof(int), (hipStream_t)stream);
         const int* vcount = count;  // valid count of this pass
         float* xscr = full ? fp(L.xscr) : nullptr;
-        if (fwd_query_ws && full) {
+        if (p.fwd_query_ws && full) {
             const QueryLayout Q = query_layout(n, V);
-            char* qb = static_cast<char*>(fwd_query_ws);
+            char* qb = static_cast<char*>(p.fwd_query_ws);
             vcount = reinterpret_cast<const int*>(qb + Q.count);
             list = reinterpret_cast<int*>(qb + Q.list);
             xscr = reinterpret_cast<float*>(qb + Q.xscr);
@@ -167,9 +207,9 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
                        (uint8_t*)nullptr, list, count);
         }
         KPN_LAUNCH(k_bwd_rows, dim3(1), dim3(1), stream, vcount, V, rows_dev);
-        bwd_prof_pass(vcount, V, keep_mask, stream);
+        bwd_prof_pass(vcount, V, p.keep_mask, stream);
         if (full) {
-            if (!fwd_query_ws) {
+            if (!p.fwd_query_ws) {
                 KPN_BPROF(BP_ROWS_FWD);
                 KPN_LAUNCH(k_geo_rows, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 1, xscr,
                            kpn_batch{0, 1 << 30});
@@ -178,43 +218,26 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
                 KPN_BPROF(BP_COLOR_BWD);
                 if (V <= 3)
                     KPN_LAUNCH(k_color_bwd<3>, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 4,
-                               (const float*)xscr, d_out + c0 * 5, C);
+                               (const float*)xscr, p.d_out + c0 * 5, u.C);
                 else
                     KPN_LAUNCH(k_color_bwd<KPN_MAXV>, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 4,
-                               (const float*)xscr, d_out + c0 * 5, C);
+                               (const float*)xscr, p.d_out + c0 * 5, u.C);
             }
-            if (full == 2) {
-                wgrad(1, 0, C.Do2, 2, 1, C.Xo2, 8, 8, 8, P_O_2, 0, 0);
-                wgrad(1, 0, C.Do1, 8, 8, C.Xo1, 16, 16, 16, P_O_1, 0, 0);
-                wgrad(1, 0, C.Do0, 16, 16, C.Xo0, KPN_LD_XO0, KPN_LD_XO0, 37, P_O_0, 0, 0);
-                wgrad(1, 0, C.Dv21, 2, 1, C.Xv21, 32, 32, 32, P_V2_1, 0, 0);
-                wgrad(1, 0, C.Dv20, 32, 32, C.Xv20, 32, 32, 32, P_V2_0, 0, 0);
-                wgrad(2, 0, C.Dv11, KPN_LD_DV11, 33, C.Xv11, 32, 32, 32, P_V1_1, 0, 0);
-                wgrad(1, 0, C.Dv10, 32, 32, C.Xv10, 32, 32, 32, P_V1_0, 0, 0);
-                wgrad(1, 0, C.Dbl1, 32, 32, C.Xb1, 64, 64, 64, P_BL_1, 0, 0);
-                wgrad(2, 0, C.Dbl0, 64, 64, C.Xbl, KPN_LD_XBL, KPN_LD_XBL, KPN_LD_XBL, P_BL_0, 2, 0);
-                wgrad(2, 0, C.Dre1, KPN_LD_XDIR, 35, C.Xe1, 16, 16, 16, P_RE_1, 0, 1);
-                wgrad(1, 0, C.Dre0, 16, 16, C.Xrd, 4, 4, 4, P_RE_0, 0, 0);
-            }
+            if (full == 2) queue_jobs(ST_COLOR);
             {
                 KPN_BPROF(BP_FUSE_BWD);
                 KPN_LAUNCH(k_fuse_bwd, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 2,
-                           (const float*)xscr, mode, d_out + c0 * 5, F);
+                           (const float*)xscr, p.mode, p.d_out + c0 * 5, u.F);
             }
-            wgrad(2, 1, F.D20, 64, 64, F.Xp, 128, 128, 128, P_G2_0, 0, 0);
-            wgrad(2, 1, F.D21, 64, 64, F.Xh0, 64, 64, 64, P_G2_1, 0, 0);
-            wgrad(1, 1, F.D22, 2, 2, F.Xh1, 64, 64, 64, P_G2_2, 0, 0);
-            if (full == 2) wgrad(1, 1, C.Dcmp, 24, 24, F.Xp, 128, 128, 128, P_CMP, 0, 0);
+            queue_jobs(ST_LAYERS2);
+            if (full == 2) queue_jobs(ST_COMPRESS);
         }
         {
             KPN_BPROF(BP_ROWS_BWD);
             KPN_LAUNCH(k_geo_rows_bwd, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 3,
-                       full ? (const float*)F.dxrows : d_x + c0 * V * 64, full ? 1 : 0, B);
+                       full ? (const float*)u.F.dxrows : p.d_x + c0 * V * 64, full ? 1 : 0, u.B);
         }
-        wgrad(4, 0, B.D0, 128, 128, B.X0, KPN_LDX0, 232, 232, P_G1_0, 1, 0);
-        wgrad(4, 0, B.D1, 128, 128, B.X1, 128, 128, 128, P_G1_1, 0, 0);
-        wgrad(4, 0, B.D2, 128, 120, B.X2, KPN_LDX2, 136, 136, P_G1_2, 0, 0);
-        wgrad(2, 0, B.D3, 64, 64, B.X3, 128, 120, 120, P_G1_3, 0, 0);
+        queue_jobs(ST_LAYERS1);
         if (overflow) return fail(KPN_EWORKSPACE, "weight-gradient scratch too small (internal)");
         {
             KPN_BPROF(BP_WGRAD);
@@ -225,10 +248,7 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
 }
 }  // namespace
 
-extern "C" size_t kpn_geo_rows_backward_workspace_bytes(int64_t N, int32_t V) {
-    if (N <= 0 || V <= 0) return 0;
-    return bwd_layout(N, V, 0).total;
-}
+extern "C" size_t kpn_geo_rows_backward_workspace_bytes(int64_t N, int32_t V) { return bwd_workspace_bytes(N, V, 0); }
 
 extern "C" int kpn_geo_rows_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N,
                                      const float* pts, uint32_t keep_mask, const float* d_x, float* d_plain, float* d_geo0,
@@ -237,14 +257,13 @@ extern "C" int kpn_geo_rows_backward(const kpn_scene_desc* d, const void* scene_
     KPN_REQUIRE(N >= 0 && N < (1ll << 31), "point count out of range");
     if (N == 0) return KPN_OK;
     KPN_REQUIRE(scene_ws && wp && pts && d_x && d_plain && d_geo0 && d_geo1 && ws, "null pointer");
-    return run_backward(d, scene_ws, wp, N, pts, nullptr, 0, keep_mask, nullptr, 0.0f, d_x, nullptr, d_plain, d_geo0, d_geo1, nullptr,
-                        ws, ws_bytes, stream);
+    BackwardPass p;
+    p.N = N; p.pts = pts; p.keep_mask = keep_mask; p.d_x = d_x;
+    p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.ws = ws; p.ws_bytes = ws_bytes;
+    return run_backward(d, scene_ws, wp, p, stream);
 }
 
-extern "C" size_t kpn_query_backward_geometry_workspace_bytes(int64_t N, int32_t V) {
-    if (N <= 0 || V <= 0) return 0;
-    return bwd_layout(N, V, 1).total;
-}
+extern "C" size_t kpn_query_backward_geometry_workspace_bytes(int64_t N, int32_t V) { return bwd_workspace_bytes(N, V, 1); }
 
 extern "C" int kpn_query_backward_geometry(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N,
                                            const float* pts, int32_t mode, uint32_t keep_mask, const float* noise,
@@ -255,14 +274,13 @@ extern "C" int kpn_query_backward_geometry(const kpn_scene_desc* d, const void* 
     KPN_REQUIRE(N >= 0 && N < (1ll << 31), "point count out of range");
     if (N == 0) return KPN_OK;
     KPN_REQUIRE(scene_ws && wp && pts && d_out && d_plain && d_geo0 && d_geo1 && ws, "null pointer");
-    return run_backward(d, scene_ws, wp, N, pts, nullptr, mode, keep_mask, noise, noise_std, nullptr, d_out, d_plain, d_geo0,
-                        d_geo1, nullptr, ws, ws_bytes, stream);
+    BackwardPass p;
+    p.N = N; p.pts = pts; p.mode = mode; p.keep_mask = keep_mask; p.noise = noise; p.noise_std = noise_std; p.d_out = d_out;
+    p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.ws = ws; p.ws_bytes = ws_bytes;
+    return run_backward(d, scene_ws, wp, p, stream);
 }
 
-extern "C" size_t kpn_query_backward_workspace_bytes(int64_t N, int32_t V) {
-    if (N <= 0 || V <= 0) return 0;
-    return bwd_layout(N, V, 2).total;
-}
+extern "C" size_t kpn_query_backward_workspace_bytes(int64_t N, int32_t V) { return bwd_workspace_bytes(N, V, 2); }
 
 extern "C" int kpn_query_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N, const float* pts,
                                   const float* view, int32_t mode, uint32_t keep_mask, const float* noise, float noise_std,
@@ -273,6 +291,8 @@ extern "C" int kpn_query_backward(const kpn_scene_desc* d, const void* scene_ws,
     KPN_REQUIRE(N >= 0 && N < (1ll << 31), "point count out of range");
     if (N == 0) return KPN_OK;
     KPN_REQUIRE(scene_ws && wp && pts && view && d_out && d_plain && d_geo0 && d_geo1 && d_tex && ws, "null pointer");
-    return run_backward(d, scene_ws, wp, N, pts, view, mode, keep_mask, noise, noise_std, nullptr, d_out, d_plain, d_geo0, d_geo1,
-                        d_tex, ws, ws_bytes, stream);
+    BackwardPass p;
+    p.N = N; p.pts = pts; p.view = view; p.mode = mode; p.keep_mask = keep_mask; p.noise = noise; p.noise_std = noise_std; p.d_out = d_out;
+    p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.d_tex = d_tex; p.ws = ws; p.ws_bytes = ws_bytes;
+    return run_backward(d, scene_ws, wp, p, stream);
 }

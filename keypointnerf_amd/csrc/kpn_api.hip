@@ -18,6 +18,7 @@
 #include "field_kernels.hip"
 #ifdef KPN_SIMT_EMU
 #include "geo_rows_pair_kernels.hip"   // the device build compiles this kernel as its own translation unit (geo_rows_pair_tu.hip)
+#include "geo_rows_pair_launch.h"      // ... with these launchers, which the device build only declares:
 #else
 extern "C" void kpn_internal_launch_row_records(int blocks, void* stream, const kpn_scene_dev* sc, const kpn_points* ps, const float* wp, const int* list,
                                                 const int* count, float* xscr, const kpn_batch* batch);
