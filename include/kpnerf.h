@@ -46,6 +46,9 @@ extern "C" {
  * kpn_avg_pool2_backward, kpn_upsample2x_add_forward, kpn_upsample2x_add_backward (nothing of ABI 9 changed) */
 /* still 10: kpn_scene_layout (where kpn_scene_prepare puts each prepared map in the scene workspace) is one more export and changes
  * nothing that a caller built against 10 uses, so the number stays; a binding that wants it looks the symbol up */
+/* still 10: the stride-2, stem and transposed convolutions with their gradients (kpn_conv2d_s2_desc, kpn_conv2d_s2_packed_floats,
+ * kpn_conv2d_s2_pack_device, kpn_conv2d_s2_workspace_bytes, kpn_conv2d_s2_wgrad_ranges, kpn_conv2d_s2_forward, kpn_conv2d_s2_backward)
+ * are additive within 10: nothing that a caller built against 10 uses changed, kpn_conv2d_* and its refusals included */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -628,6 +631,45 @@ int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, const float*
                        void* workspace, size_t workspace_bytes, void* stream);
 int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
                         float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The resolution-changing layers of the image encoders, forward and backward: the three kinds kpn_conv2d_* refuses.  groups = 1,
+ * dilation = 1, zero padding, optional bias, fp32.  Activations are NHWC (torch channels_last) except the stem's input, which is
+ * NCHW and read as it is (an already normalised tensor: no 2 x - 1).  Kernels: csrc/encoder_kernels.hip, the encoders' own.
+ *   KPN_S2_CONV3    y (N, H/2, W/2, cout) = conv(x (N, H, W, cin), w OIHW, stride 2, pad 1)
+ *                   dx = conv_transpose(dy, w, stride 2, pad 1, output_padding 1): the four-gather transposed kernel over a second
+ *                   packed copy of the same weight - exact for even H, W, which is why odd ones are refused
+ *                   dw: the stride-1 layer's weight gradient with stride-2 im2col rows
+ *   KPN_S2_STEM7    y (N, Ho, Wo, cout) = conv(x (N, cin, H, W), w OIHW, stride 2, pad 3), Ho = (H - 1) / 2 + 1; no input gradient;
+ *                   dw: the same GEMM over K rows tap * 4 + ci, the padded channel never loaded and never stored
+ *   KPN_S2_DECONV3  y (N, 2H, 2W, cout) = conv_transpose(x (N, H, W, cin), w (cin, cout, 3, 3), stride 2, pad 1, output_padding 1)
+ *                   dx = conv(dy, w read as OIHW, stride 2, pad 1)
+ *                   dw (cin, cout, 3, 3): that convolution's weight gradient with the roles swapped - im2col rows from dy, the
+ *                   other operand x, over the N H W source pixels
+ *   db[co] = sum over the pixels of dy, as kpn_conv2d_backward.
+ * Split K, the ranges of the weight gradient (the rule of kpn_conv2d_wgrad_ranges over the GEMM named above: K rows kh kw cin_p with
+ * cin_p = cin rounded up to 4, the GEMM's cout and pixel count), fp64 range sums and the fixed-order combine are those of
+ * kpn_conv2d_*: no float atomics, bit-identical from run to run.
+ * kpn_conv2d_s2_packed_floats / _pack_device read only kind, cin, cout: `packed` (device, 16-byte aligned) holds the forward copy,
+ * then (not for the stem) the input-gradient copy.  `workspace` (kpn_conv2d_s2_workspace_bytes, 16-byte aligned; 0 = unsupported
+ * descriptor) serves the forward and the backward alike.  bias: NULL exactly when has_bias = 0.
+ * kpn_conv2d_s2_backward: each of dx, dw, db may be NULL - that leg is not launched and nothing is written for it; dw and db are
+ * overwritten, not accumulated.  packed is read for dx only, x for dw only.  A refused call (KPN_EINVAL; kpn_last_error() names the
+ * field) launches nothing. */
+enum { KPN_S2_CONV3 = 0,    /* Conv2d(k=3, stride 2, pad 1); NHWC x; H, W even; cin, cout multiples of 4 in 4..1024 */
+       KPN_S2_STEM7 = 1,    /* Conv2d(k=7, stride 2, pad 3); x is NCHW (N, cin, H, W), 1 <= cin <= 4, any H, W >= 1;
+                               cout a multiple of 4 in 4..1024; no input gradient (dx must be NULL) */
+       KPN_S2_DECONV3 = 2 };/* ConvTranspose2d(k=3, stride 2, pad 1, output_padding 1); NHWC x (N,H,W,cin) -> y (N,2H,2W,cout);
+                               weight (cin, cout, 3, 3); cin, cout multiples of 4 in 4..1024 */
+typedef struct kpn_conv2d_s2_desc { int32_t N, H, W, cin, cout, kind, has_bias; } kpn_conv2d_s2_desc;
+size_t kpn_conv2d_s2_packed_floats(const kpn_conv2d_s2_desc* desc);
+int kpn_conv2d_s2_pack_device(const kpn_conv2d_s2_desc* desc, const float* w, float* packed, void* stream);
+size_t kpn_conv2d_s2_workspace_bytes(const kpn_conv2d_s2_desc* desc);
+int32_t kpn_conv2d_s2_wgrad_ranges(const kpn_conv2d_s2_desc* desc);
+int kpn_conv2d_s2_forward(const kpn_conv2d_s2_desc* desc, const float* x, const float* packed, const float* bias, float* y,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv2d_s2_backward(const kpn_conv2d_s2_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
+                           float* db, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One normalisation of the image encoders with the ReLU behind it, forward and backward: replaces torch.nn.functional.group_norm

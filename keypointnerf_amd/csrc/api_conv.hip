@@ -3,7 +3,8 @@
 // them: reference src/utils.py:416-474, 261-309, 322-414).  Kernels: encoder_kernels.hip.  The forward and the input gradient
 // are k_enc_conv over two packed copies of the weight, sized and launched by the launch layer at the head of api_encoders.hip
 // (enc::conv_geom / enc::launch_conv: the walk's own tiles and split K); the weight gradient is k_enc_wgrad / k_enc_wgrad_combine
-// on the forward's tile, the bias gradient k_enc_dbias_partial / k_enc_dbias_final.
+// on the forward's tile (enc::wgrad_plan / enc::launch_wgrad), the bias gradient k_enc_dbias_partial / k_enc_dbias_final
+// (enc::launch_dbias).  api_strided.hip serves the stride-2, stem and transposed layers through the same layer.
 namespace conv {
 // what the packed copies depend on
 const char* weight_error(const kpn_conv2d_desc* d) {
@@ -22,12 +23,11 @@ const char* desc_error(const kpn_conv2d_desc* d) {
     if (d->has_bias != 0 && d->has_bias != 1) return "has_bias must be 0 or 1";
     return nullptr;
 }
-// The ranges of the weight gradient: a range is `cpr` chunks of 16 output pixels, at least 20 (320 pixels: what a tile's store
-// and combine are worth) and otherwise as many as leave about 1024 workgroups, at most 64 ranges.  From the shape alone.
+// the forward's and the input gradient's GEMMs, the weight gradient's ranges (enc::wgrad_plan) and the workspace
 struct Plan {
     int Ho, Wo;
     enc::ConvGeom fwd, dx;
-    int wg_tiles, krows, nchunks, cpr, nranges, db_chunks;
+    enc::WgradPlan wg;
     size_t o_fwd, o_dx, o_wg, o_db, bytes;
 };
 Plan plan(const kpn_conv2d_desc* d) {
@@ -35,20 +35,13 @@ Plan plan(const kpn_conv2d_desc* d) {
     p.Ho = d->H + 2 * d->pad - d->k + 1; p.Wo = d->W + 2 * d->pad - d->k + 1;
     p.fwd = enc::conv_geom(d->N, p.Ho, p.Wo, d->cin, d->cout, d->k, d->k, 0);
     p.dx = enc::conv_geom(d->N, d->H, d->W, d->cout, d->cin, d->k, d->k, 0);
-    const int64_t M = p.fwd.M;
-    p.krows = d->k * d->k * d->cin;
-    p.wg_tiles = (p.krows + p.fwd.bm - 1) / p.fwd.bm * (p.fwd.a.cout_p / p.fwd.bn);      // the forward's tile over (K rows, cout)
-    p.nchunks = (int)((M + 15) / 16);
-    const int rmax = std::max(1, std::min(64, 1024 / p.wg_tiles));
-    p.cpr = std::max(20, (p.nchunks + rmax - 1) / rmax);
-    p.nranges = (p.nchunks + p.cpr - 1) / p.cpr;
-    p.db_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(256, M / 256));
+    p.wg = enc::wgrad_plan(p.fwd);                                  // the forward's tile over (K rows, cout)
     // the forward and the backward never run at once on a workspace: the larger of the two
     Carver f, b;
     p.o_fwd = f.take((size_t)p.fwd.partial * sizeof(float));
     p.o_dx = b.take((size_t)p.dx.partial * sizeof(float));
-    p.o_wg = b.take((size_t)p.nranges * p.krows * d->cout * sizeof(float));
-    p.o_db = b.take((size_t)p.db_chunks * d->cout * sizeof(double));
+    p.o_wg = b.take((size_t)p.wg.partial * sizeof(float));
+    p.o_db = b.take((size_t)enc::dbias_chunks(p.fwd.M) * d->cout * sizeof(double));
     p.bytes = std::max<size_t>(std::max(f.o, b.o), 256);
     return p;
 }
@@ -86,7 +79,7 @@ extern "C" size_t kpn_conv2d_workspace_bytes(const kpn_conv2d_desc* desc) {
     return conv::desc_error(desc) ? 0 : conv::plan(desc).bytes;
 }
 extern "C" int32_t kpn_conv2d_wgrad_ranges(const kpn_conv2d_desc* desc) {
-    return conv::desc_error(desc) ? 0 : conv::plan(desc).nranges;
+    return conv::desc_error(desc) ? 0 : conv::plan(desc).wg.nranges;
 }
 extern "C" int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, const float* packed, const float* bias, float* y,
                                   void* workspace, size_t workspace_bytes, void* stream) {
@@ -115,21 +108,11 @@ extern "C" int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, 
     if (dx)     // dX = conv(dY, w'[ci][co][k - 1 - ky][k - 1 - kx], pad k - 1 - p)
         conv::run(p.dx, p.Ho, p.Wo, k - 1 - desc->pad, dy, packed + p.fwd.packed, nullptr, dx, reinterpret_cast<float*>(ws + p.o_dx), stream);
     if (dw) {
-        kpn_enc_wgrad_args a{};
-        a.c = p.fwd.a;
-        a.c.Hs = desc->H; a.c.Ws = desc->W; a.c.stride = 1; a.c.pad = desc->pad;
-        a.c.src = x; a.c.src_cs = desc->cin;
-        a.dy = dy; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
-        a.partial = reinterpret_cast<float*>(ws + p.o_wg); a.dw = dw;
-        const dim3 grid((unsigned)p.wg_tiles, (unsigned)p.nranges);
-        if (p.fwd.bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64>), grid, dim3(256), stream, a);
-        else KPN_LAUNCH((k_enc_wgrad<128, 32>), grid, dim3(256), stream, a);
-        KPN_LAUNCH(k_enc_wgrad_combine, enc::grid4((int64_t)p.krows * desc->cout), dim3(256), stream, a);
+        kpn_enc_conv_args c = p.fwd.a;
+        c.Hs = desc->H; c.Ws = desc->W; c.stride = 1; c.pad = desc->pad;
+        c.src = x; c.src_cs = desc->cin;
+        enc::launch_wgrad(c, p.fwd, p.wg, 0, dy, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
     }
-    if (db) {
-        kpn_enc_dbias_args a{dy, (int64_t)desc->N * p.Ho * p.Wo, desc->cout, p.db_chunks, reinterpret_cast<double*>(ws + p.o_db), db};
-        KPN_LAUNCH(k_enc_dbias_partial, dim3((unsigned)p.db_chunks), dim3(256), stream, a);
-        KPN_LAUNCH(k_enc_dbias_final, dim3((unsigned)((desc->cout + 63) / 64)), dim3(64), stream, a);
-    }
+    if (db) enc::launch_dbias(dy, p.fwd.M, desc->cout, reinterpret_cast<double*>(ws + p.o_db), db, stream);
     return check_launch("kpn_conv2d_backward");
 }

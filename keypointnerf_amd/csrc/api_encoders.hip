@@ -6,8 +6,8 @@
 // (keypointnerf_amd/encoders.py builds it from the caller's module in the same order).
 //
 // In front of the walks, the launch layer of encoder_kernels.hip: every launch policy of the kernels that the walks share with
-// the differentiable layers (api_conv.hip, api_norm.hip, api_resample.hip) - tiles, split K, chunk counts, grids - is written
-// there once, and all four files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
+// the differentiable layers (api_conv.hip, api_strided.hip, api_norm.hip, api_resample.hip) - tiles, split K, the ranges of a weight
+// gradient, chunk counts, grids - is written there once, and all five files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
 // so a walk and a layer agree bit for bit only while they share this code.
 namespace enc {
 
@@ -70,6 +70,50 @@ inline void launch_pack(const ConvGeom& g, int tflip, const float* w, float* wp,
         const int64_t n = (int64_t)g.a.nk[c] * g.a.cout_p * 16;
         KPN_LAUNCH(k_enc_pack, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), stream, pa);
     }
+}
+// The weight gradient of the GEMM `g` (k_enc_wgrad on g's tile over (K rows, cout), then k_enc_wgrad_combine).  Its ranges: a range is
+// `cpr` chunks of 16 GEMM pixels, at least 20 (320 pixels: what a tile's store and combine are worth) and otherwise as many as leave
+// about 1024 workgroups, at most 64 ranges.  From the shape alone.
+struct WgradPlan {
+    int krows;                     // kh * kw * cin: the rows of `partial` and of dW
+    int tiles, nchunks, cpr, nranges;
+    int64_t partial;               // floats: [range][krows][cout]
+};
+inline WgradPlan wgrad_plan(const ConvGeom& g) {
+    WgradPlan p{};
+    const kpn_enc_conv_args& a = g.a;
+    p.krows = a.kh * a.kw * a.cin;
+    p.tiles = (a.kh * a.kw * a.cin_p + g.bm - 1) / g.bm * (a.cout_p / g.bn);
+    p.nchunks = (int)((g.M + 15) / 16);
+    const int rmax = std::max(1, std::min(64, 1024 / p.tiles));
+    p.cpr = std::max(20, (p.nchunks + rmax - 1) / rmax);
+    p.nranges = (p.nchunks + p.cpr - 1) / p.cpr;
+    p.partial = (int64_t)p.nranges * p.krows * a.cout;
+    return p;
+}
+// `c`: g.a with the source of A filled in (Hs, Ws, stride, pad, src, src_cs; the stem's Hraw, Wraw, stem_plain); rhs (g.M, cout) dense
+inline void launch_wgrad(const kpn_enc_conv_args& c, const ConvGeom& g, const WgradPlan& p, int stem, const float* rhs, float* partial,
+                         float* dw, void* stream) {
+    kpn_enc_wgrad_args a{};
+    a.c = c;
+    a.rhs = rhs; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
+    a.partial = partial; a.dw = dw;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.nranges);
+    if (stem) {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64, true>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_wgrad<128, 32, true>), grid, dim3(256), stream, a);
+    } else {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64, false>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_wgrad<128, 32, false>), grid, dim3(256), stream, a);
+    }
+    KPN_LAUNCH(k_enc_wgrad_combine, grid4((int64_t)c.kh * c.kw * c.cin_p * c.cout), dim3(256), stream, a);
+}
+// the bias gradient: db[c] = sum over the M rows of dy (M, C); `partial` holds dbias_chunks(M) * C doubles
+inline int dbias_chunks(int64_t M) { return (int)std::max<int64_t>(1, std::min<int64_t>(256, M / 256)); }
+inline void launch_dbias(const float* dy, int64_t M, int C, double* partial, float* db, void* stream) {
+    kpn_enc_dbias_args a{dy, M, C, dbias_chunks(M), partial, db};
+    KPN_LAUNCH(k_enc_dbias_partial, dim3((unsigned)a.nchunks), dim3(256), stream, a);
+    KPN_LAUNCH(k_enc_dbias_final, dim3((unsigned)((C + 63) / 64)), dim3(64), stream, a);
 }
 // statistics: pixel chunks per image (from the shape alone; the forward and the backward of a norm share it) and the doubles of
 // the partials [image][chunk][channel][2]

@@ -10,7 +10,8 @@
 // eight MFMAs; the loads of chunk s + 1 are in flight while chunk s is multiplied.
 //   loads    : zero padding or replication padding (a clamp of the source coordinate), stride 1 / 2; per (image, channel)
 //              scale * x + shift with optional ReLU (GroupNorm / InstanceNorm + ReLU in front of the convolution); the stems read
-//              the NCHW images, average 2 x 2 blocks when ds = 1 (the avg_pool2d of attach_*_feat; the host admits ds <= 1) and apply 2 * im - 1;
+//              the NCHW images, average 2 x 2 blocks when ds = 1 (the avg_pool2d of attach_*_feat; the host admits ds <= 1) and apply
+//              2 * im - 1 (stem_plain = 0, the walks) or nothing (stem_plain = 1, a module's own stem layer);
 //   DECONV   : ConvTranspose2d(k = 3, stride = 2, padding = 1, output_padding = 1) as four gathers, one per output parity
 //              (py, px) with (1 + py) * (1 + px) valid taps each (blockIdx.z) — no scatter;
 //   epilogue : bias, residual add from a second tensor, ReLU, store into a channel slice of a wider NHWC tensor;
@@ -38,6 +39,8 @@ struct kpn_enc_conv_args {
     const float* src;          // NHWC, pointer at the first channel of the slice; STEM: NCHW (nimg, cin, Hraw, Wraw)
     int src_cs;                // channel stride of a source pixel
     int Hraw, Wraw, ds;        // STEM
+    int stem_plain;            // STEM: 0 = the walks' raw images in [0, 1], loaded as 2 * im - 1; 1 = an already normalised tensor,
+                               // loaded as it is (a module's own stem layer, api_strided.hip)
     const float* ss;           // scale [nimg][cin] then shift [nimg][cin], or NULL
     int relu_in;
     const float* wp;           // packed [chunk][cout_p][16]
@@ -98,7 +101,8 @@ __device__ __forceinline__ kpn_f32x4 kpn_enc_load_a(const kpn_enc_conv_args& a, 
             float s = 0.0f;
             for (int j = 0; j < f; ++j)
                 for (int i = 0; i < f; ++i) s = KADD(s, p[(size_t)j * a.Wraw + i]);
-            v[e] = KSUB(KMUL(2.0f, KMUL(s, inv)), 1.0f);
+            const float m = KMUL(s, inv);
+            v[e] = a.stem_plain ? m : KSUB(KMUL(2.0f, m), 1.0f);
         }
     } else {
         v = *KPN_GLOBAL4(a.src + (((size_t)n * a.Hs + sy) * a.Ws + sx) * a.src_cs + c);
@@ -580,26 +584,37 @@ __global__ __launch_bounds__(256) void k_enc_pack(kpn_enc_pack_args a) {
     }
 }
 
-// ---- gradients of one stride-1 convolution (api_conv.hip).  The input gradient is k_enc_conv over the tflip copy of the weight.
+// ---- gradients of one convolution (api_conv.hip: stride 1; api_strided.hip: stride 2, the 7 x 7 stem, ConvTranspose2d).  The input
+// gradient is k_enc_conv over another packed copy of the weight.
 //
-// Weight gradient: dW[(tap, ci)][co] = sum over output pixels of A[pixel][(tap, ci)] * dY[pixel][co], A the forward's implicit
-// im2col row (kpn_enc_load_a: the padding logic exists once).  The MFMA K dimension is the pixel index.  A workgroup of four
+// Weight gradient: dW[(tap, ci)][co] = sum over GEMM pixels of A[pixel][(tap, ci)] * R[pixel][co], A the implicit im2col row of a
+// convolution (kpn_enc_load_a: the padding, stride and stem logic exists once) and R the dense tensor on that convolution's output
+// grid.  A Conv2d: A from x, R = dY.  A ConvTranspose2d(k 3, s 2, p 1, op 1) is the adjoint of the stride-2 convolution that reads
+// its (cin, cout, 3, 3) weight as OIHW, so the roles swap: A from dY (2H, 2W), R = x over the N H W source pixels, and the OIHW
+// result is the layer's own layout.  The MFMA K dimension is the pixel index.  A workgroup of four
 // wavefronts owns BM K-rows x BN output channels (64 x 64, or 128 x 32 for at most 32 output channels), one 32 x 32 accumulator per
 // wavefront, and walks the 16-pixel chunks [range * cpr, (range + 1) * cpr) of blockIdx.y: both operands are staged in LDS per
 // chunk (pixel-major: the lanes of an MFMA operand read consecutive floats of one pixel) with the next chunk's loads in flight.
 // After every chunk the accumulator is added to an fp64 sum and cleared: no fp32 chain is longer than 16 pixels (activations behind
 // a ReLU times a gradient with a mean give sums of like-signed terms, whose fp32 chains lose a digit per 100 terms).  The tile of a
-// range goes, rounded to fp32, to partial[range][k-row][co] - padded K rows and channels are never stored - and
+// range goes, rounded to fp32, to partial[range][tap * cin + ci][co] - padded K rows and channels are never stored - and
 // k_enc_wgrad_combine adds the ranges in order in fp64, rounds once and writes OIHW.  No atomics.
+// The GEMM's K-rows are tap * cin_p + ci (cin_p > cin for the stems only: STEM loads the NCHW tensor through
+// kpn_enc_load_a<true, false>); kpn_enc_wgrad_row maps one to its real row in `partial`, for the store and the combine alike.
 struct kpn_enc_wgrad_args {
-    kpn_enc_conv_args c;       // the forward's geometry and source (ss = NULL, no ReLU); wp, dst, partial unused
-    const float* dy;           // NHWC (nimg, Ho, Wo, cout), dense
-    int krows;                 // kh * kw * cin
+    kpn_enc_conv_args c;       // the geometry and source of A (ss = NULL, no ReLU); wp, dst, partial unused
+    const float* rhs;          // R: NHWC (nimg, Ho, Wo, cout), dense
+    int krows;                 // kh * kw * cin: the real rows
     int nchunks, cpr, nranges; // 16-pixel chunks in all / per range; ranges (gridDim.y)
     float* partial;            // [range][krows][cout]
     float* dw;                 // OIHW
 };
-template <int BM, int BN>
+// GEMM K-row kp = tap * cin_p + ci -> tap and the row tap * cin + ci of `partial`, or -1 for a padded tap or channel
+__device__ __forceinline__ int kpn_enc_wgrad_row(const kpn_enc_conv_args& c, int kp, int& tap, int& ci) {
+    tap = kp / c.cin_p; ci = kp - tap * c.cin_p;
+    return tap < c.kh * c.kw && ci < c.cin ? tap * c.cin + ci : -1;
+}
+template <int BM, int BN, bool STEM>
 __global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
     static_assert((BM / 32) * (BN / 32) == 4, "four wavefronts, one 32 x 32 accumulator each");
     constexpr int QA = BM / 4, PA = 256 / QA, NA = 16 / PA;     // K-row quads per chunk row; pixels per pass; passes
@@ -622,12 +637,12 @@ __global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
             const int64_t p = (int64_t)s * 16 + ap + j * PA;
             const bool valid = p < M;
             const int n = valid ? (int)(p / hw) : 0, rem = valid ? (int)(p % hw) : 0;
-            ra[j] = kpn_enc_load_a<false, false>(a.c, 0, valid, n, rem / a.c.Wo, rem % a.c.Wo, kt * BM + aq * 4);
+            ra[j] = kpn_enc_load_a<STEM, false>(a.c, 0, valid, n, rem / a.c.Wo, rem % a.c.Wo, kt * BM + aq * 4);
         }
         if (bload) {
             const int64_t p = (int64_t)s * 16 + bp;
             rb = kpn_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.dy + (size_t)p * a.c.cout + bco);
+            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.rhs + (size_t)p * a.c.cout + bco);
         }
     };
     const int wn = wave % (BN / 32), wm = wave / (BN / 32);
@@ -651,19 +666,23 @@ __global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
     if (co >= a.c.cout) return;
     float* out = a.partial + (size_t)blockIdx.y * a.krows * a.c.cout;
     for (int r = 0; r < 16; ++r) {
-        const int krow = kt * BM + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh2;
-        if (krow < a.krows) out[(size_t)krow * a.c.cout + co] = (float)sum[r];
+        int tap, ci;
+        const int krow = kpn_enc_wgrad_row(a.c, kt * BM + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh2, tap, ci);
+        if (krow >= 0) out[(size_t)krow * a.c.cout + co] = (float)sum[r];
     }
 }
-// the ranges of one dW element, added in range order in fp64 and rounded once; [k-row = tap * cin + ci][co] -> OIHW
+// the ranges of one dW element, added in range order in fp64 and rounded once; one thread per (GEMM K-row, co), the padded ones
+// idle; partial[range][tap * cin + ci][co] -> OIHW
 __global__ __launch_bounds__(256) void k_enc_wgrad_combine(kpn_enc_wgrad_args a) {
-    const int64_t total = (int64_t)a.krows * a.c.cout;
     const int taps = a.c.kh * a.c.kw;
+    const int64_t total = (int64_t)taps * a.c.cin_p * a.c.cout, real = (int64_t)a.krows * a.c.cout;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int co = (int)(i % a.c.cout), krow = (int)(i / a.c.cout);
-        const int tap = krow / a.c.cin, ci = krow - tap * a.c.cin;
+        const int co = (int)(i % a.c.cout);
+        int tap, ci;
+        const int krow = kpn_enc_wgrad_row(a.c, (int)(i / a.c.cout), tap, ci);
+        if (krow < 0) continue;
         double v = 0.0;
-        for (int r = 0; r < a.nranges; ++r) v += (double)a.partial[(size_t)r * total + i];
+        for (int r = 0; r < a.nranges; ++r) v += (double)a.partial[(size_t)r * real + (size_t)krow * a.c.cout + co];
         a.dw[((size_t)co * a.c.cin + ci) * taps + tap] = (float)v;
     }
 }

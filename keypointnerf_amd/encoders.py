@@ -20,13 +20,16 @@ stride-1 convolution) behind the eligible ``nn.Conv2d`` instances of a module tr
 ``install_native_norms`` does the same for ``nn.GroupNorm`` / ``nn.InstanceNorm2d`` (torch.ops.kpnerf.group_norm), and
 ``install_native_blocks`` rebinds whole ConvBlocks to ``group_norm(relu=True)`` + ``conv2d`` legs.  ``install_native_hourglass``
 rebinds a whole HourGlass to its own recursion with torch.ops.kpnerf.avg_pool2 and torch.ops.kpnerf.upsample2x_add between the
-blocks, whatever forward those have.  The four are independent: they rebind different modules, so they compose and uninstall in
-any order.
+blocks, whatever forward those have.  ``install_native_strided`` serves what ``install_native_convs`` leaves: the stride-2 3x3
+convolutions, the 7x7 stride-2 stem and the ConvTranspose2d layers (torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2).  The five
+are independent: they rebind different modules, so they compose and uninstall in any order.  ``install_native_geo`` applies all
+five to every HGFilterV2 and rebinds its forward so that the functional calls in it run on the project's kernels too.
 """
 import types
 
 import torch
 
+from . import lib as kl
 from . import ops
 from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
 from .dropin import _version_key
@@ -401,11 +404,13 @@ def uninstall_native_convs(module):
 
 # ---- training normalisations natively: torch.ops.kpnerf.group_norm behind nn.GroupNorm / nn.InstanceNorm2d ----
 class NativeTraining:
-    """native forward calls served by the rebound norms, blocks and hourglasses of all modules (the tests assert that a call was served
+    """native forward calls served by the rebound norms, blocks, hourglasses, strided layers and HGFilterV2s of all modules (the tests assert that a call was served
     natively)"""
     norm_calls = 0
     block_calls = 0
     hourglass_calls = 0
+    strided_calls = 0
+    geo_calls = 0
 
 
 def _pow2_channels(C):
@@ -555,3 +560,178 @@ def install_native_hourglass(module):
 def uninstall_native_hourglass(module):
     """Restores what ``forward`` was on every HourGlass ``install_native_hourglass`` rebound."""
     return _restore_forward(module, "_kpnerf_hourglass_saved")
+
+
+# ---- the resolution-changing layers natively: torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2 ----
+def _strided_candidate(m):
+    """the layers install_native_strided answers for: every nn.ConvTranspose2d, and the nn.Conv2d that are not stride 1 (those are
+    install_native_convs')"""
+    return type(m) is torch.nn.ConvTranspose2d or (type(m) is torch.nn.Conv2d and _pair(m.stride) != (1, 1))
+
+
+def _strided_ineligible(m):
+    """None if kpn_conv2d_s2_* serves this layer, else the reason it is left on torch"""
+    k, s, p, d = _pair(m.kernel_size), _pair(m.stride), m.padding, _pair(m.dilation)
+    transposed = type(m) is torch.nn.ConvTranspose2d
+    if isinstance(p, str):
+        return f"padding={p!r}"
+    p = _pair(p)
+    if s != (2, 2):
+        return f"stride={s} (2)"
+    if d != (1, 1):
+        return f"dilation={d}"
+    if m.groups != 1:
+        return f"groups={m.groups}"
+    if m.padding_mode != "zeros":
+        return f"padding_mode={m.padding_mode!r}"
+    if k not in (((3, 3),) if transposed else ((3, 3), (7, 7))):
+        return f"kernel_size={k} ({'3' if transposed else '3 or 7'}, square)"
+    if p != (k[0] // 2, k[0] // 2):
+        return f"padding={p} ({k[0] // 2} for kernel_size {k[0]})"
+    if transposed and _pair(m.output_padding) != (1, 1):
+        return f"output_padding={_pair(m.output_padding)} (1)"
+    kind = kl.S2_DECONV3 if transposed else (kl.S2_STEM7 if k[0] == 7 else kl.S2_CONV3)
+    if not ops.conv2d_s2_supported(kind, m.in_channels, m.out_channels):
+        return (f"channels {m.in_channels} -> {m.out_channels} " +
+                ("(at most 4 input channels, output channels a multiple of 4)" if kind == kl.S2_STEM7 else "(multiples of 4, at most 1024)"))
+    return None
+
+
+def install_native_strided(module):
+    """Opt-in: rebinds ``forward`` on the resolution-changing layers under ``module`` to the project's kernels, forward and backward in
+    HIP (kpn_conv2d_s2_forward / kpn_conv2d_s2_backward): ``nn.Conv2d`` with stride 2 and (kernel_size, padding) = (3, 1) or (7, 3) -
+    torch.ops.kpnerf.conv2d_down2 - and ``nn.ConvTranspose2d`` with kernel_size 3, stride 2, padding 1, output_padding 1 -
+    torch.ops.kpnerf.conv_transpose2d_up2; groups = 1, dilation = 1, zero padding, channel counts that are multiples of 4 (the 7x7 stem:
+    at most 4 input channels).  It serves none of the layers ``install_native_convs`` serves, and lists every other strided or
+    transposed layer with its reason.  The rebound forward calls the module's own forward for input that is not a CUDA fp32
+    (N, C, H, W) tensor, for odd H or W in front of a 3x3 stride-2 convolution, and for a stem input that requires a gradient (the
+    stem has no native input gradient); its result is channels_last.  The module tree, the parameter names and the state_dict are
+    untouched.  Returns (served, left): the names served, and {name: reason} of the layers left alone."""
+    def make_forward(_prev):
+        def forward(self, x, *args, **kwargs):
+            if args or kwargs or not _native_input(x, self.weight, self.bias):
+                return _prev(x, *args, **kwargs)
+            if type(self) is torch.nn.ConvTranspose2d:
+                NativeTraining.strided_calls += 1
+                return torch.ops.kpnerf.conv_transpose2d_up2(x, self.weight, self.bias)
+            if _pair(self.kernel_size)[0] == 3 and (x.shape[2] % 2 or x.shape[3] % 2):
+                return _prev(x)
+            if _pair(self.kernel_size)[0] == 7 and x.requires_grad and torch.is_grad_enabled():
+                return _prev(x)
+            NativeTraining.strided_calls += 1
+            return torch.ops.kpnerf.conv2d_down2(x, self.weight, self.bias)
+        return forward
+
+    return _rebind_forward(module, "_kpnerf_strided_saved", _strided_candidate, lambda m, name: _strided_ineligible(m), make_forward)
+
+
+def uninstall_native_strided(module):
+    """Restores what ``forward`` was on every layer ``install_native_strided`` rebound."""
+    return _restore_forward(module, "_kpnerf_strided_saved")
+
+
+# ---- a whole HGFilterV2 natively: the five installers above on its subtree, and its own forward on the project's kernels ----
+def _geo_ineligible(m, name):
+    """None if this HGFilterV2 has the reference's structure (src/utils.py:322-414, norm = "group", any n_stack >= 1, hd either way)
+    and its fused norms and its pool are served, else the reason it is left alone"""
+    n_stack = getattr(m, "n_stack", None)
+    if not isinstance(n_stack, int) or isinstance(n_stack, bool) or n_stack < 1:
+        return f"n_stack={n_stack!r} (an integer >= 1)"
+    if not hasattr(m, "hd"):
+        return "no attribute hd"
+    want = {"nl": None, "unpack1": "DeconvReLUGroup", "conv_out": "Conv2d", "conv1": "Conv2d", "bn1": "GroupNorm", "conv2": "ConvBlock",
+            "conv3": "ConvBlock", "conv4": "ConvBlock"}
+    for i in range(n_stack):
+        want.update({f"m{i}": "HourGlass", f"top_m_{i}": "ConvBlock", f"conv_last{i}": "Conv2d", f"bn_end{i}": "GroupNorm", f"l{i}": "Conv2d"})
+        if i < n_stack - 1:
+            want.update({f"bl{i}": "Conv2d", f"al{i}": "Conv2d"})
+    have = dict(m.named_children())
+    if set(have) != set(want):
+        return f"children {sorted(set(have) ^ set(want))} missing or unexpected (an HGFilterV2 with n_stack={n_stack})"
+    for n, t in want.items():
+        if type(have[n]) is torch.nn.BatchNorm2d:
+            return f'{n}: norm="batch" (BatchNorm2d)'
+        if t is not None and type(have[n]).__name__ != t:
+            return f"{n}: {type(have[n]).__name__} where {t} is expected"
+    un = m.unpack1
+    if type(getattr(un, "conv", None)) is not torch.nn.ConvTranspose2d or type(getattr(un, "norm", None)) is not torch.nn.GroupNorm \
+            or not isinstance(getattr(un, "nl", None), torch.nn.ReLU):
+        return f"unpack1: {un} (ConvTranspose2d, ReLU, GroupNorm expected)"
+    if not isinstance(m.nl, torch.nn.ReLU):
+        return f"nl: {m.nl}"
+    for n in ["bn1", "unpack1.norm"] + [f"bn_end{i}" for i in range(n_stack)]:      # the norms the forward fuses with their ReLU
+        why = _norm_ineligible(m.get_submodule(n))
+        if why is not None:
+            return f"{n}: {why}"
+    if not m.hd and m.conv2.conv1.out_channels % 2:
+        return f"conv2: {2 * m.conv2.conv1.out_channels} channels in front of the pool (a multiple of 4)"
+    return None
+
+
+_GEO_PARTS = ("strided", "convs", "norms", "blocks", "hourglass")
+
+
+def install_native_geo(module):
+    """Opt-in: trains every HGFilterV2 under ``module`` (``module`` itself included) on the project's kernels.  An HGFilterV2 whose
+    structure is the reference's (src/utils.py:322-414: its children for any ``n_stack`` >= 1, ``norm="group"``, ``hd`` either way) gets
+    ``install_native_strided``, ``install_native_convs``, ``install_native_norms``, ``install_native_blocks`` and
+    ``install_native_hourglass`` on its subtree, and its ``forward`` is rebound to the same dataflow with
+    ``conv1 -> torch.ops.kpnerf.group_norm(bn1, relu=True)``, the transposed convolution of ``unpack1`` followed by the same fused norm,
+    torch.ops.kpnerf.avg_pool2 in place of ``avg_pool2d`` and ``group_norm(bn_end_i, relu=True)`` behind ``conv_last_i``: no
+    convolution, normalisation, pool, upsample or ReLU is left to torch; ``torch.cat`` and the residual / skip adds are.  Input that
+    is not a CUDA fp32 (N, C, H, W) tensor whose stem output has even H and W goes to the original forward.  The module tree, the
+    parameter names and the state_dict are untouched.  Returns {installer: (served, left)} for "geo" and the five installers, the
+    names relative to ``module``; a layer that one of the five leaves because it is another's (the stride-2 stem among the
+    nn.Conv2d) is not listed as left."""
+    def make_forward(_prev):
+        def forward(self, x):
+            if not _native_input(x, *self.parameters()) or (((x.shape[2] - 1) // 2 + 1) % 2 or ((x.shape[3] - 1) // 2 + 1) % 2):
+                return _prev(x)
+            NativeTraining.geo_calls += 1
+
+            def gn(norm, t):
+                return torch.ops.kpnerf.group_norm(t, norm.weight, norm.bias, norm.num_groups, norm.eps, True)
+
+            x = self.conv2(gn(self.bn1, self.conv1(x)))
+            x_hd = self.conv_out(gn(self.unpack1.norm, self.unpack1.conv(x)))
+            if not self.hd:
+                x = torch.ops.kpnerf.avg_pool2(x)
+            previous = self.conv4(self.conv3(x))
+            sub = self._modules
+            for i in range(self.n_stack):
+                ll = sub[f"top_m_{i}"](sub[f"m{i}"](previous))
+                ll = gn(sub[f"bn_end{i}"], sub[f"conv_last{i}"](ll))
+                out = sub[f"l{i}"](ll)
+                if i < self.n_stack - 1:
+                    previous = previous + sub[f"bl{i}"](ll) + sub[f"al{i}"](out)
+            return [out, x_hd]
+        return forward
+
+    uninstall_native_geo(module)
+    served, left = _rebind_forward(module, "_kpnerf_geo_saved", lambda m: type(m).__name__ == "HGFilterV2", _geo_ineligible, make_forward)
+    report = {k: ([], {}) for k in _GEO_PARTS}
+    subs = dict(module.named_modules())
+    for name in served:
+        for part, fn in zip(_GEO_PARTS, (install_native_strided, install_native_convs, install_native_norms, install_native_blocks,
+                                         install_native_hourglass)):
+            s_, l_ = fn(subs[name])
+            pre = name + "." if name else ""
+            report[part][0].extend(pre + n for n in s_)
+            report[part][1].update({pre + n: why for n, why in l_.items()})
+    everything = {n for part in _GEO_PARTS for n in report[part][0]}
+    for part in _GEO_PARTS:
+        for n in [n for n in report[part][1] if n in everything]:
+            del report[part][1][n]
+    report["geo"] = (served, left)
+    return report
+
+
+def uninstall_native_geo(module):
+    """Restores what ``forward`` was on every HGFilterV2 ``install_native_geo`` rebound, and undoes the five installers on its
+    subtree: no attribute it added is left."""
+    for m in module.modules():
+        if "_kpnerf_geo_saved" in m.__dict__:
+            for undo in (uninstall_native_strided, uninstall_native_convs, uninstall_native_norms, uninstall_native_blocks,
+                         uninstall_native_hourglass):
+                undo(m)
+    return _restore_forward(module, "_kpnerf_geo_saved")

@@ -1013,6 +1013,109 @@ def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want
 
 
 # ------------------------------------------------------------------------------------------------
+# The resolution-changing layers and their gradients (kpn_conv2d_s2_*): Conv2d(k 3, stride 2, pad 1), the stem Conv2d(k 7, stride 2,
+# pad 3) and ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1), reference src/utils.py:199-247, 322-414.  ``kind`` is one of
+# lib.S2_CONV3 / S2_STEM7 / S2_DECONV3.  Activations are channels_last tensors of logical shape (N, C, H, W); the stem's input alone
+# is a contiguous NCHW tensor, read as it is.
+_S2_WORKSPACE = ("kpn_conv2d_s2_workspace_bytes", "kpn_conv2d_s2_forward", "conv2d_s2: unsupported convolution")
+
+
+def _s2_desc(kind, N, H, W, cin, cout, has_bias):
+    d = kl.Conv2dS2Desc()
+    d.N, d.H, d.W, d.cin, d.cout, d.kind, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(kind), int(has_bias)
+    return d
+
+
+def _s2_channels(kind, weight_shape):
+    """(cin, cout) of a weight in the layer's own layout: OIHW, or (cin, cout, 3, 3) for the transposed layer"""
+    return (weight_shape[0], weight_shape[1]) if kind == kl.S2_DECONV3 else (weight_shape[1], weight_shape[0])
+
+
+def _s2_out_hw(kind, H, W):
+    return (2 * H, 2 * W) if kind == kl.S2_DECONV3 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+
+
+def _s2_input(kind, x, name, channels=None):
+    if kind != kl.S2_STEM7:
+        return _channels_last(x, name, channels)
+    x = _dev(x, name)
+    if x.dim() != 4 or not x.is_contiguous() or (channels is not None and x.shape[1] != channels):
+        raise ValueError(f"{name} must be a contiguous NCHW (N, {channels if channels is not None else 'C'}, H, W) tensor, got {tuple(x.shape)}")
+    return x
+
+
+def conv2d_s2_supported(kind, cin, cout):
+    """whether kpn_conv2d_s2_* serves a layer of this kind and these channel counts"""
+    return kl.get_library().kpn_conv2d_s2_packed_floats(ctypes.byref(_s2_desc(kind, 1, 2, 2, cin, cout, 0))) > 0
+
+
+def conv2d_s2_pack(weight, kind):
+    """The packed copies of a weight in the layer's own layout that conv2d_s2_forward (first) and the input gradient of
+    conv2d_s2_backward (second; the stem has none) read (kpn_conv2d_s2_pack_device)."""
+    L = kl.get_library()
+    w = _conv_weight(weight.detach())
+    if w.shape[2] != (7 if kind == kl.S2_STEM7 else 3):
+        raise ValueError(f"conv2d_s2: a weight {tuple(w.shape)} does not belong to kind {kind}")
+    cin, cout = _s2_channels(kind, w.shape)
+    d = _s2_desc(kind, 1, 2, 2, cin, cout, 0)
+    n = _desc_size(L, d, "kpn_conv2d_s2_packed_floats", "kpn_conv2d_s2_pack_device", f"conv2d_s2: unsupported weight {tuple(w.shape)}")
+    packed = torch.empty(n, dtype=_f32, device=w.device)
+    L.check(L.kpn_conv2d_s2_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
+    return packed
+
+
+def conv2d_s2_forward(x, packed, bias, cout, kind):
+    """The layer's forward for packed = conv2d_s2_pack(w, kind) (kpn_conv2d_s2_forward).  x: (N, cin, H, W) channels_last, or
+    contiguous NCHW for the stem; returns (N, cout, Ho, Wo) channels_last."""
+    L = kl.get_library()
+    x = _s2_input(kind, x, "x")
+    N, cin, H, W = x.shape
+    d = _s2_desc(kind, N, H, W, cin, cout, bias is not None)
+    ws, nb = _desc_workspace(L, d, x.device, *_S2_WORKSPACE)
+    if packed.numel() != L.kpn_conv2d_s2_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError("packed does not belong to this convolution (conv2d_s2_pack)")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    if b is not None and tuple(b.shape) != (cout,):
+        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
+    Ho, Wo = _s2_out_hw(kind, H, W)
+    y = torch.empty(N, Ho, Wo, cout, dtype=_f32, device=x.device)
+    L.check(L.kpn_conv2d_s2_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
+    return y.permute(0, 3, 1, 2)
+
+
+def conv2d_s2_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, want_dw=True, want_db=True):
+    """(dx, dw, db) of conv2d_s2_forward for the output gradient dy (N, cout, Ho, Wo) channels_last (kpn_conv2d_s2_backward); a
+    gradient that is not wanted is None and its leg is not launched.  x (of shape x_shape, in the forward's layout) is read for dw
+    only and packed for dx only: either may be None when its leg is off.  dx is channels_last, dw has the weight's own layout.  The
+    stem has no input gradient."""
+    L = kl.get_library()
+    dy = _channels_last(dy, "dy")
+    N, cin, H, W = (int(v) for v in x_shape)
+    cout = dy.shape[1]
+    if want_dx and kind == kl.S2_STEM7:
+        raise ValueError("conv2d_s2: the stem has no input gradient")
+    if tuple(dy.shape) != (N, cout) + _s2_out_hw(kind, H, W):
+        raise ValueError(f"dy must be {(N, cout) + _s2_out_hw(kind, H, W)}, got {tuple(dy.shape)}")
+    want_db = bool(want_db and has_bias)
+    d = _s2_desc(kind, N, H, W, cin, cout, has_bias)
+    ws, nb = _desc_workspace(L, d, dy.device, *_S2_WORKSPACE)
+    if want_dw:
+        x = _s2_input(kind, x, "x", cin)
+        if tuple(x.shape) != (N, cin, H, W):
+            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
+    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_s2_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
+        raise ValueError("packed does not belong to this convolution (conv2d_s2_pack)")
+    k = 7 if kind == kl.S2_STEM7 else 3
+    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
+    dw = torch.empty((cin, cout, k, k) if kind == kl.S2_DECONV3 else (cout, cin, k, k), dtype=_f32, device=dy.device) if want_dw else None
+    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
+    if want_dx or want_dw or want_db:
+        L.check(L.kpn_conv2d_s2_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
+                                         _p(db), _p(ws), nb, _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+
+
+# ------------------------------------------------------------------------------------------------
 # GroupNorm / InstanceNorm2d [+ ReLU] and its gradients (kpn_group_norm_*; torch.nn.functional.group_norm [+ relu] and their autograd,
 # reference src/utils.py:416-474, 199-247).  Activations are channels_last tensors of logical shape (N, C, H, W).
 def _norm_desc(N, H, W, C, groups, affine, relu, eps):

@@ -33,6 +33,10 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
 
     torch.ops.kpnerf.conv2d(x, weight, bias?, padding) -> y   one stride-1 convolution (k in {1, 3, 5}, zero padding, channels multiples
                                  of 4), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_conv2d_forward / _backward)
+    torch.ops.kpnerf.conv2d_down2(x, weight, bias?) -> y   Conv2d(k 3, stride 2, pad 1) or, for a 7x7 weight, the stem Conv2d(k 7,
+                                 stride 2, pad 3) on an NCHW tensor; DIFFERENTIABLE (the stem w.r.t. weight and bias only)
+    torch.ops.kpnerf.conv_transpose2d_up2(x, weight, bias?) -> y   ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1),
+                                 DIFFERENTIABLE w.r.t. x, weight and bias (kpn_conv2d_s2_forward / _backward)
     torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
                                  4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
                                  _backward); y is not kept for the backward and may be overwritten in place
@@ -537,10 +541,12 @@ def conv2d_cache_clear():
         _ConvPackCache.entries.clear()
 
 
-def _conv_packed(weight):
+def _conv_packed(weight, kind=None):
+    """the packed copies of a weight: of the stride-1 layer (kind None) or of one of the kpn_conv2d_s2_* kinds"""
+    pack = ops.conv2d_pack if kind is None else (lambda w: ops.conv2d_s2_pack(w, kind))
     if weight.is_inference():
-        return ops.conv2d_pack(weight)
-    key = _tensor_key(weight)
+        return pack(weight)
+    key = _tensor_key(weight) + (kind,)
     C = _ConvPackCache
     with C.lock:
         e = C.entries.get(key[0])
@@ -548,7 +554,7 @@ def _conv_packed(weight):
             C.entries.move_to_end(key[0])
             C.hits += 1
             return e[2]
-    packed = ops.conv2d_pack(weight)
+    packed = pack(weight)
     with C.lock:
         C.misses += 1
         C.entries[key[0]] = (key, weight, packed)
@@ -623,6 +629,113 @@ def _conv2d(x, weight, bias, padding):
 
 _fragment.define("conv2d(Tensor x, Tensor weight, Tensor? bias, int padding) -> Tensor")
 _fragment.impl("conv2d", _conv2d, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2: the resolution-changing layers, DIFFERENTIABLE ----
+# Conv2d(k 3, stride 2, pad 1) and the stem Conv2d(k 7, stride 2, pad 3) share one operator, the kind following the weight's kernel
+# size; ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1) has its own.  One backward operator serves the three kinds
+# (kpn_conv2d_s2_backward).  The packed copies live in the cache of kpnerf::conv2d, keyed by weight and kind.  The stem reads a
+# contiguous NCHW tensor as it is and has no input gradient: it raises on an x that requires one.
+def _down2_kind(weight):
+    k = weight.shape[-1]
+    if k not in (3, 7):
+        raise ValueError(f"conv2d_down2: kernel size {k} (3: stride 2, padding 1; 7: the stem, stride 2, padding 3)")
+    return kl.S2_STEM7 if k == 7 else kl.S2_CONV3
+
+
+@_lib.custom_op("kpnerf::conv2d_down2_cl", mutates_args=(), device_types="cuda")
+def conv2d_down2_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """conv2d(x, weight, bias, stride=2, padding=k // 2) for weight (cout, cin, k, k), k = 3 (x channels_last, H and W even, cin and
+    cout multiples of 4) or k = 7 (x contiguous NCHW, cin <= 4) (kpn_conv2d_s2_forward): what torch.ops.kpnerf.conv2d_down2 runs
+    after its memory-format conversion.  Returns (N, cout, Ho, Wo) channels_last."""
+    kind = _down2_kind(weight)
+    return ops.conv2d_s2_forward(x, _conv_packed(weight, kind), bias, weight.shape[0], kind)
+
+
+@conv2d_down2_cl.register_fake
+def _(x, weight, bias):
+    N, _, H, W = x.shape
+    return x.new_empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, weight.shape[0]).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::conv_transpose2d_up2_cl", mutates_args=(), device_types="cuda")
+def conv_transpose2d_up2_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """conv_transpose2d(x, weight, bias, stride=2, padding=1, output_padding=1) for a channels_last x and weight (cin, cout, 3, 3), cin
+    and cout multiples of 4 (kpn_conv2d_s2_forward): what torch.ops.kpnerf.conv_transpose2d_up2 runs after its memory-format
+    conversion.  Returns (N, cout, 2H, 2W) channels_last."""
+    if weight.shape[-1] != 3:
+        raise ValueError(f"conv_transpose2d_up2: kernel size {weight.shape[-1]} (3 only)")
+    return ops.conv2d_s2_forward(x, _conv_packed(weight, kl.S2_DECONV3), bias, weight.shape[1], kl.S2_DECONV3)
+
+
+@conv_transpose2d_up2_cl.register_fake
+def _(x, weight, bias):
+    N, _, H, W = x.shape
+    return x.new_empty(N, 2 * H, 2 * W, weight.shape[1]).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::conv2d_s2_backward", mutates_args=(), device_types="cuda")
+def conv2d_s2_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, kind: int, has_bias: bool,
+                       mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of kpnerf::conv2d_down2_cl / conv_transpose2d_up2_cl for the output gradient dy (kpn_conv2d_s2_backward);
+    kind is the KPN_S2_* value; mask = [dx, dweight, dbias] wanted: a leg that is not wanted is not launched and its result is an
+    empty tensor."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = ops.conv2d_s2_backward(x, dy, _conv_packed(weight, kind) if mask[0] else None, x.shape, kind, has_bias,
+                                        want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    return _empty_for_none(dy, dx, dw, db)
+
+
+@conv2d_s2_backward.register_fake
+def _(x, weight, dy, kind, has_bias, mask):
+    e = x.new_empty(0)
+    cout = weight.shape[1 if kind == kl.S2_DECONV3 else 0]
+    return (torch.empty_like(x, memory_format=torch.channels_last) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
+            x.new_empty(cout) if mask[2] and has_bias else e)
+
+
+def _s2_setup(kind_of):
+    def setup(ctx, inputs, output):
+        x, weight, bias = inputs
+        ctx.kind, ctx.has_bias = kind_of(weight), bias is not None
+        if ctx.kind == kl.S2_STEM7 and ctx.needs_input_grad[0]:
+            raise RuntimeError("kpnerf::conv2d_down2: the 7x7 stem has no input gradient (x.requires_grad is set)")
+        ctx.save_for_backward(x, weight)
+        ctx.set_materialize_grads(False)
+    return setup
+
+
+def _s2_bwd(ctx, dy):
+    if dy is None:
+        return None, None, None
+    x, weight = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
+    if not any(mask):
+        return None, None, None
+    dx, dw, db = torch.ops.kpnerf.conv2d_s2_backward(x, weight, dy, ctx.kind, ctx.has_bias, mask)
+    return _none_unless(mask, dx, dw, db)
+
+
+conv2d_down2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(_down2_kind))
+conv_transpose2d_up2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(lambda w: kl.S2_DECONV3))
+
+
+# torch.ops.kpnerf.conv2d_down2(x, weight, bias) / conv_transpose2d_up2(x, weight, bias): x in any memory format, converted once (as
+# kpnerf::conv2d does) - to channels_last, or to contiguous NCHW for the stem, which reads that layout as it is.
+def _conv2d_down2(x, weight, bias):
+    stem = _down2_kind(weight) == kl.S2_STEM7
+    return torch.ops.kpnerf.conv2d_down2_cl(x.contiguous() if stem else x.contiguous(memory_format=torch.channels_last), weight, bias)
+
+
+def _conv_transpose2d_up2(x, weight, bias):
+    return torch.ops.kpnerf.conv_transpose2d_up2_cl(x.contiguous(memory_format=torch.channels_last), weight, bias)
+
+
+_fragment.define("conv2d_down2(Tensor x, Tensor weight, Tensor? bias) -> Tensor")
+_fragment.impl("conv2d_down2", _conv2d_down2, "CompositeImplicitAutograd")
+_fragment.define("conv_transpose2d_up2(Tensor x, Tensor weight, Tensor? bias) -> Tensor")
+_fragment.impl("conv_transpose2d_up2", _conv_transpose2d_up2, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.group_norm: GroupNorm / InstanceNorm2d [+ ReLU], DIFFERENTIABLE w.r.t. x, weight and bias ----
