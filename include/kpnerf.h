@@ -49,6 +49,9 @@ extern "C" {
 /* still 10: the stride-2, stem and transposed convolutions with their gradients (kpn_conv2d_s2_desc, kpn_conv2d_s2_packed_floats,
  * kpn_conv2d_s2_pack_device, kpn_conv2d_s2_workspace_bytes, kpn_conv2d_s2_wgrad_ranges, kpn_conv2d_s2_forward, kpn_conv2d_s2_backward)
  * are additive within 10: nothing that a caller built against 10 uses changed, kpn_conv2d_* and its refusals included */
+/* still 10: the replication-padded stride-1 convolutions with their gradients (kpn_conv2d_rp_desc, kpn_conv2d_rp_packed_floats,
+ * kpn_conv2d_rp_pack_device, kpn_conv2d_rp_workspace_bytes, kpn_conv2d_rp_wgrad_ranges, kpn_conv2d_rp_forward, kpn_conv2d_rp_backward)
+ * are additive within 10 in the same way */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -669,6 +672,44 @@ int32_t kpn_conv2d_s2_wgrad_ranges(const kpn_conv2d_s2_desc* desc);
 int kpn_conv2d_s2_forward(const kpn_conv2d_s2_desc* desc, const float* x, const float* packed, const float* bias, float* y,
                           void* workspace, size_t workspace_bytes, void* stream);
 int kpn_conv2d_s2_backward(const kpn_conv2d_s2_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
+                           float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The replication-padded convolutions of the texture encoder, forward and backward: ReplicationPad2d(k / 2) + Conv2d(k, stride 1) as
+ * ResBlkEncoder and ResBlk hold them (src/utils.py:199-259) - the 7x7 stem, the two 3x3 convolutions of every ResBlk, the 7x7 output
+ * layer.  groups = 1, dilation = 1, optional bias, fp32; the output grid is the input grid, and any H, W >= 1 is served, sizes below
+ * the pad included.  The padded tensor never exists: the loads clamp the source coordinate.  Activations are NHWC (torch channels_last)
+ * except the stem's input, which is NCHW and read as it is.  Kernels: csrc/encoder_kernels.hip, the encoders' own.
+ *   y[o] = sum_tap sum_ci w[co][ci][tap] x[clamp(o + tap - p)] + bias           k_enc_conv with the clamped load, split K as there
+ *   dx[(y, x)][ci] = sum_(ky, kx) sum_co w[co][ci][ky][kx] sum_{oy in Ry(y, ky)} sum_{ox in Rx(x, kx)} dy[(oy, ox)][co]
+ *        Ry(y, ky) = { oy in [0, H) : clamp(oy + ky - p, 0, H - 1) = y }: the one position y - ky + p for 0 < y < H - 1,
+ *        [0, min(H - 1, p - ky)] for y = 0, [max(0, H - 1 - ky + p), H - 1] for y = H - 1 (their union when H = 1); Rx alike.
+ *        The same GEMM as the zero-padded input gradient over the flipped copy of the weight; its A entry is the sum of dy over that
+ *        rectangle (at most (p + 1)^2 values, on the outermost ring of pixels only), added oy outer, ox inner: a gather - no scratch
+ *        copy of a padded gradient, no scatter, no atomics
+ *   dw: the weight gradient of kpn_conv2d_backward with im2col rows through the clamped load (the stem: K rows tap * 4 + ci over
+ *        the NCHW tensor, the padded channel never loaded and never stored); the ranges follow the rule of kpn_conv2d_wgrad_ranges over
+ *        K rows k k cin_p (cin_p = cin rounded up to 4), cout and the N H W pixels
+ *   db[co] = sum over the pixels of dy, as kpn_conv2d_backward.
+ * No float atomics: bit-identical from run to run.
+ * kpn_conv2d_rp_packed_floats / _pack_device read only kind, cin, cout: `packed` (device, 16-byte aligned) holds the forward copy,
+ * then (not for the stem) the input-gradient copy.  `workspace` (kpn_conv2d_rp_workspace_bytes, 16-byte aligned; 0 = unsupported
+ * descriptor) serves the forward and the backward alike.  bias: NULL exactly when has_bias = 0.
+ * kpn_conv2d_rp_backward: each of dx, dw, db may be NULL - that leg is not launched and nothing is written for it; dw (OIHW) and db
+ * are overwritten, not accumulated.  packed is read for dx only, x for dw only.  A refused call (KPN_EINVAL; kpn_last_error() names
+ * the field) launches nothing. */
+enum { KPN_RP_CONV3 = 0,    /* ReplicationPad2d(1) + Conv2d(k=3); NHWC x; cin, cout multiples of 4 in 4..1024 */
+       KPN_RP_CONV7 = 1,    /* ReplicationPad2d(3) + Conv2d(k=7); NHWC x; the same channel rule */
+       KPN_RP_STEM7 = 2 };  /* ReplicationPad2d(3) + Conv2d(k=7); x is NCHW (N, cin, H, W), 1 <= cin <= 4; cout a multiple of 4 in
+                               4..1024; no input gradient (dx must be NULL) */
+typedef struct kpn_conv2d_rp_desc { int32_t N, H, W, cin, cout, kind, has_bias; } kpn_conv2d_rp_desc;
+size_t kpn_conv2d_rp_packed_floats(const kpn_conv2d_rp_desc* desc);
+int kpn_conv2d_rp_pack_device(const kpn_conv2d_rp_desc* desc, const float* w_oihw, float* packed, void* stream);
+size_t kpn_conv2d_rp_workspace_bytes(const kpn_conv2d_rp_desc* desc);
+int32_t kpn_conv2d_rp_wgrad_ranges(const kpn_conv2d_rp_desc* desc);
+int kpn_conv2d_rp_forward(const kpn_conv2d_rp_desc* desc, const float* x, const float* packed, const float* bias, float* y,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv2d_rp_backward(const kpn_conv2d_rp_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
                            float* db, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

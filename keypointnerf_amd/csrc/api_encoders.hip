@@ -63,6 +63,15 @@ inline void launch_conv(const kpn_enc_conv_args& a, const ConvGeom& g, int stem,
     }
     if (a.ksplit > 1) KPN_LAUNCH(k_enc_combine, grid4((int64_t)g.ncls * g.M * a.cout), dim3(256), stream, a, g.deconv);
 }
+// the input gradient of a replication-padded stride-1 convolution (api_reppad.hip): the same GEMM, tiles, split K and combine, with
+// the adjoint of the clamped load in place of the load.  `a`: g.a of conv_geom(N, H, W, layer cout, layer cin, k, k, 0) with src = dy,
+// (Hs, Ws) = (H, W), pad = k / 2 and the tflip copy of the weight
+inline void launch_conv_rp_adjoint(const kpn_enc_conv_args& a, const ConvGeom& g, void* stream) {
+    const dim3 grid((unsigned)((g.M + g.bm - 1) / g.bm * (a.cout_p / g.bn)), (unsigned)a.ksplit, 1u);
+    if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, false, false, true>), grid, dim3(256), stream, a);
+    else KPN_LAUNCH((k_enc_conv<128, 32, false, false, true>), grid, dim3(256), stream, a);
+    if (a.ksplit > 1) KPN_LAUNCH(k_enc_combine, grid4(g.M * a.cout), dim3(256), stream, a, 0);
+}
 // plain OIHW (DECONV: IOHW) weight `w` -> the packed weight `wp`, every class.  tflip: the operand of the input gradient
 inline void launch_pack(const ConvGeom& g, int tflip, const float* w, float* wp, void* stream) {
     for (int c = 0; c < g.ncls; ++c) {

@@ -12,6 +12,8 @@
 //              scale * x + shift with optional ReLU (GroupNorm / InstanceNorm + ReLU in front of the convolution); the stems read
 //              the NCHW images, average 2 x 2 blocks when ds = 1 (the avg_pool2d of attach_*_feat; the host admits ds <= 1) and apply
 //              2 * im - 1 (stem_plain = 0, the walks) or nothing (stem_plain = 1, a module's own stem layer);
+//   RPADJ    : the input gradient of a replication-padded stride-1 convolution: the adjoint of the clamped load, the sum of dy over
+//              the positions that the clamp maps onto the pixel (kpn_enc_load_a_rp_adjoint) - a gather, no scatter;
 //   DECONV   : ConvTranspose2d(k = 3, stride = 2, padding = 1, output_padding = 1) as four gathers, one per output parity
 //              (py, px) with (1 + py) * (1 + px) valid taps each (blockIdx.z) — no scatter;
 //   epilogue : bias, residual add from a second tensor, ReLU, store into a channel slice of a wider NHWC tensor;
@@ -117,8 +119,44 @@ __device__ __forceinline__ kpn_f32x4 kpn_enc_load_a(const kpn_enc_conv_args& a, 
     return v;
 }
 
-template <int BM, int BN, bool STEM, bool DECONV>
+// The adjoint of the clamped load: the A entry of the input gradient of a replication-padded stride-1 convolution with an odd
+// kernel and pad = k / 2 (api_reppad.hip).  GEMM row (n, y, x) is an input pixel, K entry (tap', co) with tap' = (ky', kx') counted as
+// the flipped packed copy counts it (ky = kh - 1 - ky'), the source is dy on the same (Hs, Ws) grid.  The forward read
+// x[clamp(o + ky - pad)], so dx[y] collects every dy[oy] with clamp(oy + ky - pad, 0, Hs - 1) == y: for an interior y the one position
+// y + ky' - pad (the zero-padded gradient's), for y = 0 everything up to it, for y = Hs - 1 everything from it on - one contiguous range
+// per axis, at most pad + 1 long, and only on the outermost ring.  The rectangle is added oy outer, ox inner: a gather in a fixed order.
+__device__ __forceinline__ void kpn_enc_rp_range(int y, int base, int n, int& lo, int& hi) {
+    lo = y == 0 ? 0 : base;
+    hi = y == n - 1 ? n - 1 : base;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n - 1 ? n - 1 : hi;
+}
+__device__ __forceinline__ kpn_f32x4 kpn_enc_load_a_rp_adjoint(const kpn_enc_conv_args& a, bool valid, int n, int y, int x, int kk) {
+    kpn_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int tap = kk / a.cin_p, c = kk - tap * a.cin_p;
+    const int ky = tap / a.kw, kx = tap - ky * a.kw;
+    if (!valid || ky >= a.kh) return v;
+    int y0, y1, x0, x1;
+    kpn_enc_rp_range(y, y + ky - a.pad, a.Hs, y0, y1);
+    kpn_enc_rp_range(x, x + kx - a.pad, a.Ws, x0, x1);
+    if (y0 > y1 || x0 > x1) return v;
+    // the first value is loaded as the plain load loads it, with nothing consuming it before the next chunk's LDS store: an interior
+    // pixel, and a wavefront without a ring pixel, pays nothing for the mode.  Only a ring pixel with more values enters the loop, whose
+    // adds wait for their loads
+    v = *KPN_GLOBAL4(a.src + (((size_t)n * a.Hs + y0) * a.Ws + x0) * a.src_cs + c);
+    if (y1 > y0 || x1 > x0)
+        for (int sy = y0; sy <= y1; ++sy)
+            for (int sx = sy == y0 ? x0 + 1 : x0; sx <= x1; ++sx) {
+                const kpn_f32x4 d = *KPN_GLOBAL4(a.src + (((size_t)n * a.Hs + sy) * a.Ws + sx) * a.src_cs + c);
+                for (int e = 0; e < 4; ++e) v[e] = KADD(v[e], d[e]);
+            }
+    return v;
+}
+
+// RPADJ: the A loads are kpn_enc_load_a_rp_adjoint (STEM and DECONV off); everything else is the same GEMM
+template <int BM, int BN, bool STEM, bool DECONV, bool RPADJ = false>
 __global__ __launch_bounds__(256) void k_enc_conv(kpn_enc_conv_args a) {
+    static_assert(!RPADJ || (!STEM && !DECONV), "the adjoint load is a mode of the plain NHWC GEMM");
     static_assert((BM / 32) * (BN / 32) == 4, "four wavefronts, one 32 x 32 accumulator each");
     constexpr int NA = BM * 4 / 256;        // float4s of A per thread and K chunk
     constexpr int KQ = 256 / BM;            // K quarter step between the float4s of one thread
@@ -147,7 +185,10 @@ __global__ __launch_bounds__(256) void k_enc_conv(kpn_enc_conv_args a) {
     const int s0 = (int)((int64_t)ks * nk / a.ksplit), s1 = (int)((int64_t)(ks + 1) * nk / a.ksplit);
     kpn_f32x4 ra[NA], rb = {0.0f, 0.0f, 0.0f, 0.0f};
     auto load = [&](int s) {
-        for (int j = 0; j < NA; ++j) ra[j] = kpn_enc_load_a<STEM, DECONV>(a, cls, valid, n, oy, ox, s * 16 + (akq + j * KQ) * 4);
+        for (int j = 0; j < NA; ++j) {
+            if constexpr (RPADJ) ra[j] = kpn_enc_load_a_rp_adjoint(a, valid, n, oy, ox, s * 16 + (akq + j * KQ) * 4);
+            else ra[j] = kpn_enc_load_a<STEM, DECONV>(a, cls, valid, n, oy, ox, s * 16 + (akq + j * KQ) * 4);
+        }
         if (bload) rb = *KPN_GLOBAL4(wbase + (size_t)s * a.cout_p * 16);
     };
     const int wn = wave % (BN / 32), wm = wave / (BN / 32);

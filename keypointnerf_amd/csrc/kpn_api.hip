@@ -48,6 +48,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "api_encoders.hip"
 #include "api_conv.hip"
 #include "api_strided.hip"
+#include "api_reppad.hip"
 #include "api_norm.hip"
 #include "api_resample.hip"
 #include "api_params.hip"

@@ -24,6 +24,9 @@ blocks, whatever forward those have.  ``install_native_strided`` serves what ``i
 convolutions, the 7x7 stride-2 stem and the ConvTranspose2d layers (torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2).  The five
 are independent: they rebind different modules, so they compose and uninstall in any order.  ``install_native_geo`` applies all
 five to every HGFilterV2 and rebinds its forward so that the functional calls in it run on the project's kernels too.
+``install_native_tex`` does the same for every ResBlkEncoder: ``install_native_strided`` and ``install_native_norms`` on its subtree,
+and a forward that runs every ReplicationPad2d + Conv2d pair as torch.ops.kpnerf.conv2d_replicate and every InstanceNorm2d + ReLU
+pair as one fused torch.ops.kpnerf.group_norm.
 """
 import types
 
@@ -404,13 +407,14 @@ def uninstall_native_convs(module):
 
 # ---- training normalisations natively: torch.ops.kpnerf.group_norm behind nn.GroupNorm / nn.InstanceNorm2d ----
 class NativeTraining:
-    """native forward calls served by the rebound norms, blocks, hourglasses, strided layers and HGFilterV2s of all modules (the tests assert that a call was served
+    """native forward calls served by the rebound norms, blocks, hourglasses, strided layers, HGFilterV2s and ResBlkEncoders of all modules (the tests assert that a call was served
     natively)"""
     norm_calls = 0
     block_calls = 0
     hourglass_calls = 0
     strided_calls = 0
     geo_calls = 0
+    tex_calls = 0
 
 
 def _pow2_channels(C):
@@ -735,3 +739,107 @@ def uninstall_native_geo(module):
                          uninstall_native_hourglass):
                 undo(m)
     return _restore_forward(module, "_kpnerf_geo_saved")
+
+
+# ---- a whole ResBlkEncoder natively: the replication-padded convolutions, the fused norms and the two installers its other layers need ----
+def _tex_ineligible(m, name):
+    """None if this ResBlkEncoder has the reference's structure (src/utils.py:199-259, norm = "instance": the check the native encoder
+    makes) and every one of its layers is served by its kernel, else the reason it is left alone"""
+    L = list(getattr(m, "layers", ()))
+    if len(L) < 2 or type(L[-1]) is not torch.nn.Conv2d or type(L[-2]) is not torch.nn.ReplicationPad2d:
+        return (f"layers.{len(L) - 1}: {type(L[-1]).__name__ if L else 'nothing'} where the output layer ReplicationPad2d(3) + Conv2d(k 7) "
+                "is expected (n_upsample=0)")
+    try:
+        tex_params(m)
+    except NotImplementedError as e:
+        return str(e)
+    for n, sub in m.named_modules():
+        if type(sub) is torch.nn.InstanceNorm2d:
+            why = _norm_ineligible(sub)
+        elif _strided_candidate(sub):
+            why = _strided_ineligible(sub)
+        elif type(sub) is torch.nn.Conv2d:          # behind a ReplicationPad2d: tex_params has checked that
+            kind = ops.conv2d_rp_kind(sub.weight.shape)
+            why = None
+            if sub is L[-1] and kind == kl.RP_STEM7:
+                why = f"{sub.in_channels} input channels (conv2d_replicate reads a 7x7 weight with at most 4 as the stem; more than 4)"
+            elif kind != kl.RP_STEM7 and sub.out_channels % 4:
+                why = f"out_ch {sub.out_channels} (a multiple of 4)" if sub is L[-1] else f"channels {sub.out_channels} (a multiple of 4)"
+            elif not ops.conv2d_rp_supported(kind, sub.in_channels, sub.out_channels):
+                why = f"channels {sub.in_channels} -> {sub.out_channels} (multiples of 4, at most 1024)"
+        else:
+            continue
+        if why is not None:
+            return f"{n}: {why}"
+    return None
+
+
+_TEX_PARTS = ("strided", "norms")
+
+
+def install_native_tex(module):
+    """Opt-in: trains every ResBlkEncoder under ``module`` (``module`` itself included) on the project's kernels.  A ResBlkEncoder whose
+    structure is the reference's (src/utils.py:199-259 with ``norm="instance"`` and ``n_upsample`` >= 1: the check of ``tex_params``),
+    whose norms have a power of two in 4 .. 1024 channels, whose ``out_ch`` is a multiple of 4 and whose convolutions their kernels
+    serve gets ``install_native_strided`` and ``install_native_norms`` on its subtree, and its ``forward`` is rebound to the same walk
+    of ``layers``: every ReplicationPad2d + Conv2d pair is torch.ops.kpnerf.conv2d_replicate, every InstanceNorm2d + ReLU pair
+    torch.ops.kpnerf.group_norm(relu=True), a ResBlk ``x + group_norm(conv2d_replicate(...), relu=False)`` with the add on torch, and
+    the stride-2 and transposed layers run through their rebound modules: no convolution, pad, normalisation or ReLU is left to torch.
+    Input that is not a CUDA fp32 (N, 3, H, W) tensor with H and W divisible by 2^n_downsample, or that requires a gradient (the stem
+    has no native input gradient), goes to the original forward.  An encoder that fails a check is left alone with its reason, not
+    refused.  The module tree, the parameter names and the state_dict are untouched.  Returns {"tex": (served, left), "strided": ...,
+    "norms": ...}, the names relative to ``module``."""
+    def make_forward(_prev):
+        def forward(self, x):
+            nn = torch.nn
+            L = list(self.layers)
+            f = 1 << sum(type(m) is nn.Conv2d and _pair(m.stride) == (2, 2) for m in L)
+            if (not _native_input(x, *self.parameters()) or x.shape[1] != 3 or x.shape[2] % f or x.shape[3] % f
+                    or (x.requires_grad and torch.is_grad_enabled())):
+                return _prev(x)
+            NativeTraining.tex_calls += 1
+
+            def rp(t, conv):
+                return torch.ops.kpnerf.conv2d_replicate(t, conv.weight, conv.bias)
+
+            def inorm(t, norm, relu):
+                return torch.ops.kpnerf.group_norm(t, None, None, norm.num_features, norm.eps, relu)
+
+            i = 0
+            while i < len(L):
+                m = L[i]
+                if type(m) is nn.ReplicationPad2d:
+                    x, i = rp(x, L[i + 1]), i + 2
+                elif type(m) is nn.InstanceNorm2d:              # tex_params has seen the ReLU behind it
+                    x, i = inorm(x, m, True), i + 2
+                elif type(m).__name__ == "ResBlk":
+                    b = m.layers
+                    t = inorm(rp(x, b[1]), b[2], True)
+                    x, i = x + inorm(rp(t, b[5]), b[6], False), i + 1
+                else:                                           # a stride-2 or transposed convolution, rebound
+                    x, i = m(x), i + 1
+            return x
+        return forward
+
+    uninstall_native_tex(module)
+    served, left = _rebind_forward(module, "_kpnerf_tex_saved", lambda m: type(m).__name__ == "ResBlkEncoder", _tex_ineligible, make_forward)
+    report = {k: ([], {}) for k in _TEX_PARTS}
+    subs = dict(module.named_modules())
+    for name in served:
+        for part, fn in zip(_TEX_PARTS, (install_native_strided, install_native_norms)):
+            s_, l_ = fn(subs[name])
+            pre = name + "." if name else ""
+            report[part][0].extend(pre + n for n in s_)
+            report[part][1].update({pre + n: why for n, why in l_.items()})
+    report["tex"] = (served, left)
+    return report
+
+
+def uninstall_native_tex(module):
+    """Restores what ``forward`` was on every ResBlkEncoder ``install_native_tex`` rebound, and undoes the two installers on its
+    subtree: no attribute it added is left."""
+    for m in module.modules():
+        if "_kpnerf_tex_saved" in m.__dict__:
+            for undo in (uninstall_native_strided, uninstall_native_norms):
+                undo(m)
+    return _restore_forward(module, "_kpnerf_tex_saved")

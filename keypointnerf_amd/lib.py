@@ -94,6 +94,14 @@ class Conv2dS2Desc(ctypes.Structure):
 S2_CONV3, S2_STEM7, S2_DECONV3 = 0, 1, 2      # KPN_S2_*
 
 
+class Conv2dRpDesc(ctypes.Structure):
+    """struct kpn_conv2d_rp_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "cin", "cout", "kind", "has_bias")]
+
+
+RP_CONV3, RP_CONV7, RP_STEM7 = 0, 1, 2        # KPN_RP_*
+
+
 class GroupNormDesc(ctypes.Structure):
     """struct kpn_group_norm_desc"""
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "C", "G", "affine", "relu")] + [("eps", c_f)]
@@ -212,6 +220,12 @@ _SIGNATURES = {
     "kpn_conv2d_s2_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dS2Desc)]),
     "kpn_conv2d_s2_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dS2Desc), c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv2d_s2_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dS2Desc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv2d_rp_packed_floats": (c_sz, [ctypes.POINTER(Conv2dRpDesc)]),
+    "kpn_conv2d_rp_pack_device": (ctypes.c_int, [ctypes.POINTER(Conv2dRpDesc), c_p, c_p, c_p]),
+    "kpn_conv2d_rp_workspace_bytes": (c_sz, [ctypes.POINTER(Conv2dRpDesc)]),
+    "kpn_conv2d_rp_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dRpDesc)]),
+    "kpn_conv2d_rp_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dRpDesc), c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv2d_rp_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dRpDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_group_norm_stats_floats": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
     "kpn_group_norm_workspace_bytes": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
     "kpn_group_norm_forward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),

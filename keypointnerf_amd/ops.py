@@ -1116,6 +1116,100 @@ def conv2d_s2_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, wan
 
 
 # ------------------------------------------------------------------------------------------------
+# The replication-padded stride-1 convolutions and their gradients (kpn_conv2d_rp_*): ReplicationPad2d(k // 2) + Conv2d(k) for k = 3,
+# k = 7 and the 7x7 stem, reference src/utils.py:199-259.  ``kind`` is one of lib.RP_CONV3 / RP_CONV7 / RP_STEM7.  Activations are
+# channels_last tensors of logical shape (N, C, H, W); the stem's input alone is a contiguous NCHW tensor, read as it is.  The output
+# has the input's size.
+_RP_WORKSPACE = ("kpn_conv2d_rp_workspace_bytes", "kpn_conv2d_rp_forward", "conv2d_rp: unsupported convolution")
+
+
+def _rp_desc(kind, N, H, W, cin, cout, has_bias):
+    d = kl.Conv2dRpDesc()
+    d.N, d.H, d.W, d.cin, d.cout, d.kind, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(kind), int(has_bias)
+    return d
+
+
+def _rp_input(kind, x, name, channels=None):
+    return _s2_input(kl.S2_STEM7 if kind == kl.RP_STEM7 else kl.S2_CONV3, x, name, channels)
+
+
+def conv2d_rp_kind(weight_shape):
+    """the kind a (cout, cin, k, k) weight belongs to: k = 3, k = 7, or the stem (k = 7 with at most 4 input channels)"""
+    k = weight_shape[-1]
+    if len(weight_shape) != 4 or k not in (3, 7) or weight_shape[-2] != k:
+        raise ValueError(f"conv2d_rp: a weight {tuple(weight_shape)} (3x3 under ReplicationPad2d(1) or 7x7 under ReplicationPad2d(3))")
+    return kl.RP_CONV3 if k == 3 else (kl.RP_STEM7 if weight_shape[1] <= 4 else kl.RP_CONV7)
+
+
+def conv2d_rp_supported(kind, cin, cout):
+    """whether kpn_conv2d_rp_* serves a layer of this kind and these channel counts"""
+    return kl.get_library().kpn_conv2d_rp_packed_floats(ctypes.byref(_rp_desc(kind, 1, 1, 1, cin, cout, 0))) > 0
+
+
+def conv2d_rp_pack(weight, kind):
+    """The packed copies of an OIHW weight that conv2d_rp_forward (first) and the input gradient of conv2d_rp_backward (second:
+    transposed and flipped; the stem has none) read (kpn_conv2d_rp_pack_device)."""
+    L = kl.get_library()
+    w = _conv_weight(weight.detach())
+    if w.shape[2] != (3 if kind == kl.RP_CONV3 else 7):
+        raise ValueError(f"conv2d_rp: a weight {tuple(w.shape)} does not belong to kind {kind}")
+    d = _rp_desc(kind, 1, 1, 1, w.shape[1], w.shape[0], 0)
+    n = _desc_size(L, d, "kpn_conv2d_rp_packed_floats", "kpn_conv2d_rp_pack_device", f"conv2d_rp: unsupported weight {tuple(w.shape)}")
+    packed = torch.empty(n, dtype=_f32, device=w.device)
+    L.check(L.kpn_conv2d_rp_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
+    return packed
+
+
+def conv2d_rp_forward(x, packed, bias, cout, kind):
+    """The layer's forward for packed = conv2d_rp_pack(w, kind) (kpn_conv2d_rp_forward).  x: (N, cin, H, W) channels_last, or
+    contiguous NCHW for the stem; returns (N, cout, H, W) channels_last."""
+    L = kl.get_library()
+    x = _rp_input(kind, x, "x")
+    N, cin, H, W = x.shape
+    d = _rp_desc(kind, N, H, W, cin, cout, bias is not None)
+    ws, nb = _desc_workspace(L, d, x.device, *_RP_WORKSPACE)
+    if packed.numel() != L.kpn_conv2d_rp_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError("packed does not belong to this convolution (conv2d_rp_pack)")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    if b is not None and tuple(b.shape) != (cout,):
+        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
+    y = torch.empty(N, H, W, cout, dtype=_f32, device=x.device)
+    L.check(L.kpn_conv2d_rp_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
+    return y.permute(0, 3, 1, 2)
+
+
+def conv2d_rp_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, want_dw=True, want_db=True):
+    """(dx, dw, db) of conv2d_rp_forward for the output gradient dy (N, cout, H, W) channels_last (kpn_conv2d_rp_backward); a gradient
+    that is not wanted is None and its leg is not launched.  x (of shape x_shape, in the forward's layout) is read for dw only and
+    packed for dx only: either may be None when its leg is off.  dx is channels_last, dw OIHW.  The stem has no input gradient."""
+    L = kl.get_library()
+    dy = _channels_last(dy, "dy")
+    N, cin, H, W = (int(v) for v in x_shape)
+    cout = dy.shape[1]
+    if want_dx and kind == kl.RP_STEM7:
+        raise ValueError("conv2d_rp: the stem has no input gradient")
+    if tuple(dy.shape) != (N, cout, H, W):
+        raise ValueError(f"dy must be {(N, cout, H, W)}, got {tuple(dy.shape)}")
+    want_db = bool(want_db and has_bias)
+    d = _rp_desc(kind, N, H, W, cin, cout, has_bias)
+    ws, nb = _desc_workspace(L, d, dy.device, *_RP_WORKSPACE)
+    if want_dw:
+        x = _rp_input(kind, x, "x", cin)
+        if tuple(x.shape) != (N, cin, H, W):
+            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
+    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_rp_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
+        raise ValueError("packed does not belong to this convolution (conv2d_rp_pack)")
+    k = 3 if kind == kl.RP_CONV3 else 7
+    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
+    dw = torch.empty(cout, cin, k, k, dtype=_f32, device=dy.device) if want_dw else None
+    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
+    if want_dx or want_dw or want_db:
+        L.check(L.kpn_conv2d_rp_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
+                                         _p(db), _p(ws), nb, _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+
+
+# ------------------------------------------------------------------------------------------------
 # GroupNorm / InstanceNorm2d [+ ReLU] and its gradients (kpn_group_norm_*; torch.nn.functional.group_norm [+ relu] and their autograd,
 # reference src/utils.py:416-474, 199-247).  Activations are channels_last tensors of logical shape (N, C, H, W).
 def _norm_desc(N, H, W, C, groups, affine, relu, eps):

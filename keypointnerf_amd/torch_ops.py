@@ -37,6 +37,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
                                  stride 2, pad 3) on an NCHW tensor; DIFFERENTIABLE (the stem w.r.t. weight and bias only)
     torch.ops.kpnerf.conv_transpose2d_up2(x, weight, bias?) -> y   ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1),
                                  DIFFERENTIABLE w.r.t. x, weight and bias (kpn_conv2d_s2_forward / _backward)
+    torch.ops.kpnerf.conv2d_replicate(x, weight, bias?) -> y   ReplicationPad2d(k // 2) + Conv2d(k) for a 3x3 or 7x7 weight (a 7x7 weight
+                                 with at most 4 input channels: the stem, on an NCHW tensor); DIFFERENTIABLE (the stem w.r.t. weight and
+                                 bias only) (kpn_conv2d_rp_forward / _backward); the input gradient is a gather without atomics
     torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
                                  4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
                                  _backward); y is not kept for the backward and may be overwritten in place
@@ -542,8 +545,14 @@ def conv2d_cache_clear():
 
 
 def _conv_packed(weight, kind=None):
-    """the packed copies of a weight: of the stride-1 layer (kind None) or of one of the kpn_conv2d_s2_* kinds"""
-    pack = ops.conv2d_pack if kind is None else (lambda w: ops.conv2d_s2_pack(w, kind))
+    """the packed copies of a weight: of the stride-1 layer (kind None), of one of the kpn_conv2d_s2_* kinds (an integer) or of one of
+    the kpn_conv2d_rp_* kinds (("rp", kind))"""
+    if kind is None:
+        pack = ops.conv2d_pack
+    elif isinstance(kind, tuple):           # ("rp", KPN_RP_*)
+        pack = lambda w: ops.conv2d_rp_pack(w, kind[1])  # noqa: E731
+    else:
+        pack = lambda w: ops.conv2d_s2_pack(w, kind)  # noqa: E731
     if weight.is_inference():
         return pack(weight)
     key = _tensor_key(weight) + (kind,)
@@ -736,6 +745,82 @@ _fragment.define("conv2d_down2(Tensor x, Tensor weight, Tensor? bias) -> Tensor"
 _fragment.impl("conv2d_down2", _conv2d_down2, "CompositeImplicitAutograd")
 _fragment.define("conv_transpose2d_up2(Tensor x, Tensor weight, Tensor? bias) -> Tensor")
 _fragment.impl("conv_transpose2d_up2", _conv_transpose2d_up2, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.conv2d_replicate: ReplicationPad2d(k // 2) + Conv2d(k), DIFFERENTIABLE ----
+# One operator for the three kinds of kpn_conv2d_rp_*, the kind following the weight: 3x3, 7x7, or - a 7x7 weight with at most 4 input
+# channels - the stem, which reads a contiguous NCHW tensor as it is and has no input gradient: it raises on an x that requires one.
+# The packed copies live in the cache of kpnerf::conv2d, keyed by weight and kind.
+def _rp_key(kind):
+    return ("rp", kind)         # beside None (stride 1) and the KPN_S2_* integers in the cache key
+
+
+@_lib.custom_op("kpnerf::conv2d_replicate_cl", mutates_args=(), device_types="cuda")
+def conv2d_replicate_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """conv2d(pad(x, k // 2, mode="replicate"), weight, bias) for weight (cout, cin, k, k), k = 3 or 7 (x channels_last, cin and cout
+    multiples of 4) or k = 7 with cin <= 4 (x contiguous NCHW) (kpn_conv2d_rp_forward): what torch.ops.kpnerf.conv2d_replicate runs
+    after its memory-format conversion.  Returns (N, cout, H, W) channels_last."""
+    kind = ops.conv2d_rp_kind(weight.shape)
+    return ops.conv2d_rp_forward(x, _conv_packed(weight, _rp_key(kind)), bias, weight.shape[0], kind)
+
+
+@conv2d_replicate_cl.register_fake
+def _(x, weight, bias):
+    N, _, H, W = x.shape
+    return x.new_empty(N, H, W, weight.shape[0]).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::conv2d_rp_backward", mutates_args=(), device_types="cuda")
+def conv2d_rp_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, kind: int, has_bias: bool,
+                       mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dweight, dbias) of kpnerf::conv2d_replicate_cl for the output gradient dy (kpn_conv2d_rp_backward); kind is the KPN_RP_*
+    value; mask = [dx, dweight, dbias] wanted: a leg that is not wanted is not launched and its result is an empty tensor."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = ops.conv2d_rp_backward(x, dy, _conv_packed(weight, _rp_key(kind)) if mask[0] else None, x.shape, kind, has_bias,
+                                        want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    return _empty_for_none(dy, dx, dw, db)
+
+
+@conv2d_rp_backward.register_fake
+def _(x, weight, dy, kind, has_bias, mask):
+    e = x.new_empty(0)
+    return (torch.empty_like(x, memory_format=torch.channels_last) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
+            x.new_empty(weight.shape[0]) if mask[2] and has_bias else e)
+
+
+def _rp_setup(ctx, inputs, output):
+    x, weight, bias = inputs
+    ctx.kind, ctx.has_bias = ops.conv2d_rp_kind(weight.shape), bias is not None
+    if ctx.kind == kl.RP_STEM7 and ctx.needs_input_grad[0]:
+        raise RuntimeError("kpnerf::conv2d_replicate: the 7x7 stem has no input gradient (x.requires_grad is set)")
+    ctx.save_for_backward(x, weight)
+    ctx.set_materialize_grads(False)
+
+
+def _rp_bwd(ctx, dy):
+    if dy is None:
+        return None, None, None
+    x, weight = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
+    if not any(mask):
+        return None, None, None
+    dx, dw, db = torch.ops.kpnerf.conv2d_rp_backward(x, weight, dy, ctx.kind, ctx.has_bias, mask)
+    return _none_unless(mask, dx, dw, db)
+
+
+conv2d_replicate_cl.register_autograd(_rp_bwd, setup_context=_rp_setup)
+
+
+# torch.ops.kpnerf.conv2d_replicate(x, weight, bias): x in any memory format, converted once (as kpnerf::conv2d does) - to channels_last,
+# or to contiguous NCHW for the stem, which reads that layout as it is.
+def _conv2d_replicate(x, weight, bias):
+    stem = ops.conv2d_rp_kind(weight.shape) == kl.RP_STEM7
+    return torch.ops.kpnerf.conv2d_replicate_cl(x.contiguous() if stem else x.contiguous(memory_format=torch.channels_last), weight, bias)
+
+
+_fragment.define("conv2d_replicate(Tensor x, Tensor weight, Tensor? bias) -> Tensor")
+_fragment.impl("conv2d_replicate", _conv2d_replicate, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.group_norm: GroupNorm / InstanceNorm2d [+ ReLU], DIFFERENTIABLE w.r.t. x, weight and bias ----
