@@ -52,6 +52,9 @@ extern "C" {
 /* still 10: the replication-padded stride-1 convolutions with their gradients (kpn_conv2d_rp_desc, kpn_conv2d_rp_packed_floats,
  * kpn_conv2d_rp_pack_device, kpn_conv2d_rp_workspace_bytes, kpn_conv2d_rp_wgrad_ranges, kpn_conv2d_rp_forward, kpn_conv2d_rp_backward)
  * are additive within 10 in the same way */
+/* still 10: a whole ConvBlock as one differentiable operator (kpn_conv_block_desc, kpn_conv_block_params, kpn_conv_block_grads,
+ * kpn_conv_block_workspace_bytes, kpn_conv_block_state_floats, kpn_conv_block_forward, kpn_conv_block_backward) is additive within 10
+ * in the same way */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -772,6 +775,56 @@ int kpn_avg_pool2_backward(const kpn_resample2_desc* desc, const float* dy_low, 
 int kpn_upsample2x_add_forward(const kpn_resample2_desc* desc, const float* low, const float* skip /* NULL or high */,
                                float* y_high /* may alias skip */, void* stream);
 int kpn_upsample2x_add_backward(const kpn_resample2_desc* desc, const float* dy_high, float* d_low, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A whole ConvBlock(cin, cout, norm = "group") (src/utils.py:416-474) for training, forward and backward, as one call each: replaces
+ * the three or four GroupNorm -> ReLU -> Conv2d legs, torch.cat and the residual add, with their autograd.  With c = cout the legs
+ * are bn1 / conv1 (cin -> c/2, 3x3), bn2 / conv2 (c/2 -> c/4), bn3 / conv3 (c/4 -> c/4) and, for cin != cout, bn4 / the 1x1
+ * downsample convolution (cin -> c); every norm is GroupNorm(min(32, C), C) with parameters, no convolution has a bias.
+ * Activations are NHWC (torch channels_last), dense, fp32: x, dx (N, H, W, cin); y, dy (N, H, W, cout).
+ * Scope: cin, cout / 2 and cout / 4 powers of two in 4 .. 1024 (cout <= 1024 when cin != cout), N in 1 .. 65535, H, W >= 1,
+ * N H W max(cin, cout) < 2^31, eps > 0; every pointer 16-byte aligned.  Anything else is refused with KPN_EINVAL, kpn_last_error()
+ * names the field, and nothing is launched.  Kernels: csrc/encoder_kernels.hip; dataflow: csrc/api_block.hip.
+ *   params:  gamma[i] / beta[i] of bn(i+1), packed[i] = what kpn_conv2d_pack_device gives for the weight of conv(i+1) (k = 3) and,
+ *            at index 3, of the downsample convolution (k = 1): the forward copy, then the flipped copy.  Index 3 is not read for
+ *            cin == cout.  The backward does not read beta.
+ *   forward: the dataflow of the inference encoders - GroupNorm statistics only (those of kpn_group_norm_forward), scale / shift and
+ *            the ReLU applied inside the loads of the convolution (those of kpn_conv2d_forward), the convolutions writing channel
+ *            slices, the residual (x, or the downsample leg) added once: y has the bits of the same block computed leg by leg with
+ *            kpn_group_norm_forward(relu = 1), kpn_conv2d_forward, a concatenation and one fp32 add.
+ *   state (kpn_conv_block_state_floats; written by the forward, read by the backward):
+ *            S (N, H, W, 3c/4): the outputs of conv1 (channels [0, c/2)) and conv2 ([c/2, 3c/4)) before the residual is added - the
+ *            sources of bn2 and bn3; conv3's output is added to the residual in its epilogue and is not kept.  Then, per leg in
+ *            order: scale [N][C], shift [N][C], mean [N][G], rstd [N][G] as kpn_group_norm_forward keeps them.  No normalised tensor.
+ *   backward: dx (or NULL), and per leg grads->dgamma[i], dbeta[i], dw[i] (OIHW), each of which may be NULL: nothing is written for
+ *            a NULL result, and a leg that neither it nor anything upstream of it needs is not launched.  Results are overwritten,
+ *            not accumulated.  Each leg is the input gradient of kpn_conv2d_backward, the weight gradient with the norm and the ReLU
+ *            recomputed in its loads, and the norm gradient of kpn_group_norm_backward with the part of dy that reached the leg's
+ *            source through the concatenation added behind its expression.  dx = dy + (norm gradient of bn1) for cin == cout;
+ *            dx = (norm gradient of bn1) + (norm gradient of bn4), in this order, for cin != cout.
+ * `workspace` (kpn_conv_block_workspace_bytes; 0 = unsupported descriptor) serves the forward and the backward alike.
+ * No float atomics: every result is bit-identical from run to run, and an image's y and dx do not depend on its batch. */
+typedef struct kpn_conv_block_desc {
+    int32_t N, H, W, cin, cout;
+    float eps;
+} kpn_conv_block_desc;
+typedef struct kpn_conv_block_params {
+    const float* gamma[4];
+    const float* beta[4];
+    const float* packed[4];
+} kpn_conv_block_params;
+typedef struct kpn_conv_block_grads {
+    float* dgamma[4];
+    float* dbeta[4];
+    float* dw[4];
+} kpn_conv_block_grads;
+size_t kpn_conv_block_workspace_bytes(const kpn_conv_block_desc* desc);
+size_t kpn_conv_block_state_floats(const kpn_conv_block_desc* desc);
+int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const float* x, const kpn_conv_block_params* params, float* y, float* state,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
+                            const float* state, float* dx, const kpn_conv_block_grads* grads, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -111,7 +111,7 @@ extern "C" int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, 
         kpn_enc_conv_args c = p.fwd.a;
         c.Hs = desc->H; c.Ws = desc->W; c.stride = 1; c.pad = desc->pad;
         c.src = x; c.src_cs = desc->cin;
-        enc::launch_wgrad(c, p.fwd, p.wg, 0, dy, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
+        enc::launch_wgrad(c, p.fwd, p.wg, 0, dy, desc->cout, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
     }
     if (db) enc::launch_dbias(dy, p.fwd.M, desc->cout, reinterpret_cast<double*>(ws + p.o_db), db, stream);
     return check_launch("kpn_conv2d_backward");

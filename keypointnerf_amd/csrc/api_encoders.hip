@@ -6,8 +6,8 @@
 // (keypointnerf_amd/encoders.py builds it from the caller's module in the same order).
 //
 // In front of the walks, the launch layer of encoder_kernels.hip: every launch policy of the kernels that the walks share with
-// the differentiable layers (api_conv.hip, api_strided.hip, api_norm.hip, api_resample.hip) - tiles, split K, the ranges of a weight
-// gradient, chunk counts, grids - is written there once, and all five files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
+// the differentiable layers (api_conv.hip, api_strided.hip, api_reppad.hip, api_norm.hip, api_block.hip, api_resample.hip) - tiles,
+// split K, the ranges of a weight gradient, chunk counts, grids - is written there once, and all of these files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
 // so a walk and a layer agree bit for bit only while they share this code.
 namespace enc {
 
@@ -100,12 +100,13 @@ inline WgradPlan wgrad_plan(const ConvGeom& g) {
     p.partial = (int64_t)p.nranges * p.krows * a.cout;
     return p;
 }
-// `c`: g.a with the source of A filled in (Hs, Ws, stride, pad, src, src_cs; the stem's Hraw, Wraw, stem_plain); rhs (g.M, cout) dense
-inline void launch_wgrad(const kpn_enc_conv_args& c, const ConvGeom& g, const WgradPlan& p, int stem, const float* rhs, float* partial,
-                         float* dw, void* stream) {
+// `c`: g.a with the source of A filled in (Hs, Ws, stride, pad, src, src_cs; the stem's Hraw, Wraw, stem_plain; ss and relu_in = 1 for
+// a norm fused into the loads); rhs (g.M, cout) with channel stride rhs_cs
+inline void launch_wgrad(const kpn_enc_conv_args& c, const ConvGeom& g, const WgradPlan& p, int stem, const float* rhs, int rhs_cs,
+                         float* partial, float* dw, void* stream) {
     kpn_enc_wgrad_args a{};
     a.c = c;
-    a.rhs = rhs; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
+    a.rhs = rhs; a.rhs_cs = rhs_cs; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
     a.partial = partial; a.dw = dw;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.nranges);
     if (stem) {
@@ -134,6 +135,15 @@ inline int stats_chunks(int nimg, int HW, int C, int64_t* partial_doubles) {
 inline void launch_stats(const kpn_enc_stats_args& a, void* stream) {
     KPN_LAUNCH(k_enc_stats_partial, dim3((unsigned)a.nchunks, (unsigned)a.nimg), dim3(256), stream, a);
     KPN_LAUNCH(k_enc_stats_final, dim3((unsigned)((a.nimg * a.G + 63) / 64)), dim3(64), stream, a);
+}
+// the three passes of a norm's gradient (pass 3 only with a.coef); a.nchunks is stats_chunks' of the same shape
+inline void launch_norm_bwd(const kpn_enc_norm_bwd_args& a, void* stream) {
+    KPN_LAUNCH(k_enc_norm_bwd_partial, dim3((unsigned)a.nchunks, (unsigned)a.nimg), dim3(256), stream, a);
+    KPN_LAUNCH(k_enc_norm_bwd_final, dim3((unsigned)((a.nimg * a.G + a.C + 63) / 64)), dim3(64), stream, a);
+    if (a.coef) KPN_LAUNCH(k_enc_norm_bwd_dx, grid4((int64_t)a.nimg * a.HW * a.C / 4), dim3(256), stream, a);
+}
+inline void launch_add_cs(const float* a, int a_cs, const float* b, int b_cs, float* dst, int dst_cs, int64_t M, int C, void* stream) {
+    KPN_LAUNCH(k_enc_add_cs, grid4(M * C / 4), dim3(256), stream, a, a_cs, b, b_cs, dst, dst_cs, M, C);
 }
 inline void launch_affine(const float* src, const float* ss, int relu, const float* res, float* dst, int nimg, int HW, int C, void* stream) {
     KPN_LAUNCH(k_enc_affine, grid4((int64_t)nimg * HW * C / 4), dim3(256), stream, src, ss, relu, res, dst, nimg, HW, C);

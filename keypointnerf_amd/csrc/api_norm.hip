@@ -75,13 +75,11 @@ extern "C" int kpn_group_norm_backward(const kpn_group_norm_desc* desc, const fl
     if (!dx && !dgamma && !dbeta) return KPN_OK;
     char* ws = static_cast<char*>(workspace);
     kpn_enc_norm_bwd_args a{};
-    a.x = x; a.dy = dy; a.ss = stats; a.mr = stats + (size_t)2 * desc->N * desc->C; a.gamma = gamma;
+    a.x = x; a.x_cs = desc->C; a.dy = dy; a.ss = stats; a.mr = stats + (size_t)2 * desc->N * desc->C; a.gamma = gamma;
     a.relu = desc->relu; a.C = desc->C; a.HW = p.HW; a.nchunks = p.nchunks; a.nimg = desc->N; a.G = desc->G;
     a.partial = reinterpret_cast<double*>(ws + p.o_partial);
     a.coef = dx ? reinterpret_cast<float*>(ws + p.o_coef) : nullptr;
     a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
-    KPN_LAUNCH(k_enc_norm_bwd_partial, dim3((unsigned)p.nchunks, (unsigned)desc->N), dim3(256), stream, a);
-    KPN_LAUNCH(k_enc_norm_bwd_final, dim3((unsigned)((desc->N * desc->G + desc->C + 63) / 64)), dim3(64), stream, a);
-    if (dx) KPN_LAUNCH(k_enc_norm_bwd_dx, enc::grid4((int64_t)desc->N * p.HW * desc->C / 4), dim3(256), stream, a);
+    enc::launch_norm_bwd(a, stream);
     return check_launch("kpn_group_norm_backward");
 }

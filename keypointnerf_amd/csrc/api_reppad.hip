@@ -124,7 +124,7 @@ extern "C" int kpn_conv2d_rp_backward(const kpn_conv2d_rp_desc* desc, const floa
     if (dw) {
         kpn_enc_conv_args c = p.g.fwd.a;
         rp::source(c, desc, x);
-        enc::launch_wgrad(c, p.g.fwd, p.wg, desc->kind == KPN_RP_STEM7, dy, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
+        enc::launch_wgrad(c, p.g.fwd, p.wg, desc->kind == KPN_RP_STEM7, dy, c.cout, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
     }
     if (db) enc::launch_dbias(dy, p.g.fwd.M, desc->cout, reinterpret_cast<double*>(ws + p.o_db), db, stream);
     return check_launch("kpn_conv2d_rp_backward");

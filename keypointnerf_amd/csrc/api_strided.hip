@@ -161,7 +161,7 @@ extern "C" int kpn_conv2d_s2_backward(const kpn_conv2d_s2_desc* desc, const floa
         if (desc->kind == KPN_S2_CONV3) s2::strided_source(c, x, desc->H, desc->W);
         else if (desc->kind == KPN_S2_STEM7) s2::stem_source(c, x, desc->H, desc->W);
         else { s2::strided_source(c, dy, p.Ho, p.Wo); rhs = x; }             // the swapped roles
-        enc::launch_wgrad(c, p.g.wg, p.wg, desc->kind == KPN_S2_STEM7, rhs, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
+        enc::launch_wgrad(c, p.g.wg, p.wg, desc->kind == KPN_S2_STEM7, rhs, c.cout, reinterpret_cast<float*>(ws + p.o_wg), dw, stream);
     }
     if (db) enc::launch_dbias(dy, p.My, desc->cout, reinterpret_cast<double*>(ws + p.o_db), db, stream);
     return check_launch("kpn_conv2d_s2_backward");

@@ -21,7 +21,7 @@
 //              them in split order and runs the epilogue.  The split depends on the per-image geometry only.
 // Beside it: k_enc_stats_partial / k_enc_stats_final (GroupNorm / InstanceNorm statistics in fp64 partial sums, reduced in a
 // fixed order and folded with gamma / beta into the scale / shift the next loads use), k_enc_affine (normalise [+ ReLU]
-// [+ residual] where the value is needed as a tensor), k_enc_norm_bwd_partial / _final / _dx (the gradient of statistics +
+// [+ residual] where the value is needed as a tensor), k_enc_add_cs (the sum of two channel slices), k_enc_norm_bwd_partial / _final / _dx (the gradient of statistics +
 // affine, api_norm.hip), k_enc_pool2 / k_enc_pool2_bwd (avg_pool2d(x, 2, 2) and its gradient), k_enc_upadd (bicubic x2,
 // align_corners = True, ATen's coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of HourGlass._forward;
 // out of place or in place, with or without the added tensor), k_enc_up2_bwd (its gradient with respect to the low tensor, a gather
@@ -327,6 +327,22 @@ __global__ __launch_bounds__(256) void k_enc_affine(const float* src, const floa
     }
 }
 
+// dst[p][c] = a[p][c] + b[p][c] over M pixels of C channels, each tensor with its own channel stride: the residual add of the
+// single-operator ConvBlock over the channel slices it keeps (api_block.hip).  dst may be b itself: a thread reads its float4 of b
+// before it writes the same float4 of dst, and no other thread touches it
+__global__ __launch_bounds__(256) void k_enc_add_cs(const float* a, int a_cs, const float* b, int b_cs, float* dst, int dst_cs, int64_t M, int C) {
+    const int c4 = C / 4;
+    const int64_t total = M * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const size_t p = (size_t)(i / c4);
+        const kpn_f32x4 u = *KPN_GLOBAL4(a + p * a_cs + c), r = *KPN_GLOBAL4(b + p * b_cs + c);
+        kpn_f32x4 v;
+        for (int e = 0; e < 4; ++e) v[e] = KADD(u[e], r[e]);
+        *reinterpret_cast<kpn_f32x4*>(dst + p * dst_cs + c) = v;
+    }
+}
+
 // ---- gradient of y = [relu](x * scale + shift), scale / shift / mean / rstd as k_enc_stats_final left them (api_norm.hip).
 // With g = the gradient behind the ReLU (the mask is recomputed from fmaf(x, scale, shift): the forward's own bits),
 // A_c = sum g and B_c = sum g x per (image, channel), ds = sum_c gamma_c B_c, db = sum_c gamma_c A_c over a group, cnt = cpg HW:
@@ -334,8 +350,9 @@ __global__ __launch_bounds__(256) void k_enc_affine(const float* src, const floa
 //   dgamma_c = sum_n (B_nc - mean A_nc) rstd,   dbeta_c = sum_n A_nc
 // Every sum is fp64 in a fixed order (no atomics); each result is rounded once.
 struct kpn_enc_norm_bwd_args {
-    const float* x;        // NHWC dense (nimg, HW, C)
-    const float* dy;
+    const float* x;        // NHWC (nimg, HW, C) with channel stride x_cs (C for a dense tensor; wider for a channel slice)
+    int x_cs;
+    const float* dy;       // dense, like dx
     const float* ss;       // scale [nimg][C] then shift [nimg][C]
     const float* mr;       // mean [nimg][G] then rstd [nimg][G]
     const float* gamma;    // or NULL
@@ -345,6 +362,8 @@ struct kpn_enc_norm_bwd_args {
     float* dx;
     float* dgamma;         // or NULL
     float* dbeta;          // or NULL
+    const float* add;      // or NULL; pass 3: dx = add + (g a + (x c2 + c3)), one fp32 add behind the expression.  (nimg, HW, C) with
+    int add_cs;            // channel stride add_cs; add may be dx itself (a thread reads its float4 before it writes the same one)
 };
 __device__ __forceinline__ kpn_f32x4 kpn_enc_norm_g(kpn_f32x4 x, kpn_f32x4 dy, kpn_f32x4 sc, kpn_f32x4 sh, int relu) {
     kpn_f32x4 g = dy;
@@ -366,8 +385,8 @@ __global__ __launch_bounds__(256) void k_enc_norm_bwd_partial(kpn_enc_norm_bwd_a
         kpn_f32x4 v[4], d[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const size_t o = ((size_t)n * a.HW + (p + j * PP < p1 ? p + j * PP : p)) * a.C + cl * 4;
-            v[j] = *KPN_GLOBAL4(a.x + o); d[j] = *KPN_GLOBAL4(a.dy + o);
+            const size_t q = (size_t)n * a.HW + (p + j * PP < p1 ? p + j * PP : p);
+            v[j] = *KPN_GLOBAL4(a.x + q * a.x_cs + cl * 4); d[j] = *KPN_GLOBAL4(a.dy + q * a.C + cl * 4);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -426,7 +445,7 @@ __global__ __launch_bounds__(64) void k_enc_norm_bwd_final(kpn_enc_norm_bwd_args
     if (a.dgamma) a.dgamma[c] = (float)dg;
     if (a.dbeta) a.dbeta[c] = (float)dbt;
 }
-// pass 3: dx = g a + (x c2 + c3), elementwise over float4s like k_enc_affine
+// pass 3: dx = [add +] (g a + (x c2 + c3)), elementwise over float4s like k_enc_affine
 __global__ __launch_bounds__(256) void k_enc_norm_bwd_dx(kpn_enc_norm_bwd_args a) {
     const int c4 = a.C / 4;
     const int64_t total = (int64_t)a.nimg * a.HW * c4;
@@ -435,13 +454,17 @@ __global__ __launch_bounds__(256) void k_enc_norm_bwd_dx(kpn_enc_norm_bwd_args a
         const int c = (int)(i % c4) * 4;
         const int n = (int)(i / c4 / a.HW);
         const size_t k = (size_t)n * a.C + c;
-        const kpn_f32x4 v = *KPN_GLOBAL4(a.x + i * 4);
+        const kpn_f32x4 v = *KPN_GLOBAL4(a.x + (size_t)(i / c4) * a.x_cs + c);
         kpn_f32x4 sc = {0.0f, 0.0f, 0.0f, 0.0f}, sh = sc;
         if (a.relu) { sc = *KPN_GLOBAL4(a.ss + k); sh = *KPN_GLOBAL4(a.ss + nc + k); }
         const kpn_f32x4 g = kpn_enc_norm_g(v, *KPN_GLOBAL4(a.dy + i * 4), sc, sh, a.relu);
         const kpn_f32x4 ca = *KPN_GLOBAL4(a.coef + k), c2 = *KPN_GLOBAL4(a.coef + nc + k), c3 = *KPN_GLOBAL4(a.coef + 2 * nc + k);
         kpn_f32x4 o;
         for (int e = 0; e < 4; ++e) o[e] = fmaf(g[e], ca[e], fmaf(v[e], c2[e], c3[e]));
+        if (a.add) {
+            const kpn_f32x4 r = *KPN_GLOBAL4(a.add + (size_t)(i / c4) * a.add_cs + c);
+            for (int e = 0; e < 4; ++e) o[e] = KADD(r[e], o[e]);
+        }
         *reinterpret_cast<kpn_f32x4*>(a.dx + i * 4) = o;
     }
 }
@@ -643,8 +666,10 @@ __global__ __launch_bounds__(256) void k_enc_pack(kpn_enc_pack_args a) {
 // The GEMM's K-rows are tap * cin_p + ci (cin_p > cin for the stems only: STEM loads the NCHW tensor through
 // kpn_enc_load_a<true, false>); kpn_enc_wgrad_row maps one to its real row in `partial`, for the store and the combine alike.
 struct kpn_enc_wgrad_args {
-    kpn_enc_conv_args c;       // the geometry and source of A (ss = NULL, no ReLU); wp, dst, partial unused
-    const float* rhs;          // R: NHWC (nimg, Ho, Wo, cout), dense
+    kpn_enc_conv_args c;       // the geometry and source of A; wp, dst, partial unused.  ss with relu_in = 1: A is relu(fmaf(x, scale,
+                               // shift)) computed in the loads from the un-normalised source (the legs of api_block.hip); else ss = NULL
+    const float* rhs;          // R: NHWC (nimg, Ho, Wo, cout) with channel stride rhs_cs (cout for a dense tensor)
+    int rhs_cs;
     int krows;                 // kh * kw * cin: the real rows
     int nchunks, cpr, nranges; // 16-pixel chunks in all / per range; ranges (gridDim.y)
     float* partial;            // [range][krows][cout]
@@ -683,7 +708,7 @@ __global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
         if (bload) {
             const int64_t p = (int64_t)s * 16 + bp;
             rb = kpn_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.rhs + (size_t)p * a.c.cout + bco);
+            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.rhs + (size_t)p * a.rhs_cs + bco);
         }
     };
     const int wn = wave % (BN / 32), wm = wave / (BN / 32);

@@ -411,6 +411,7 @@ class NativeTraining:
     natively)"""
     norm_calls = 0
     block_calls = 0
+    fused_block_calls = 0
     hourglass_calls = 0
     strided_calls = 0
     geo_calls = 0
@@ -484,13 +485,47 @@ def _block_ineligible(m, name):
     return None
 
 
-def install_native_blocks(module):
+def _fused_block_ineligible(m, name):
+    """_block_ineligible, and that kpn_conv_block_* serves the widths and every norm has one eps"""
+    why = _block_ineligible(m, name)
+    if why is not None:
+        return why
+    cin, cout = m.bn1.num_channels, 2 * m.conv1.out_channels
+    if not ops.conv_block_supported(cin, cout):
+        return f"channels {cin} -> {cout} (the single-operator block serves at most 1024 output channels behind a downsample leg)"
+    eps = {float(getattr(m, f"bn{i}").eps) for i in range(1, 5 if cin != cout else 4)}
+    if len(eps) != 1:
+        return f"the norms have different eps {sorted(eps)}"
+    return None
+
+
+def install_native_blocks(module, fused=False):
     """Opt-in: rebinds ``forward`` on every ConvBlock under ``module`` whose structure is the reference's (src/utils.py:416-474; the
     check the native encoder makes) to the same dataflow on the project's kernels: each ``bn -> nl -> conv`` leg, the downsample leg
     included, is torch.ops.kpnerf.group_norm(relu=True) followed by torch.ops.kpnerf.conv2d; ``torch.cat`` and the residual add
     stay on torch.  A ConvBlock that fails the check is left alone.  CPU or non-fp32 input goes to the original forward.  The module
     tree, the parameter names and the state_dict are untouched.  Returns (served, left): the names served, and {name: reason} of
-    the ConvBlocks left alone."""
+    the ConvBlocks left alone.
+
+    ``fused=True``: the rebound forward is one torch.ops.kpnerf.conv_block call instead (kpn_conv_block_forward / _backward): one
+    autograd node per block, no aten operator inside it - the norms and the ReLUs run in the loads of the convolutions, forward and
+    backward, the convolutions write their slices of the concatenation, the residual is added once - and x plus 3/4 of an
+    output-sized tensor kept for the backward instead of every leg's input and normalised input.  Its forward has the bits of the
+    unfused path.  ``NativeTraining.fused_block_calls`` counts these calls (``block_calls`` the unfused ones)."""
+    def make_fused(_prev):
+        def forward(self, x):
+            if not _native_input(x, *self.parameters()):
+                return _prev(x)
+            NativeTraining.fused_block_calls += 1
+            legs = [(self.bn1, self.conv1), (self.bn2, self.conv2), (self.bn3, self.conv3)]
+            if self.downsample is not None:
+                legs.append((self.bn4, self.downsample[2]))
+            return torch.ops.kpnerf.conv_block(x, [t for bn, conv in legs for t in (bn.weight, bn.bias, conv.weight)], self.bn1.eps)
+        return forward
+
+    if fused:
+        return _rebind_forward(module, "_kpnerf_block_saved", lambda m: type(m).__name__ == "ConvBlock", _fused_block_ineligible, make_fused)
+
     def make_forward(_prev):
         def forward(self, x):
             if not _native_input(x, *self.parameters()):
@@ -513,7 +548,7 @@ def install_native_blocks(module):
 
 
 def uninstall_native_blocks(module):
-    """Restores what ``forward`` was on every ConvBlock ``install_native_blocks`` rebound."""
+    """Restores what ``forward`` was on every ConvBlock ``install_native_blocks`` rebound, fused or not."""
     return _restore_forward(module, "_kpnerf_block_saved")
 
 
@@ -675,7 +710,7 @@ def _geo_ineligible(m, name):
 _GEO_PARTS = ("strided", "convs", "norms", "blocks", "hourglass")
 
 
-def install_native_geo(module):
+def install_native_geo(module, fused_blocks=False):
     """Opt-in: trains every HGFilterV2 under ``module`` (``module`` itself included) on the project's kernels.  An HGFilterV2 whose
     structure is the reference's (src/utils.py:322-414: its children for any ``n_stack`` >= 1, ``norm="group"``, ``hd`` either way) gets
     ``install_native_strided``, ``install_native_convs``, ``install_native_norms``, ``install_native_blocks`` and
@@ -686,7 +721,8 @@ def install_native_geo(module):
     is not a CUDA fp32 (N, C, H, W) tensor whose stem output has even H and W goes to the original forward.  The module tree, the
     parameter names and the state_dict are untouched.  Returns {installer: (served, left)} for "geo" and the five installers, the
     names relative to ``module``; a layer that one of the five leaves because it is another's (the stride-2 stem among the
-    nn.Conv2d) is not listed as left."""
+    nn.Conv2d) is not listed as left.  ``fused_blocks=True`` installs the ConvBlocks as ``install_native_blocks(fused=True)`` does:
+    one torch.ops.kpnerf.conv_block per block, and no ``torch.cat`` or residual add left inside a block."""
     def make_forward(_prev):
         def forward(self, x):
             if not _native_input(x, *self.parameters()) or (((x.shape[2] - 1) // 2 + 1) % 2 or ((x.shape[3] - 1) // 2 + 1) % 2):
@@ -716,8 +752,8 @@ def install_native_geo(module):
     report = {k: ([], {}) for k in _GEO_PARTS}
     subs = dict(module.named_modules())
     for name in served:
-        for part, fn in zip(_GEO_PARTS, (install_native_strided, install_native_convs, install_native_norms, install_native_blocks,
-                                         install_native_hourglass)):
+        for part, fn in zip(_GEO_PARTS, (install_native_strided, install_native_convs, install_native_norms,
+                                         lambda m: install_native_blocks(m, fused=fused_blocks), install_native_hourglass)):
             s_, l_ = fn(subs[name])
             pre = name + "." if name else ""
             report[part][0].extend(pre + n for n in s_)

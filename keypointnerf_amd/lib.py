@@ -107,6 +107,21 @@ class GroupNormDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "C", "G", "affine", "relu")] + [("eps", c_f)]
 
 
+class ConvBlockDesc(ctypes.Structure):
+    """struct kpn_conv_block_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "cin", "cout")] + [("eps", c_f)]
+
+
+class ConvBlockParams(ctypes.Structure):
+    """struct kpn_conv_block_params"""
+    _fields_ = [("gamma", c_p * 4), ("beta", c_p * 4), ("packed", c_p * 4)]
+
+
+class ConvBlockGrads(ctypes.Structure):
+    """struct kpn_conv_block_grads"""
+    _fields_ = [("dgamma", c_p * 4), ("dbeta", c_p * 4), ("dw", c_p * 4)]
+
+
 class ResampleDesc(ctypes.Structure):
     """struct kpn_resample2_desc"""
     _fields_ = [(n, c_i32) for n in ("N", "h", "w", "C")]
@@ -230,6 +245,11 @@ _SIGNATURES = {
     "kpn_group_norm_workspace_bytes": (c_sz, [ctypes.POINTER(GroupNormDesc)]),
     "kpn_group_norm_forward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_group_norm_backward": (ctypes.c_int, [ctypes.POINTER(GroupNormDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv_block_workspace_bytes": (c_sz, [ctypes.POINTER(ConvBlockDesc)]),
+    "kpn_conv_block_state_floats": (c_sz, [ctypes.POINTER(ConvBlockDesc)]),
+    "kpn_conv_block_forward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv_block_backward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p,
+                                               ctypes.POINTER(ConvBlockGrads), c_p, c_sz, c_p]),
     "kpn_avg_pool2_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_avg_pool2_backward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_upsample2x_add_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p, c_p]),

@@ -1276,6 +1276,94 @@ def group_norm_backward(x, dy, weight, stats, groups, eps, relu, want_dx=True, w
 
 
 # ------------------------------------------------------------------------------------------------
+# A whole ConvBlock and its gradients as one call each (kpn_conv_block_*; reference src/utils.py:416-474, norm = "group").  Activations
+# are channels_last tensors of logical shape (N, C, H, W).  ``norms`` is [(gamma, beta)] and ``packed`` [conv2d_pack(weight)] per leg:
+# bn1 / conv1, bn2 / conv2, bn3 / conv3 and, for cin != cout, bn4 / the 1x1 downsample convolution.
+_BLOCK_WORKSPACE = ("kpn_conv_block_workspace_bytes", "kpn_conv_block_forward", "conv_block: unsupported block")
+
+
+def _block_desc(N, H, W, cin, cout, eps):
+    d = kl.ConvBlockDesc()
+    d.N, d.H, d.W, d.cin, d.cout, d.eps = int(N), int(H), int(W), int(cin), int(cout), float(eps)
+    return d
+
+
+def conv_block_supported(cin, cout):
+    """whether kpn_conv_block_* serves a ConvBlock of these widths"""
+    return kl.get_library().kpn_conv_block_workspace_bytes(ctypes.byref(_block_desc(1, 1, 1, cin, cout, 1e-5))) > 0
+
+
+def _block_widths(cin, cout):
+    legs = 4 if cin != cout else 3
+    return legs, (cin, cout // 2, cout // 4, cin)[:legs], (cout // 2, cout // 4, cout // 4, cout)[:legs]
+
+
+def _block_params(L, cin, cout, norms, packed, device, keep):
+    """kpn_conv_block_params of the legs; the tensors it points to are appended to ``keep``"""
+    legs, win, wout = _block_widths(cin, cout)
+    if len(norms) != legs or len(packed) != legs:
+        raise ValueError(f"a ConvBlock({cin}, {cout}) has {legs} legs, got {len(norms)} norms and {len(packed)} packed weights")
+    pr = kl.ConvBlockParams()
+    for i in range(legs):
+        g, b = (_norm_vec(t, f"bn{i + 1}.{n}", win[i]) for t, n in zip(norms[i], ("weight", "bias")))
+        cd = _conv_desc(1, 1, 1, win[i], wout[i], 3 if i < 3 else 1, 0, 0)
+        pk = packed[i]
+        if pk.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(cd)) or pk.dtype != _f32 or pk.device != device:
+            raise ValueError(f"packed[{i}] does not belong to this block's convolution {win[i]} -> {wout[i]} (conv2d_pack)")
+        keep += [g, b, pk]
+        pr.gamma[i], pr.beta[i], pr.packed[i] = g.data_ptr(), b.data_ptr(), pk.data_ptr()
+    return pr
+
+
+def conv_block_forward(x, norms, packed, cout, eps):
+    """ConvBlock(cin, cout)(x) (kpn_conv_block_forward).  x: (N, cin, H, W) channels_last.  Returns (y (N, cout, H, W) channels_last,
+    state): state holds the outputs of conv1 and conv2 and the statistics of every norm, which conv_block_backward reads."""
+    L = kl.get_library()
+    x = _channels_last(x, "x")
+    N, cin, H, W = x.shape
+    d = _block_desc(N, H, W, cin, cout, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_BLOCK_WORKSPACE)
+    keep = []
+    pr = _block_params(L, cin, cout, norms, packed, x.device, keep)
+    y = torch.empty(N, cout, H, W, dtype=_f32, device=x.device, memory_format=torch.channels_last)
+    state = torch.empty(L.kpn_conv_block_state_floats(ctypes.byref(d)), dtype=_f32, device=x.device)
+    L.check(L.kpn_conv_block_forward(ctypes.byref(d), _p(x), ctypes.byref(pr), _p(y), _p(state), _p(ws), nb, _stream()))
+    return y, state
+
+
+def conv_block_backward(x, dy, norms, packed, state, eps, want_dx=True, want=None):
+    """(dx, [(dgamma, dbeta, dw)] per leg) of conv_block_forward for the output gradient dy (N, cout, H, W) channels_last
+    (kpn_conv_block_backward).  ``want`` is [(dgamma, dbeta, dw) wanted] per leg (default: all); what is not wanted is None, and a leg
+    that nothing wanted needs is not launched.  dx is channels_last, dw OIHW."""
+    L = kl.get_library()
+    x, dy = _channels_last(x, "x"), _channels_last(dy, "dy")
+    N, cin, H, W = x.shape
+    cout = dy.shape[1]
+    if tuple(dy.shape) != (N, cout, H, W):
+        raise ValueError(f"dy must be {(N, cout, H, W)}, got {tuple(dy.shape)}")
+    d = _block_desc(N, H, W, cin, cout, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_BLOCK_WORKSPACE)
+    keep = []
+    pr = _block_params(L, cin, cout, norms, packed, x.device, keep)
+    if state.numel() != L.kpn_conv_block_state_floats(ctypes.byref(d)) or state.dtype != _f32 or state.device != x.device:
+        raise ValueError("state does not belong to this block (conv_block_forward)")
+    legs, win, wout = _block_widths(cin, cout)
+    want = [(True, True, True)] * legs if want is None else want
+    new = lambda *shape: torch.empty(*shape, dtype=_f32, device=x.device)  # noqa: E731
+    dx = new(N, H, W, cin) if want_dx else None
+    gr, out = kl.ConvBlockGrads(), []
+    for i in range(legs):
+        k = 3 if i < 3 else 1
+        t = (new(win[i]) if want[i][0] else None, new(win[i]) if want[i][1] else None, new(wout[i], win[i], k, k) if want[i][2] else None)
+        gr.dgamma[i], gr.dbeta[i], gr.dw[i] = (None if v is None else v.data_ptr() for v in t)
+        out.append(t)
+    if want_dx or any(any(w) for w in want):
+        L.check(L.kpn_conv_block_backward(ctypes.byref(d), _p(x), _p(dy), ctypes.byref(pr), _p(state.contiguous()), _p(dx), ctypes.byref(gr),
+                                          _p(ws), nb, _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), out
+
+
+# ------------------------------------------------------------------------------------------------
 # The two resampling steps of an HourGlass and their gradients (kpn_avg_pool2_* / kpn_upsample2x_add_*; avg_pool2d(x, 2, stride=2)
 # and skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) with their autograd, reference
 # src/utils.py:287-306).  Activations are channels_last tensors of logical shape (N, C, H, W).

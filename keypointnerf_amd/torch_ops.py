@@ -43,6 +43,10 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
                                  4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
                                  _backward); y is not kept for the backward and may be overwritten in place
+    torch.ops.kpnerf.conv_block(x, tensors, eps) -> y   a whole ConvBlock(cin, cout, norm="group") as ONE autograd node: tensors =
+                                 [bn1.weight, bn1.bias, conv1.weight, ... bn3 ..., conv3.weight (, bn4.weight, bn4.bias, downsample
+                                 weight)]; channels-last result, DIFFERENTIABLE w.r.t. x and every tensor (kpn_conv_block_forward /
+                                 _backward); keeps x and 3/4 of a y-sized tensor for the backward, never y or a normalised tensor
     torch.ops.kpnerf.avg_pool2(x) -> y   avg_pool2d(x, 2, stride=2) (C a multiple of 4, even H and W), channels-last result,
                                  DIFFERENTIABLE w.r.t. x (kpn_avg_pool2_forward / _backward)
     torch.ops.kpnerf.upsample2x_add(low, skip?) -> y   skip + bicubic x2 of low (align_corners=True; C a multiple of 4), channels-last
@@ -889,6 +893,87 @@ def _group_norm(x, weight, bias, groups, eps, relu):
 
 _fragment.define("group_norm(Tensor x, Tensor? weight, Tensor? bias, int groups, float eps, bool relu) -> Tensor")
 _fragment.impl("group_norm", _group_norm, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.conv_block: a whole ConvBlock, DIFFERENTIABLE w.r.t. x and every parameter, one autograd node ----
+# tensors: per leg (norm weight, norm bias, convolution weight) - bn1 / conv1, bn2 / conv2, bn3 / conv3 and, for cin != cout, bn4 / the
+# 1x1 downsample convolution: 9 or 12 tensors.  The packed copies of the weights come from the cache of kpnerf::conv2d.  The backward
+# reads x, the parameters and `state` (the outputs of conv1 and conv2 and every norm's statistics); it never reads y.
+def _block_legs(tensors):
+    if len(tensors) not in (9, 12):
+        raise ValueError(f"conv_block takes 9 tensors (cin == cout) or 12 (with the downsample leg), got {len(tensors)}")
+    return [tensors[i:i + 3] for i in range(0, len(tensors), 3)]
+
+
+@_lib.custom_op("kpnerf::conv_block_cl", mutates_args=(), device_types="cuda")
+def conv_block_cl(x: torch.Tensor, tensors: List[torch.Tensor], eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, state) of a ConvBlock for a channels_last x (kpn_conv_block_forward): what torch.ops.kpnerf.conv_block runs after its
+    memory-format conversion.  y is (N, cout, H, W) channels_last with cout = 2 * conv1.weight.shape[0]; state is the side buffer of the
+    backward."""
+    legs = _block_legs(tensors)
+    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_conv_packed(w) for _, _, w in legs], 2 * legs[0][2].shape[0], eps)
+
+
+@conv_block_cl.register_fake
+def _(x, tensors, eps):
+    N, cin, H, W = x.shape
+    cout = 2 * tensors[2].shape[0]
+    G = lambda C: min(32, C)  # noqa: E731
+    widths = (cin, cout // 2, cout // 4) + ((cin,) if len(tensors) == 12 else ())
+    return (x.new_empty(N, H, W, cout).permute(0, 3, 1, 2),
+            x.new_empty(N * H * W * (cout // 2 + cout // 4) + sum(2 * N * C + 2 * N * G(C) for C in widths)))
+
+
+@_lib.custom_op("kpnerf::conv_block_backward", mutates_args=(), device_types="cuda")
+def conv_block_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: torch.Tensor, dy: torch.Tensor, eps: float,
+                        mask: List[bool]) -> List[torch.Tensor]:
+    """[dx] + one gradient per tensor of kpnerf::conv_block_cl for the output gradient dy (kpn_conv_block_backward); mask = [dx wanted]
+    + one flag per tensor: what is not wanted is not computed and its result is an empty tensor."""
+    legs = _block_legs(tensors)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
+    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_conv_packed(w) for _, _, w in legs], state, eps,
+                                        want_dx=mask[0], want=want)
+    return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
+
+
+@conv_block_backward.register_fake
+def _(x, tensors, state, dy, eps, mask):
+    # one empty tensor per gradient that is not wanted, as the operator returns them: no two results share memory
+    return [torch.empty_like(x) if mask[0] else x.new_empty(0)] + [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask[1:])]
+
+
+def _conv_block_setup(ctx, inputs, output):
+    x, tensors, eps = inputs
+    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
+    ctx.eps = eps
+    ctx.set_materialize_grads(False)
+
+
+def _conv_block_bwd(ctx, dy, _d_state):
+    x, state, *tensors = ctx.saved_tensors
+    none = (None, [None] * len(tensors), None)
+    if dy is None:
+        return none
+    mask = [bool(ctx.needs_input_grad[0])] + [bool(b) for b in ctx.needs_input_grad[1]]
+    if not any(mask):
+        return none
+    out = torch.ops.kpnerf.conv_block_backward(x, list(tensors), state, dy, ctx.eps, mask)
+    out = _none_unless(mask, *out)
+    return out[0], list(out[1:]), None
+
+
+conv_block_cl.register_autograd(_conv_block_bwd, setup_context=_conv_block_setup)
+
+
+# torch.ops.kpnerf.conv_block(x, tensors, eps): x in any memory format, converted to channels_last once (as kpnerf::conv2d does); the
+# result is channels_last.
+def _conv_block(x, tensors, eps):
+    return torch.ops.kpnerf.conv_block_cl(x.contiguous(memory_format=torch.channels_last), tensors, eps)[0]
+
+
+_fragment.define("conv_block(Tensor x, Tensor[] tensors, float eps) -> Tensor")
+_fragment.impl("conv_block", _conv_block, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.avg_pool2 / upsample2x_add: the two resampling steps of an HourGlass, DIFFERENTIABLE ----

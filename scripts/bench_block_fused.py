@@ -1,0 +1,156 @@
+"""Times training (forward + backward to every gradient) through ConvBlocks and through a whole HGFilterV2 three ways - the untouched
+module, the per-layer native path (encoders.install_native_blocks / install_native_geo) and the single-operator blocks
+(``fused=True`` / ``fused_blocks=True``, torch.ops.kpnerf.conv_block) - and records the peak memory of one training step of the network.
+
+    python scripts/bench_block_fused.py [--views 3] [--size 512] [--reps 20] [--inner 5] [--root CHECKOUT] [--out FILE.md]
+
+blocks: ConvBlock(256, 256) and ConvBlock(128, 256) on N = views channels_last tensors of 64 x 64 and 16 x 16 (the sizes of
+        profiles/norm_backward.md).
+net:    tests/encoder_golden.HGFilterV2 on views x 3 x (size / 2)^2 channels_last input (the geometry encoder at ds = 1).
+memory: torch.cuda.max_memory_allocated over one forward + backward of the network per arm, above what was allocated before the step
+        (parameters, input and seed gradients).
+
+The arms alternate within every repetition: a repetition times `inner` back-to-back steps of one arm between two device events, then
+the next arm; the figures are the median and the range over the repetitions.  ``--root`` imports keypointnerf_amd and tests from another
+checkout of the project (one built there), e.g. the parent commit for a baseline in the same call; a checkout without the
+single-operator block is measured without that arm.  Needs a GPU.
+"""
+import argparse
+import copy
+import inspect
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+
+def timed(fn, inner):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner            # ms
+
+
+def alternate(arms, reps, inner, warm=3):
+    """arms: [(name, fn)] -> {name: dict(median, min, max)} in ms"""
+    for _ in range(warm):
+        for _, fn in arms:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in arms}
+    for _ in range(reps):
+        for n, fn in arms:
+            ts[n].append(timed(fn, inner))
+    return {n: dict(median=statistics.median(t), min=min(t), max=max(t)) for n, t in ts.items()}
+
+
+def cell(r, scale=1.0, digits=2):
+    return f"{r['median'] * scale:.{digits}f} ({r['min'] * scale:.{digits}f} .. {r['max'] * scale:.{digits}f})"
+
+
+def seeded(net, seed):
+    with torch.no_grad():
+        for i, p in enumerate(net.parameters()):
+            p.copy_(torch.randn(p.shape, generator=torch.Generator().manual_seed(100 * seed + i)) * (0.05 if p.dim() > 1 else 1.0))
+    return net
+
+
+def step_of(net, x, gs):
+    params = [p for p in net.parameters()]
+    return lambda: torch.autograd.grad(net(x), [x] + params if x.requires_grad else params, gs, allow_unused=True)
+
+
+def bench_blocks(args, encoders, has_fused):
+    from tests.encoder_golden import ConvBlock
+    cl = torch.channels_last
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rows = []
+    for cin, cout in ((256, 256), (128, 256)):
+        for hw in (64, 16):
+            plain = seeded(ConvBlock(cin, cout), 3).cuda()
+            native, fused = copy.deepcopy(plain), copy.deepcopy(plain)
+            assert encoders.install_native_blocks(native)[0] == [""]
+            x = torch.randn(args.views, cin, hw, hw, device="cuda", generator=gen).contiguous(memory_format=cl).requires_grad_(True)
+            g = torch.randn(args.views, cout, hw, hw, device="cuda", generator=gen).contiguous(memory_format=cl)
+            arms = [("untouched module", step_of(plain, x, [g])), ("install_native_blocks()", step_of(native, x, [g]))]
+            if has_fused:
+                assert encoders.install_native_blocks(fused, fused=True)[0] == [""]
+                arms.append(("install_native_blocks(fused=True)", step_of(fused, x, [g])))
+            rows.append(dict(block=f"ConvBlock({cin}, {cout})", size=f"{hw}x{hw}", us={n: {k: v * 1000.0 for k, v in r.items()}
+                                                                                     for n, r in alternate(arms, args.reps, args.inner).items()}))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def bench_net(args, encoders, has_fused):
+    from tests import encoder_golden as eg
+    cl = torch.channels_last
+    hw = args.size >> 1
+    plain = eg.stand_in_geo(1).train().cuda()
+    nets = [("untouched module", plain), ("install_native_geo()", copy.deepcopy(plain))]
+    encoders.install_native_geo(nets[1][1])
+    if has_fused:
+        nets.append(("install_native_geo(fused_blocks=True)", copy.deepcopy(plain)))
+        report = encoders.install_native_geo(nets[2][1], fused_blocks=True)
+        assert not any(left for _, left in report.values()), report
+    x = eg.net_input(eg.case_image((args.views, 3, args.size, args.size), 1).cuda(), 1).contiguous(memory_format=cl)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    gs = [torch.randn(args.views, 64, hw // 4, hw // 4, device="cuda", generator=gen).contiguous(memory_format=cl),
+          torch.randn(args.views, 8, hw, hw, device="cuda", generator=gen).contiguous(memory_format=cl)]
+    arms = [(n, step_of(net, x, gs)) for n, net in nets]
+    times = alternate(arms, args.reps, 1)
+    memory = {}
+    for n, fn in arms:
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        out = fn()
+        torch.cuda.synchronize()
+        memory[n] = dict(peak_above_base_mib=(torch.cuda.max_memory_allocated() - base) / 2**20, base_mib=base / 2**20)
+        del out
+    return dict(net=f"HGFilterV2, {args.views} x 3 x {hw}^2 input", ms=times, memory=memory)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--views", type=int, default=3)
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--label", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_block_fused.py needs a GPU: a time measured anywhere else says nothing")
+    sys.path.insert(0, os.path.abspath(args.root))
+    from keypointnerf_amd import encoders
+    has_fused = "fused" in inspect.signature(encoders.install_native_blocks).parameters
+    label = args.label or os.path.abspath(args.root)
+    blocks = bench_blocks(args, encoders, has_fused)
+    net = bench_net(args, encoders, has_fused)
+    names = list(net["ms"])
+    lines = [f"Checkout: {label} ({'with' if has_fused else 'without'} the single-operator block); N = {args.views}; median (min .. max) over "
+             f"{args.reps} repetitions; the block rows use install_native_blocks in place of install_native_geo", "",
+             "| forward + backward | " + " | ".join(names) + " |", "|---|" + "---|" * len(names)]
+    for r in blocks:
+        lines.append(f"| {r['block']} at {r['size']} (us) | " + " | ".join(cell(v, digits=1) for v in r["us"].values()) + " |")
+    lines.append(f"| {net['net']} (ms) | " + " | ".join(cell(net["ms"][n]) for n in names) + " |")
+    lines.append("| peak memory of one step above parameters and inputs (MiB) | " + " | ".join(f"{net['memory'][n]['peak_above_base_mib']:.1f}" for n in names) + " |")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps({"bench": "block_fused", "label": label, "blocks": blocks, "net": net}))
+
+
+if __name__ == "__main__":
+    main()
