@@ -55,6 +55,9 @@ extern "C" {
 /* still 10: a whole ConvBlock as one differentiable operator (kpn_conv_block_desc, kpn_conv_block_params, kpn_conv_block_grads,
  * kpn_conv_block_workspace_bytes, kpn_conv_block_state_floats, kpn_conv_block_forward, kpn_conv_block_backward) is additive within 10
  * in the same way */
+/* still 10: a whole ResBlkEncoder as one differentiable operator (kpn_res_encoder_desc, kpn_res_encoder_layers,
+ * kpn_res_encoder_workspace_bytes, kpn_res_encoder_state_floats, kpn_res_encoder_packed_floats, kpn_res_encoder_pack_device,
+ * kpn_res_encoder_forward, kpn_res_encoder_backward) is additive within 10 in the same way */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -825,6 +828,53 @@ int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const float* x, cons
 int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
                             const float* state, float* dx, const kpn_conv_block_grads* grads, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A whole ResBlkEncoder(norm = "instance") (src/utils.py:199-259) for training, forward and backward, as one call each: replaces every
+ * ReplicationPad2d + Conv2d pair, stride-2 and transposed convolution, InstanceNorm2d [+ ReLU] and residual add, with their autograd.
+ * Layers, in module order (kpn_res_encoder_layers = 2 + n_down + 2 n_blocks + n_up of them): the 7x7 stem in_ch -> ngf, n_down
+ * Conv2d(k 3, stride 2, pad 1) doubling the width, two replication-padded 3x3 convolutions per ResBlk, n_up ConvTranspose2d(k 3,
+ * stride 2, pad 1, output_padding 1) halving it, the replication-padded 7x7 output layer -> out_ch.  Every convolution has a bias;
+ * every layer but the last has an InstanceNorm2d(affine = False) behind it.
+ * x is the NCHW image (N, in_ch, H, W), read as it is (KPN_RP_STEM7); y, dy are NHWC (N, H >> (n_down - n_up), W >> (n_down - n_up),
+ * out_ch), dense, fp32.
+ * Scope: in_ch in 1 .. 4; ngf a power of two >= 4 with ngf << n_down <= 1024; 1 <= n_up <= n_down; n_blocks in 0 .. 64; out_ch a multiple
+ * of 4 in 4 .. 1024; N in 1 .. 65535; H and W divisible by 2^n_down; every layer's input and output below 2^31 elements; eps > 0; every
+ * pointer but x 16-byte aligned.  Anything else is refused with KPN_EINVAL (the size queries return 0), kpn_last_error() names the field,
+ * and nothing is launched.  Kernels: csrc/encoder_kernels.hip; dataflow: csrc/api_tex_train.hip.
+ *   packed (kpn_res_encoder_packed_floats / _pack_device; they read only in_ch .. out_ch): per layer, in order, what the layer's own
+ *            packer writes (kpn_conv2d_rp_pack_device / kpn_conv2d_s2_pack_device): the forward copy, then (not for the stem) the
+ *            input-gradient copy.  weights[i]: the plain weight of layer i as the module holds it (OIHW; IOHW for a transposed layer).
+ *   forward: the dataflow of kpn_tex_encode with nothing released - InstanceNorm statistics only, scale / shift and the ReLU applied
+ *            inside the loads of the next convolution; a normalised tensor exists only where a residual needs it: a_0 = relu(norm(c)) in
+ *            front of the first ResBlk and a_k = norm(c2) + a_{k-1} behind ResBlk k.  bias[i]: the bias of layer i.  y has the bits of the
+ *            same encoder computed layer by layer (kpn_conv2d_rp_forward, kpn_conv2d_s2_forward, kpn_group_norm_forward, one fp32 add
+ *            per ResBlk).
+ *   state (kpn_res_encoder_state_floats = sum numel(c_i) + sum numel(a_k) + 4 N sum C_norm; written by the forward, read by the
+ *            backward): the output c_i (NHWC) of every layer but the last, in order; then a_0 .. a_{n_blocks}; then, per layer but the
+ *            last, scale [N][C], shift [N][C], mean [N][C], rstd [N][C] of the norm behind it.  No normalised tensor of a non-residual
+ *            layer, no padded tensor.
+ *   backward: dw[i] (the layout of weights[i]) and db[i] per layer, each of which may be NULL: nothing is written for a NULL result,
+ *            and the walk ends at the lowest layer whose dw is wanted.  Results are overwritten, not accumulated.  There is no dx (the
+ *            stem has no input gradient).  db[i] of every layer but the last is written as exact zeros and nothing is reduced for it: a
+ *            bias in front of an InstanceNorm2d without parameters does not reach the output (IN(c + b) = IN(c)), where torch returns
+ *            rounding noise.  db of the output layer is the sum of dy over the pixels.  Every layer's gradients are those of its own
+ *            kpn_conv2d_*_backward and kpn_group_norm_backward, the norm and the ReLU recomputed in the loads of the weight gradient.
+ * `workspace` (kpn_res_encoder_workspace_bytes; 0 = unsupported descriptor) serves the forward and the backward alike.
+ * No float atomics: every result is bit-identical from run to run, and an image's y does not depend on its batch. */
+typedef struct kpn_res_encoder_desc {
+    int32_t N, H, W, in_ch, ngf, n_down, n_blocks, n_up, out_ch;
+    float eps;
+} kpn_res_encoder_desc;
+int32_t kpn_res_encoder_layers(const kpn_res_encoder_desc* desc);
+size_t kpn_res_encoder_workspace_bytes(const kpn_res_encoder_desc* desc);
+size_t kpn_res_encoder_state_floats(const kpn_res_encoder_desc* desc);
+size_t kpn_res_encoder_packed_floats(const kpn_res_encoder_desc* desc);
+int kpn_res_encoder_pack_device(const kpn_res_encoder_desc* desc, const float* const* weights, float* packed, void* stream);
+int kpn_res_encoder_forward(const kpn_res_encoder_desc* desc, const float* x, const float* packed, const float* const* bias, float* y,
+                            float* state, void* workspace, size_t workspace_bytes, void* stream);
+int kpn_res_encoder_backward(const kpn_res_encoder_desc* desc, const float* x, const float* dy, const float* packed, const float* state,
+                             float* const* dw, float* const* db, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -101,12 +101,13 @@ inline WgradPlan wgrad_plan(const ConvGeom& g) {
     return p;
 }
 // `c`: g.a with the source of A filled in (Hs, Ws, stride, pad, src, src_cs; the stem's Hraw, Wraw, stem_plain; ss and relu_in = 1 for
-// a norm fused into the loads); rhs (g.M, cout) with channel stride rhs_cs
+// a norm fused into the loads); rhs (g.M, cout) with channel stride rhs_cs; rhs_ss: the scale / shift of a norm + ReLU fused into the
+// loads of rhs, or NULL
 inline void launch_wgrad(const kpn_enc_conv_args& c, const ConvGeom& g, const WgradPlan& p, int stem, const float* rhs, int rhs_cs,
-                         float* partial, float* dw, void* stream) {
+                         float* partial, float* dw, void* stream, const float* rhs_ss = nullptr) {
     kpn_enc_wgrad_args a{};
     a.c = c;
-    a.rhs = rhs; a.rhs_cs = rhs_cs; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
+    a.rhs = rhs; a.rhs_cs = rhs_cs; a.rhs_ss = rhs_ss; a.rhs_relu = rhs_ss != nullptr; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
     a.partial = partial; a.dw = dw;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.nranges);
     if (stem) {

@@ -670,6 +670,9 @@ struct kpn_enc_wgrad_args {
                                // shift)) computed in the loads from the un-normalised source (the legs of api_block.hip); else ss = NULL
     const float* rhs;          // R: NHWC (nimg, Ho, Wo, cout) with channel stride rhs_cs (cout for a dense tensor)
     int rhs_cs;
+    const float* rhs_ss;       // scale [nimg][cout] then shift [nimg][cout] of R, or NULL: R is [relu](fmaf(rhs, scale, shift)) computed in
+    int rhs_relu;              // its loads (the transposed layers of api_tex_train.hip, whose swapped roles make R the layer's lazily
+                               // normalised input); NULL: rhs is loaded as it is
     int krows;                 // kh * kw * cin: the real rows
     int nchunks, cpr, nranges; // 16-pixel chunks in all / per range; ranges (gridDim.y)
     float* partial;            // [range][krows][cout]
@@ -708,7 +711,17 @@ __global__ __launch_bounds__(256) void k_enc_wgrad(kpn_enc_wgrad_args a) {
         if (bload) {
             const int64_t p = (int64_t)s * 16 + bp;
             rb = kpn_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (p < M && bco < a.c.cout) rb = *KPN_GLOBAL4(a.rhs + (size_t)p * a.rhs_cs + bco);
+            if (p < M && bco < a.c.cout) {
+                rb = *KPN_GLOBAL4(a.rhs + (size_t)p * a.rhs_cs + bco);
+                if (a.rhs_ss) {
+                    const size_t n = (size_t)(p / hw);          // the image of the pixel
+                    const kpn_f32x4 sc = *KPN_GLOBAL4(a.rhs_ss + n * a.c.cout + bco);
+                    const kpn_f32x4 sh = *KPN_GLOBAL4(a.rhs_ss + ((size_t)a.c.nimg + n) * a.c.cout + bco);
+                    for (int e = 0; e < 4; ++e) rb[e] = fmaf(rb[e], sc[e], sh[e]);
+                    if (a.rhs_relu)
+                        for (int e = 0; e < 4; ++e) rb[e] = rb[e] > 0.0f ? rb[e] : 0.0f;
+                }
+            }
         }
     };
     const int wn = wave % (BN / 32), wm = wave / (BN / 32);

@@ -51,6 +51,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "api_reppad.hip"
 #include "api_norm.hip"
 #include "api_block.hip"
+#include "api_tex_train.hip"
 #include "api_resample.hip"
 #include "api_params.hip"
 

@@ -26,7 +26,7 @@ are independent: they rebind different modules, so they compose and uninstall in
 five to every HGFilterV2 and rebinds its forward so that the functional calls in it run on the project's kernels too.
 ``install_native_tex`` does the same for every ResBlkEncoder: ``install_native_strided`` and ``install_native_norms`` on its subtree,
 and a forward that runs every ReplicationPad2d + Conv2d pair as torch.ops.kpnerf.conv2d_replicate and every InstanceNorm2d + ReLU
-pair as one fused torch.ops.kpnerf.group_norm.
+pair as one fused torch.ops.kpnerf.group_norm; with ``fused=True`` the forward is one torch.ops.kpnerf.res_encoder call instead.
 """
 import types
 
@@ -416,6 +416,7 @@ class NativeTraining:
     strided_calls = 0
     geo_calls = 0
     tex_calls = 0
+    fused_tex_calls = 0
 
 
 def _pow2_channels(C):
@@ -778,9 +779,8 @@ def uninstall_native_geo(module):
 
 
 # ---- a whole ResBlkEncoder natively: the replication-padded convolutions, the fused norms and the two installers its other layers need ----
-def _tex_ineligible(m, name):
-    """None if this ResBlkEncoder has the reference's structure (src/utils.py:199-259, norm = "instance": the check the native encoder
-    makes) and every one of its layers is served by its kernel, else the reason it is left alone"""
+def _tex_structure_error(m):
+    """None if this ResBlkEncoder has the reference's structure (the check of ``tex_params``, with an output layer), else the reason"""
     L = list(getattr(m, "layers", ()))
     if len(L) < 2 or type(L[-1]) is not torch.nn.Conv2d or type(L[-2]) is not torch.nn.ReplicationPad2d:
         return (f"layers.{len(L) - 1}: {type(L[-1]).__name__ if L else 'nothing'} where the output layer ReplicationPad2d(3) + Conv2d(k 7) "
@@ -789,6 +789,16 @@ def _tex_ineligible(m, name):
         tex_params(m)
     except NotImplementedError as e:
         return str(e)
+    return None
+
+
+def _tex_ineligible(m, name):
+    """None if this ResBlkEncoder has the reference's structure (src/utils.py:199-259, norm = "instance": the check the native encoder
+    makes) and every one of its layers is served by its kernel, else the reason it is left alone"""
+    why = _tex_structure_error(m)
+    if why is not None:
+        return why
+    L = list(m.layers)
     for n, sub in m.named_modules():
         if type(sub) is torch.nn.InstanceNorm2d:
             why = _norm_ineligible(sub)
@@ -813,7 +823,20 @@ def _tex_ineligible(m, name):
 _TEX_PARTS = ("strided", "norms")
 
 
-def install_native_tex(module):
+def _fused_tex_plan(m):
+    """(convolutions in module order, n_down, n_blocks, n_up, eps) if kpn_res_encoder_* serves this ResBlkEncoder (one that
+    _tex_ineligible has passed), else the reason it stays on the per-layer path"""
+    _, (ngf, n_down, n_blocks, n_up, out_ch), eps = tex_params(m)
+    convs = [c for c in m.modules() if type(c) in (torch.nn.Conv2d, torch.nn.ConvTranspose2d)]
+    if any(c.bias is None for c in convs):
+        return "a convolution without bias"
+    why = ops.res_encoder_refusal(convs[0].in_channels, (ngf, n_down, n_blocks, n_up, out_ch))
+    if why is not None:
+        return f"the single-operator encoder does not serve it: {why}"
+    return convs, n_down, n_blocks, n_up, eps
+
+
+def install_native_tex(module, fused=False):
     """Opt-in: trains every ResBlkEncoder under ``module`` (``module`` itself included) on the project's kernels.  A ResBlkEncoder whose
     structure is the reference's (src/utils.py:199-259 with ``norm="instance"`` and ``n_upsample`` >= 1: the check of ``tex_params``),
     whose norms have a power of two in 4 .. 1024 channels, whose ``out_ch`` is a multiple of 4 and whose convolutions their kernels
@@ -824,7 +847,15 @@ def install_native_tex(module):
     Input that is not a CUDA fp32 (N, 3, H, W) tensor with H and W divisible by 2^n_downsample, or that requires a gradient (the stem
     has no native input gradient), goes to the original forward.  An encoder that fails a check is left alone with its reason, not
     refused.  The module tree, the parameter names and the state_dict are untouched.  Returns {"tex": (served, left), "strided": ...,
-    "norms": ...}, the names relative to ``module``."""
+    "norms": ...}, the names relative to ``module``.
+
+    ``fused=True``: the rebound forward of every encoder of the reference's structure that kpn_res_encoder_* serves (whether or not the
+    per-layer kernels serve each of its layers) is one torch.ops.kpnerf.res_encoder call instead (kpn_res_encoder_forward / _backward): one autograd node per encoder and no aten operator inside it - the norms and the
+    ReLUs run in the loads of the convolutions, forward and backward, the residual adds in the kernels - with x, the convolution outputs
+    and the ResBlk sums kept for the backward instead of every layer's input and normalised input.  Its forward has the bits of the
+    per-layer path.  Such an encoder needs neither of the two installers on its subtree and gets neither.  An encoder that the
+    operator does not serve stays on the per-layer path, if that serves it; the report gains "fused": (the names on the operator, {name: reason} of those
+    left on the per-layer path).  ``NativeTraining.fused_tex_calls`` counts the operator's calls (``tex_calls`` the per-layer ones)."""
     def make_forward(_prev):
         def forward(self, x):
             nn = torch.nn
@@ -833,6 +864,11 @@ def install_native_tex(module):
             if (not _native_input(x, *self.parameters()) or x.shape[1] != 3 or x.shape[2] % f or x.shape[3] % f
                     or (x.requires_grad and torch.is_grad_enabled())):
                 return _prev(x)
+            plan = self.__dict__.get("_kpnerf_tex_fused")
+            if plan is not None:
+                NativeTraining.fused_tex_calls += 1
+                convs, n_down, n_blocks, n_up, eps = plan
+                return torch.ops.kpnerf.res_encoder(x, [t for c in convs for t in (c.weight, c.bias)], n_down, n_blocks, n_up, eps)
             NativeTraining.tex_calls += 1
 
             def rp(t, conv):
@@ -858,10 +894,31 @@ def install_native_tex(module):
         return forward
 
     uninstall_native_tex(module)
-    served, left = _rebind_forward(module, "_kpnerf_tex_saved", lambda m: type(m).__name__ == "ResBlkEncoder", _tex_ineligible, make_forward)
+    plans = {}
+
+    def ineligible(m, name):
+        # the operator first: it serves an encoder whatever the per-layer kernels say of its layers
+        if fused:
+            why = _tex_structure_error(m)
+            if why is not None:
+                return why
+            plans[name] = _fused_tex_plan(m)
+            if not isinstance(plans[name], str):
+                return None
+        return _tex_ineligible(m, name)
+
+    served, left = _rebind_forward(module, "_kpnerf_tex_saved", lambda m: type(m).__name__ == "ResBlkEncoder", ineligible, make_forward)
     report = {k: ([], {}) for k in _TEX_PARTS}
     subs = dict(module.named_modules())
+    if fused:
+        report["fused"] = ([], {})
     for name in served:
+        if fused:
+            if not isinstance(plans[name], str):
+                subs[name]._kpnerf_tex_fused = plans[name]
+                report["fused"][0].append(name)
+                continue
+            report["fused"][1][name] = plans[name]
         for part, fn in zip(_TEX_PARTS, (install_native_strided, install_native_norms)):
             s_, l_ = fn(subs[name])
             pre = name + "." if name else ""
@@ -876,6 +933,7 @@ def uninstall_native_tex(module):
     subtree: no attribute it added is left."""
     for m in module.modules():
         if "_kpnerf_tex_saved" in m.__dict__:
+            m.__dict__.pop("_kpnerf_tex_fused", None)
             for undo in (uninstall_native_strided, uninstall_native_norms):
                 undo(m)
     return _restore_forward(module, "_kpnerf_tex_saved")

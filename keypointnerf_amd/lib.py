@@ -122,6 +122,11 @@ class ConvBlockGrads(ctypes.Structure):
     _fields_ = [("dgamma", c_p * 4), ("dbeta", c_p * 4), ("dw", c_p * 4)]
 
 
+class ResEncoderDesc(ctypes.Structure):
+    """struct kpn_res_encoder_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "in_ch", "ngf", "n_down", "n_blocks", "n_up", "out_ch")] + [("eps", c_f)]
+
+
 class ResampleDesc(ctypes.Structure):
     """struct kpn_resample2_desc"""
     _fields_ = [(n, c_i32) for n in ("N", "h", "w", "C")]
@@ -250,6 +255,14 @@ _SIGNATURES = {
     "kpn_conv_block_forward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv_block_backward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p,
                                                ctypes.POINTER(ConvBlockGrads), c_p, c_sz, c_p]),
+    "kpn_res_encoder_layers": (c_i32, [ctypes.POINTER(ResEncoderDesc)]),
+    "kpn_res_encoder_workspace_bytes": (c_sz, [ctypes.POINTER(ResEncoderDesc)]),
+    "kpn_res_encoder_state_floats": (c_sz, [ctypes.POINTER(ResEncoderDesc)]),
+    "kpn_res_encoder_packed_floats": (c_sz, [ctypes.POINTER(ResEncoderDesc)]),
+    "kpn_res_encoder_pack_device": (ctypes.c_int, [ctypes.POINTER(ResEncoderDesc), ctypes.POINTER(c_p), c_p, c_p]),
+    "kpn_res_encoder_forward": (ctypes.c_int, [ctypes.POINTER(ResEncoderDesc), c_p, c_p, ctypes.POINTER(c_p), c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_res_encoder_backward": (ctypes.c_int, [ctypes.POINTER(ResEncoderDesc), c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
+                                                c_p, c_sz, c_p]),
     "kpn_avg_pool2_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_avg_pool2_backward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_upsample2x_add_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p, c_p]),

@@ -1364,6 +1364,135 @@ def conv_block_backward(x, dy, norms, packed, state, eps, want_dx=True, want=Non
 
 
 # ------------------------------------------------------------------------------------------------
+# A whole ResBlkEncoder and its parameter gradients as one call each (kpn_res_encoder_*; reference src/utils.py:199-259,
+# norm = "instance").  x is the contiguous NCHW image, read as it is; y is a channels_last tensor of logical shape (N, out_ch, Ho, Wo).
+# ``cfg`` is (ngf, n_down, n_blocks, n_up, out_ch); the layers are the convolutions in module order: the stem, the stride-2 layers, two
+# per ResBlk, the transposed layers, the output layer.
+_RES_ENCODER_WORKSPACE = ("kpn_res_encoder_workspace_bytes", "kpn_res_encoder_forward", "res_encoder: unsupported encoder")
+
+
+def _res_encoder_desc(N, H, W, in_ch, cfg, eps):
+    d = kl.ResEncoderDesc()
+    d.N, d.H, d.W, d.in_ch, d.eps = int(N), int(H), int(W), int(in_ch), float(eps)
+    d.ngf, d.n_down, d.n_blocks, d.n_up, d.out_ch = (int(v) for v in cfg)
+    return d
+
+
+def res_encoder_supported(in_ch, cfg, N=1, H=None, W=None):
+    """whether kpn_res_encoder_* serves an encoder of this configuration (and, when given, of this input size)"""
+    return res_encoder_refusal(in_ch, cfg, N, H, W) is None
+
+
+def res_encoder_refusal(in_ch, cfg, N=1, H=None, W=None):
+    """None if kpn_res_encoder_* serves the encoder, else the library's reason"""
+    L = kl.get_library()
+    f = 1 << max(0, min(int(cfg[1]), 16))
+    d = _res_encoder_desc(N, f if H is None else H, f if W is None else W, in_ch, cfg, 1e-5)
+    if L.kpn_res_encoder_workspace_bytes(ctypes.byref(d)) > 0:
+        return None
+    L.kpn_res_encoder_forward(ctypes.byref(d), None, None, None, None, None, None, 0, None)
+    return L.kpn_last_error().decode()
+
+
+def _pointer_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def res_encoder_layer_shapes(in_ch, cfg):
+    """[(weight shape, bias length)] of the layers in module order"""
+    ngf, n_down, n_blocks, n_up, out_ch = (int(v) for v in cfg)
+    out, C = [((ngf, in_ch, 7, 7), ngf)], ngf
+    for _ in range(n_down):
+        out.append(((2 * C, C, 3, 3), 2 * C))
+        C *= 2
+    out += [((C, C, 3, 3), C)] * (2 * n_blocks)
+    for _ in range(n_up):
+        out.append(((C, C // 2, 3, 3), C // 2))        # ConvTranspose2d: (cin, cout, k, k)
+        C //= 2
+    out.append(((out_ch, C, 7, 7), out_ch))
+    return out
+
+
+def _res_encoder_vectors(tensors, in_ch, cfg, what):
+    shapes = res_encoder_layer_shapes(in_ch, cfg)
+    if len(tensors) != len(shapes):
+        raise ValueError(f"res_encoder: {len(shapes)} layers, got {len(tensors)} {what}")
+    return shapes
+
+
+def res_encoder_pack(weights, in_ch, cfg):
+    """The packed weights of every layer in one buffer (kpn_res_encoder_pack_device): per layer what its own packer gives
+    (conv2d_rp_pack / conv2d_s2_pack)."""
+    L = kl.get_library()
+    shapes = _res_encoder_vectors(weights, in_ch, cfg, "weights")
+    ws = [_conv_weight(w.detach()) for w in weights]
+    for i, (w, (shape, _)) in enumerate(zip(ws, shapes)):
+        if tuple(w.shape) != shape:
+            raise ValueError(f"res_encoder: the weight of layer {i} must be {shape}, got {tuple(w.shape)}")
+    d = _res_encoder_desc(1, 1 << int(cfg[1]), 1 << int(cfg[1]), in_ch, cfg, 1e-5)
+    n = _desc_size(L, d, "kpn_res_encoder_packed_floats", "kpn_res_encoder_pack_device", "res_encoder: unsupported encoder")
+    packed = torch.empty(n, dtype=_f32, device=ws[0].device)
+    L.check(L.kpn_res_encoder_pack_device(ctypes.byref(d), _pointer_array(ws), _p(packed), _stream()))
+    return packed
+
+
+def _res_encoder_x(x):
+    x = _dev(x, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"x must be a contiguous NCHW (N, C, H, W) tensor, got {tuple(x.shape)}")
+    return x
+
+
+def res_encoder_forward(x, packed, biases, cfg, eps):
+    """ResBlkEncoder(x) for packed = res_encoder_pack(weights, ...) and the layers' biases (kpn_res_encoder_forward).  x: contiguous NCHW
+    (N, in_ch, H, W).  Returns (y (N, out_ch, Ho, Wo) channels_last, state): state holds every convolution output, every a_k and every
+    norm's statistics, which res_encoder_backward reads."""
+    L = kl.get_library()
+    x = _res_encoder_x(x)
+    N, in_ch, H, W = x.shape
+    shapes = _res_encoder_vectors(biases, in_ch, cfg, "biases")
+    d = _res_encoder_desc(N, H, W, in_ch, cfg, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_RES_ENCODER_WORKSPACE)
+    if packed.numel() != L.kpn_res_encoder_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError("packed does not belong to this encoder (res_encoder_pack)")
+    bs = [_norm_vec(b, f"bias of layer {i}", n) for i, (b, (_, n)) in enumerate(zip(biases, shapes))]
+    f = int(cfg[1]) - int(cfg[3])
+    y = torch.empty(N, H >> f, W >> f, int(cfg[4]), dtype=_f32, device=x.device)
+    state = torch.empty(L.kpn_res_encoder_state_floats(ctypes.byref(d)), dtype=_f32, device=x.device)
+    L.check(L.kpn_res_encoder_forward(ctypes.byref(d), _p(x), _p(packed), _pointer_array(bs), _p(y), _p(state), _p(ws), nb, _stream()))
+    return y.permute(0, 3, 1, 2), state
+
+
+def res_encoder_backward(x, dy, packed, state, cfg, eps, want=None):
+    """[(dw, db)] per layer of res_encoder_forward for the output gradient dy (N, out_ch, Ho, Wo) channels_last
+    (kpn_res_encoder_backward).  ``want`` is [(dw, db) wanted] per layer (default: all); what is not wanted is None, and the layers below
+    the lowest wanted weight gradient are not walked.  The db of every layer but the last is exactly zero (a bias in front of an
+    InstanceNorm2d without parameters does not reach the output)."""
+    L = kl.get_library()
+    x, dy = _res_encoder_x(x), _channels_last(dy, "dy")
+    N, in_ch, H, W = x.shape
+    shapes = res_encoder_layer_shapes(in_ch, cfg)
+    want = [(True, True)] * len(shapes) if want is None else want
+    if len(want) != len(shapes):
+        raise ValueError(f"res_encoder: {len(shapes)} layers, got {len(want)} entries of want")
+    f = int(cfg[1]) - int(cfg[3])
+    if tuple(dy.shape) != (N, int(cfg[4]), H >> f, W >> f):
+        raise ValueError(f"dy must be {(N, int(cfg[4]), H >> f, W >> f)}, got {tuple(dy.shape)}")
+    d = _res_encoder_desc(N, H, W, in_ch, cfg, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_RES_ENCODER_WORKSPACE)
+    if packed.numel() != L.kpn_res_encoder_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError("packed does not belong to this encoder (res_encoder_pack)")
+    if state.numel() != L.kpn_res_encoder_state_floats(ctypes.byref(d)) or state.dtype != _f32 or state.device != x.device:
+        raise ValueError("state does not belong to this encoder (res_encoder_forward)")
+    new = lambda *shape: torch.empty(*shape, dtype=_f32, device=x.device)  # noqa: E731
+    out = [(new(*shape) if w_[0] else None, new(n) if w_[1] else None) for (shape, n), w_ in zip(shapes, want)]
+    if any(any(w_) for w_ in want):
+        L.check(L.kpn_res_encoder_backward(ctypes.byref(d), _p(x), _p(dy), _p(packed), _p(state.contiguous()), _pointer_array([o[0] for o in out]),
+                                           _pointer_array([o[1] for o in out]), _p(ws), nb, _stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # The two resampling steps of an HourGlass and their gradients (kpn_avg_pool2_* / kpn_upsample2x_add_*; avg_pool2d(x, 2, stride=2)
 # and skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) with their autograd, reference
 # src/utils.py:287-306).  Activations are channels_last tensors of logical shape (N, C, H, W).

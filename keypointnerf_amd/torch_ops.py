@@ -47,6 +47,10 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
                                  [bn1.weight, bn1.bias, conv1.weight, ... bn3 ..., conv3.weight (, bn4.weight, bn4.bias, downsample
                                  weight)]; channels-last result, DIFFERENTIABLE w.r.t. x and every tensor (kpn_conv_block_forward /
                                  _backward); keeps x and 3/4 of a y-sized tensor for the backward, never y or a normalised tensor
+    torch.ops.kpnerf.res_encoder(x, tensors, n_down, n_blocks, n_up, eps) -> y   a whole ResBlkEncoder(norm="instance") as ONE autograd
+                                 node: tensors = [weight, bias] per convolution in module order; x is the NCHW image; channels-last
+                                 result, DIFFERENTIABLE w.r.t. every tensor, not x (kpn_res_encoder_forward / _backward); keeps x, the
+                                 convolution outputs and the ResBlk sums for the backward, never a normalised or padded tensor
     torch.ops.kpnerf.avg_pool2(x) -> y   avg_pool2d(x, 2, stride=2) (C a multiple of 4, even H and W), channels-last result,
                                  DIFFERENTIABLE w.r.t. x (kpn_avg_pool2_forward / _backward)
     torch.ops.kpnerf.upsample2x_add(low, skip?) -> y   skip + bicubic x2 of low (align_corners=True; C a multiple of 4), channels-last
@@ -974,6 +978,135 @@ def _conv_block(x, tensors, eps):
 
 _fragment.define("conv_block(Tensor x, Tensor[] tensors, float eps) -> Tensor")
 _fragment.impl("conv_block", _conv_block, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.res_encoder: a whole ResBlkEncoder, DIFFERENTIABLE w.r.t. every parameter, one autograd node ----
+# tensors: [weight, bias] per convolution in module order - the stem, the stride-2 layers, two per ResBlk, the transposed layers, the
+# output layer.  The packed copies of all weights are one buffer, packed once per parameter version (the key is _tensor_key of every
+# weight, as in the cache of kpnerf::conv2d).  The backward reads x, `state` (every convolution output, every a_k and every norm's
+# statistics) and the packed weights; it never reads y.  There is no input gradient: an x that requires one raises.
+def _res_cfg(tensors, n_down, n_blocks, n_up):
+    n = 2 + n_down + 2 * n_blocks + n_up
+    if len(tensors) != 2 * n or n_down < 0 or n_blocks < 0 or n_up < 0:
+        raise ValueError(f"res_encoder takes [weight, bias] for each of its {n} convolutions, got {len(tensors)} tensors")
+    return (tensors[0].shape[0], n_down, n_blocks, n_up, tensors[-2].shape[0])
+
+
+def _res_state_floats(N, H, W, in_ch, cfg):
+    """kpn_res_encoder_state_floats, restated for the fake kernels"""
+    shapes = ops.res_encoder_layer_shapes(in_ch, cfg)[:-1]
+    total, h, w = 0, H, W
+    for i, (_, C) in enumerate(shapes):
+        if 1 <= i <= cfg[1]:
+            h, w = h // 2, w // 2
+        elif i > cfg[1] + 2 * cfg[2]:
+            h, w = 2 * h, 2 * w
+        total += N * h * w * C + 4 * N * C
+    f = 1 << cfg[1]
+    return total + (cfg[2] + 1) * N * (H // f) * (W // f) * (cfg[0] * f)
+
+
+class _ResPackCache:
+    lock = threading.Lock()
+    entries = collections.OrderedDict()     # data_ptr of the stem's weight -> (key, weights, packed)
+    limit = 16
+    hits = misses = 0                       # observable by the tests
+
+
+def res_encoder_cache_clear():
+    with _ResPackCache.lock:
+        _ResPackCache.entries.clear()
+
+
+def _res_packed(weights, in_ch, cfg):
+    if any(w.is_inference() for w in weights):
+        return ops.res_encoder_pack(weights, in_ch, cfg)
+    key = tuple(_tensor_key(w) for w in weights) + (tuple(cfg),)
+    C = _ResPackCache
+    with C.lock:
+        e = C.entries.get(key[0][0])
+        if e is not None and e[0] == key:
+            C.entries.move_to_end(key[0][0])
+            C.hits += 1
+            return e[2]
+    packed = ops.res_encoder_pack(weights, in_ch, cfg)
+    with C.lock:
+        C.misses += 1
+        C.entries[key[0][0]] = (key, list(weights), packed)
+        C.entries.move_to_end(key[0][0])
+        while len(C.entries) > C.limit:
+            C.entries.popitem(last=False)
+    return packed
+
+
+@_lib.custom_op("kpnerf::res_encoder_cl", mutates_args=(), device_types="cuda")
+def res_encoder_cl(x: torch.Tensor, tensors: List[torch.Tensor], n_down: int, n_blocks: int, n_up: int,
+                   eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, state) of a ResBlkEncoder for a contiguous NCHW x (kpn_res_encoder_forward): what torch.ops.kpnerf.res_encoder runs after its
+    memory-format conversion.  y is (N, out_ch, H >> (n_down - n_up), W >> (n_down - n_up)) channels_last; state is the side buffer of the
+    backward."""
+    cfg = _res_cfg(tensors, n_down, n_blocks, n_up)
+    return ops.res_encoder_forward(x, _res_packed(tensors[0::2], x.shape[1], cfg), tensors[1::2], cfg, eps)
+
+
+@res_encoder_cl.register_fake
+def _(x, tensors, n_down, n_blocks, n_up, eps):
+    cfg = _res_cfg(tensors, n_down, n_blocks, n_up)
+    N, in_ch, H, W = x.shape
+    f = n_down - n_up
+    return x.new_empty(N, H >> f, W >> f, cfg[4]).permute(0, 3, 1, 2), x.new_empty(_res_state_floats(N, H, W, in_ch, cfg))
+
+
+@_lib.custom_op("kpnerf::res_encoder_backward", mutates_args=(), device_types="cuda")
+def res_encoder_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: torch.Tensor, dy: torch.Tensor, n_down: int, n_blocks: int,
+                         n_up: int, eps: float, mask: List[bool]) -> List[torch.Tensor]:
+    """one gradient per tensor of kpnerf::res_encoder_cl for the output gradient dy (kpn_res_encoder_backward); mask has one flag per
+    tensor: what is not wanted is not computed and its result is an empty tensor."""
+    cfg = _res_cfg(tensors, n_down, n_blocks, n_up)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    want = [(bool(mask[2 * i]), bool(mask[2 * i + 1])) for i in range(len(tensors) // 2)]
+    grads = ops.res_encoder_backward(x, dy, _res_packed(tensors[0::2], x.shape[1], cfg), state, cfg, eps, want=want)
+    return list(_empty_for_none(dy, *[g for pair in grads for g in pair]))
+
+
+@res_encoder_backward.register_fake
+def _(x, tensors, state, dy, n_down, n_blocks, n_up, eps, mask):
+    # one empty tensor per gradient that is not wanted, as the operator returns them: no two results share memory
+    return [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask)]
+
+
+def _res_encoder_setup(ctx, inputs, output):
+    x, tensors, n_down, n_blocks, n_up, eps = inputs
+    if ctx.needs_input_grad[0]:
+        raise RuntimeError("kpnerf::res_encoder: the 7x7 stem has no input gradient (x.requires_grad is set)")
+    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
+    ctx.cfg = (n_down, n_blocks, n_up, eps)
+    ctx.set_materialize_grads(False)
+
+
+def _res_encoder_bwd(ctx, dy, _d_state):
+    x, state, *tensors = ctx.saved_tensors
+    none = (None, [None] * len(tensors), None, None, None, None)
+    if dy is None:
+        return none
+    mask = [bool(b) for b in ctx.needs_input_grad[1]]
+    if not any(mask):
+        return none
+    out = torch.ops.kpnerf.res_encoder_backward(x, list(tensors), state, dy, *ctx.cfg, mask)
+    return None, list(_none_unless(mask, *out)), None, None, None, None
+
+
+res_encoder_cl.register_autograd(_res_encoder_bwd, setup_context=_res_encoder_setup)
+
+
+# torch.ops.kpnerf.res_encoder(x, tensors, n_down, n_blocks, n_up, eps): x in any memory format, converted once to the contiguous NCHW
+# layout the stem reads as it is; the result is channels_last.
+def _res_encoder(x, tensors, n_down, n_blocks, n_up, eps):
+    return torch.ops.kpnerf.res_encoder_cl(x.contiguous(), tensors, n_down, n_blocks, n_up, eps)[0]
+
+
+_fragment.define("res_encoder(Tensor x, Tensor[] tensors, int n_down, int n_blocks, int n_up, float eps) -> Tensor")
+_fragment.impl("res_encoder", _res_encoder, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.avg_pool2 / upsample2x_add: the two resampling steps of an HourGlass, DIFFERENTIABLE ----

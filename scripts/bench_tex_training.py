@@ -11,8 +11,9 @@ layers:  the three replication-padded layers at the shipped widths (tests/encode
          a backward that yields every gradient the layer has (the stem: dW and db only, on both arms).
 adjoint: the input gradient alone, kpn_conv2d_rp_backward(KPN_RP_CONV3) against kpn_conv2d_backward(k 3, pad 1) at the same shapes: the
          same GEMM, only the loads of the outermost ring of pixels differ.
-net:     tests/encoder_golden.ResBlkEncoder with encoders.install_native_tex against the untouched module, on channels_last and on NCHW
-         tensors, forward + backward to every parameter gradient, and forward alone.
+net:     tests/encoder_golden.ResBlkEncoder with encoders.install_native_tex, and with install_native_tex(fused=True) (one
+         torch.ops.kpnerf.res_encoder per forward), against the untouched module, on channels_last and on NCHW tensors, forward + backward
+         to every parameter gradient, and forward alone; and each arm's peak memory above parameters and inputs over one training step.
 
 The arms alternate: each repetition times `inner` back-to-back calls of one arm between two device events, then the next arm; the
 figure is the median over the repetitions.  Run each mode under a time limit of its own.  Needs a GPU.
@@ -124,8 +125,10 @@ def bench_net(args):
     hw = args.size >> 1
     native = eg.stand_in_tex(1).train().cuda()
     plain = copy.deepcopy(native)                               # the untouched module
+    fused = copy.deepcopy(native)
     report = encoders.install_native_tex(native)
     left = {k: v[1] for k, v in report.items() if v[1]}
+    assert encoders.install_native_tex(fused, fused=True)["fused"] == ([""], {})
     x_nchw = eg.net_input(eg.case_image((args.views, 3, args.size, args.size), 1).cuda(), 1).contiguous()
     x = x_nchw.contiguous(memory_format=cl)
     a = eg.TEX_ARGS
@@ -142,16 +145,31 @@ def bench_net(args):
 
     arms = (("native (install_native_tex), channels_last tensors", native, x, g),
             ("native (install_native_tex), NCHW tensors", native, x_nchw, g_nchw),
+            ("native fused (install_native_tex(fused=True)), channels_last tensors", fused, x, g),
+            ("native fused (install_native_tex(fused=True)), NCHW tensors", fused, x_nchw, g_nchw),
             ("torch, untouched module, channels_last tensors", plain, x, g),
             ("torch, untouched module, NCHW tensors", plain, x_nchw, g_nchw))
-    calls = encoders.NativeTraining.tex_calls
+    calls = encoders.NativeTraining.tex_calls, encoders.NativeTraining.fused_tex_calls
     rows, lines = [], [f"| ResBlkEncoder, {args.views} x 3 x {hw}^2 input | " + " | ".join(a[0] + " (ms)" for a in arms) + " |", "|---|" + "---|" * len(arms)]
     for what, fn in (("forward + backward", step), ("forward alone (no_grad)", forward)):
         ms = alternate([lambda net=net, xx=xx, gg=gg: fn(net, xx, gg) for _, net, xx, gg in arms], args.reps, 1)
         rows.append(dict(what=what, ms={a[0]: dict(median=m[0] / 1000.0, min=m[1] / 1000.0, max=m[2] / 1000.0) for a, m in zip(arms, ms)}))
         lines.append(f"| {what} | " + " | ".join(cell(m, 1e-3, 2) for m in ms) + " |")
         print(lines[-1], flush=True)
-    assert encoders.NativeTraining.tex_calls > calls                    # the native arms were served natively
+    # peak memory of one training step above what is resident before it (parameters, inputs, the packed weights of earlier calls)
+    peaks = []
+    for _, net, xx, gg in arms:
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        grads = step(net, xx, gg)
+        torch.cuda.synchronize()
+        peaks.append((torch.cuda.max_memory_allocated() - base) / 2.0 ** 20)
+        del grads
+    rows.append(dict(what="peak memory of forward + backward (MiB)", mib={a[0]: p for a, p in zip(arms, peaks)}))
+    lines.append("| peak memory of forward + backward above parameters and inputs (MiB) | " + " | ".join(f"{p:.0f}" for p in peaks) + " |")
+    print(lines[-1], flush=True)
+    assert encoders.NativeTraining.tex_calls > calls[0] and encoders.NativeTraining.fused_tex_calls > calls[1]    # served natively
     lines.append(f"\nLayers left on torch by install_native_tex: {left or 'none'}.")
     return rows, lines
 
