@@ -104,8 +104,9 @@ def query(lib, hs, packed, pts, view, mode=0):
     return out, valid.astype(bool)
 
 
-def render(lib, hs, packed, cam_tar, bounds, grid, Sc, Sf, fine=True, chunk_rays=0, stages=False):
-    """grid = (x0, y0, step, nx, ny[, step_y]).  stages: -> (outputs, kpn_render_stages arrays in ray order)."""
+def render(lib, hs, packed, cam_tar, bounds, grid, Sc, Sf, fine=True, chunk_rays=0, stages=False, rows_kernel=None, fuse_kernel=None):
+    """grid = (x0, y0, step, nx, ny[, step_y]).  stages: -> (outputs, kpn_render_stages arrays in ray order).  rows_kernel / fuse_kernel:
+    the kernels of this call ("f32" / "bf16x3" / "f16x2", "f32" / "f16x2"; None = the process-wide selection), as ops.RenderPlan."""
     x0, y0, step, nx, ny = grid[:5]
     K, RT, b = f32(cam_tar["K"]).reshape(4, 4), f32(cam_tar["RT"]).reshape(4, 4), f32(bounds).reshape(2, 3)
     R = nx * ny
@@ -120,6 +121,8 @@ def render(lib, hs, packed, cam_tar, bounds, grid, Sc, Sf, fine=True, chunk_rays
     a.x0, a.y0, a.step, a.nx, a.ny = x0, y0, step, nx, ny
     a.step_y = grid[5] if len(grid) > 5 else 0
     a.n_coarse, a.n_fine, a.fine, a.chunk_rays = Sc, Sf, int(fine), chunk_rays
+    a.rows_kernel = {None: 0, "f32": 1, "bf16x3": 2, "f16x2": 3}[rows_kernel]
+    a.fuse_kernel = {None: 0, "f32": 1, "f16x2": 2}[fuse_kernel]
     for k, v in o.items():
         setattr(a, k, v.ctypes.data)
     st = None
