@@ -37,9 +37,8 @@ const char* desc_error(const kpn_conv_block_desc* d) {
 }
 // leg i: GroupNorm(min(32, cin), cin) + ReLU in the loads of a k x k convolution cin -> cout
 struct Leg {
-    int cin, cout, k, G, nchunks;
-    enc::ConvGeom fwd, dx;
-    enc::WgradPlan wg;
+    int cin, cout, G, nchunks;
+    enc::Layer e;               // the convolution (api_layer.hip): zero pad k / 2, k 3 or (the downsample leg) 1
     int64_t stat_doubles;
     size_t ss, mr;              // offsets (floats) in `state`
 };
@@ -62,17 +61,16 @@ Plan plan(const kpn_conv_block_desc* d) {
     size_t stat = 0, fconv = 0, bconv = 0, wg = 0, dn = 0, coef = 0;
     for (int i = 0; i < p.nlegs; ++i) {
         Leg& l = p.leg[i];
-        l.cin = cin[i]; l.cout = co[i]; l.k = i < 3 ? 3 : 1; l.G = std::min(32, l.cin);
-        l.fwd = enc::conv_geom(d->N, d->H, d->W, l.cin, l.cout, l.k, l.k, 0);
-        l.dx = enc::conv_geom(d->N, d->H, d->W, l.cout, l.cin, l.k, l.k, 0);
-        l.wg = enc::wgrad_plan(l.fwd);
+        const int k = i < 3 ? 3 : 1;
+        l.cin = cin[i]; l.cout = co[i]; l.G = std::min(32, l.cin);
+        l.e = enc::layer(enc::LayerSpec{l.cin, l.cout, k, 1, k / 2, 0, 0, 0}, d->N, d->H, d->W);
         l.nchunks = enc::stats_chunks(d->N, p.HW, l.cin, &l.stat_doubles);
         l.ss = st; st += (size_t)2 * d->N * l.cin;
         l.mr = st; st += (size_t)2 * d->N * l.G;
         stat = std::max(stat, (size_t)l.stat_doubles * sizeof(double));
-        fconv = std::max(fconv, (size_t)l.fwd.partial * sizeof(float));
-        bconv = std::max(bconv, (size_t)l.dx.partial * sizeof(float));
-        wg = std::max(wg, (size_t)l.wg.partial * sizeof(float));
+        fconv = std::max(fconv, (size_t)l.e.fwd.partial * sizeof(float));
+        bconv = std::max(bconv, (size_t)l.e.dx.partial * sizeof(float));
+        wg = std::max(wg, (size_t)l.e.wgp.partial * sizeof(float));
         dn = std::max(dn, (size_t)p.P * l.cin * sizeof(float));
         coef = std::max(coef, (size_t)3 * d->N * l.cin * sizeof(float));
     }
@@ -91,23 +89,6 @@ Plan plan(const kpn_conv_block_desc* d) {
     p.bytes = std::max<size_t>(std::max(f.o, b.o), 256);
     return p;
 }
-// dst = conv(src [normalised and rectified in the loads with ss], wp, pad) [+ res], every tensor with its own channel stride
-void conv(const enc::ConvGeom& g, int H, int W, int pad, const float* src, int src_cs, const float* ss, const float* wp, float* dst, int dst_cs,
-          const float* res, int res_cs, float* partial, void* stream) {
-    kpn_enc_conv_args a = g.a;
-    a.Hs = H; a.Ws = W; a.stride = 1; a.pad = pad;
-    a.src = src; a.src_cs = src_cs; a.ss = ss; a.relu_in = ss != nullptr;
-    a.wp = wp;
-    a.dst = dst; a.dst_cs = dst_cs;
-    a.res = res; a.res_cs = res_cs;
-    a.partial = g.partial ? partial : nullptr;
-    enc::launch_conv(a, g, 0, stream);
-}
-bool aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t u = 0;
-    for (const void* q : ps) u |= (uintptr_t)q;
-    return (u & 15) == 0;
-}
 }  // namespace blk
 
 #define KPN_BLOCK_REQUIRE_DESC(desc) do { if (const char* e_ = blk::desc_error(desc)) return fail(KPN_EINVAL, std::string("kpn_conv_block_desc: ") + e_); } while (0)
@@ -125,14 +106,18 @@ extern "C" int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const flo
     const blk::Plan p = blk::plan(desc);
     for (int i = 0; i < p.nlegs; ++i) {
         KPN_REQUIRE(params->gamma[i] && params->beta[i] && params->packed[i], "params: gamma / beta / packed of a leg is null");
-        KPN_REQUIRE(blk::aligned16({params->gamma[i], params->beta[i], params->packed[i]}), "params: gamma / beta / packed must be 16-byte aligned");
+        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->beta[i], params->packed[i]}), "params: gamma / beta / packed must be 16-byte aligned");
     }
-    KPN_REQUIRE(blk::aligned16({x, y, state, workspace}), "x / y / state / workspace must be 16-byte aligned");
+    KPN_REQUIRE(enc::aligned16({x, y, state, workspace}), "x / y / state / workspace must be 16-byte aligned");
     KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
     char* ws = static_cast<char*>(workspace);
     double* stat = reinterpret_cast<double*>(ws + p.f_stats);
     float* part = reinterpret_cast<float*>(ws + p.f_conv);
-    const int N = desc->N, H = desc->H, W = desc->W, c = desc->cout;
+    const int N = desc->N, c = desc->cout;
+    // leg i: dst = conv_i(src normalised and rectified in the loads with ss_i) [+ res], every tensor with its own channel stride
+    auto conv = [&](int i, const float* src, int src_cs, float* dst, int dst_cs, const float* res, int res_cs) {
+        enc::layer_forward(p.leg[i].e, src, src_cs, state + p.leg[i].ss, params->packed[i], nullptr, dst, dst_cs, res, res_cs, part, stream);
+    };
     auto stats = [&](int i, const float* src, int cs) {
         const blk::Leg& l = p.leg[i];
         kpn_enc_stats_args a{};
@@ -146,15 +131,15 @@ extern "C" int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const flo
     int base_cs = desc->cin;
     if (p.nlegs == 4) {         // the downsample leg first: y = conv4(relu(bn4(x))), the base the three slices are added to
         stats(3, x, desc->cin);
-        blk::conv(p.leg[3].fwd, H, W, 0, x, desc->cin, state + p.leg[3].ss, params->packed[3], y, c, nullptr, 0, part, stream);
+        conv(3, x, desc->cin, y, c, nullptr, 0);
         base = y; base_cs = c;
     }
     stats(0, x, desc->cin);
-    blk::conv(p.leg[0].fwd, H, W, 1, x, desc->cin, state + p.leg[0].ss, params->packed[0], state, p.cs, nullptr, 0, part, stream);
+    conv(0, x, desc->cin, state, p.cs, nullptr, 0);
     stats(1, state, p.cs);
-    blk::conv(p.leg[1].fwd, H, W, 1, state, p.cs, state + p.leg[1].ss, params->packed[1], state + c / 2, p.cs, nullptr, 0, part, stream);
+    conv(1, state, p.cs, state + c / 2, p.cs, nullptr, 0);
     stats(2, state + c / 2, p.cs);
-    blk::conv(p.leg[2].fwd, H, W, 1, state + c / 2, p.cs, state + p.leg[2].ss, params->packed[2], y + p.cs, c, base + p.cs, base_cs, part, stream);
+    conv(2, state + c / 2, p.cs, y + p.cs, c, base + p.cs, base_cs);
     enc::launch_add_cs(state, p.cs, base, base_cs, y, c, p.P, p.cs, stream);
     return check_launch("kpn_conv_block_forward");
 }
@@ -166,11 +151,11 @@ extern "C" int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const fl
     const blk::Plan p = blk::plan(desc);
     for (int i = 0; i < p.nlegs; ++i) {
         KPN_REQUIRE(params->gamma[i] && params->packed[i], "params: gamma / packed of a leg is null");
-        KPN_REQUIRE(blk::aligned16({params->gamma[i], params->packed[i], grads->dgamma[i], grads->dbeta[i], grads->dw[i]}),
+        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->packed[i], grads->dgamma[i], grads->dbeta[i], grads->dw[i]}),
                     "params / grads: gamma / packed / dgamma / dbeta / dw must be 16-byte aligned");
     }
     KPN_REQUIRE(p.nlegs == 4 || !(grads->dgamma[3] || grads->dbeta[3] || grads->dw[3]), "grads of the downsample leg given for cin == cout");
-    KPN_REQUIRE(blk::aligned16({x, dy, state, dx, workspace}), "x / dy / state / dx / workspace must be 16-byte aligned");
+    KPN_REQUIRE(enc::aligned16({x, dy, state, dx, workspace}), "x / dy / state / dx / workspace must be 16-byte aligned");
     KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
     char* ws = static_cast<char*>(workspace);
     float* dn = reinterpret_cast<float*>(ws + p.b_dn);
@@ -180,23 +165,16 @@ extern "C" int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const fl
     float* wpart = reinterpret_cast<float*>(ws + p.b_wg);
     double* stat = reinterpret_cast<double*>(ws + p.b_stats);
     float* coef = reinterpret_cast<float*>(ws + p.b_coef);
-    const int N = desc->N, H = desc->H, W = desc->W, c = desc->cout;
+    const int N = desc->N, c = desc->cout;
     const bool down = p.nlegs == 4;
     // one leg: R (channel stride r_cs) is the gradient of the leg's convolution output; src (stride src_cs) the un-normalised source
     auto leg = [&](int i, const float* src, int src_cs, const float* R, int r_cs, float* gout, const float* add, int add_cs) {
         const blk::Leg& l = p.leg[i];
-        const int pad = l.k / 2;
         float* dgm = grads->dgamma[i];
         float* dbt = grads->dbeta[i];
-        if (grads->dw[i]) {
-            kpn_enc_conv_args a = l.fwd.a;
-            a.Hs = H; a.Ws = W; a.stride = 1; a.pad = pad;
-            a.src = src; a.src_cs = src_cs; a.ss = state + l.ss; a.relu_in = 1;
-            enc::launch_wgrad(a, l.fwd, l.wg, 0, R, r_cs, wpart, grads->dw[i], stream);
-        }
+        if (grads->dw[i]) enc::layer_wgrad(l.e, src, src_cs, state + l.ss, R, r_cs, wpart, grads->dw[i], stream);
         if (!gout && !dgm && !dbt) return;
-        // d(n_i) = conv(R, w'[ci][co][k - 1 - ky][k - 1 - kx], pad k - 1 - pad): the second packed copy
-        blk::conv(l.dx, H, W, l.k - 1 - pad, R, r_cs, nullptr, params->packed[i] + l.fwd.packed, dn, l.cin, nullptr, 0, cpart, stream);
+        enc::layer_dgrad(l.e, R, r_cs, params->packed[i], dn, l.cin, nullptr, 0, cpart, stream);        // d(n_i)
         kpn_enc_norm_bwd_args a{};
         a.x = src; a.x_cs = src_cs; a.dy = dn; a.ss = state + l.ss; a.mr = state + l.mr; a.gamma = params->gamma[i];
         a.relu = 1; a.C = l.cin; a.HW = p.HW; a.nchunks = l.nchunks; a.nimg = N; a.G = l.G;

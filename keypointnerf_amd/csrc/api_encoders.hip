@@ -8,7 +8,8 @@
 // In front of the walks, the launch layer of encoder_kernels.hip: every launch policy of the kernels that the walks share with
 // the differentiable layers (api_conv.hip, api_strided.hip, api_reppad.hip, api_norm.hip, api_block.hip, api_resample.hip) - tiles,
 // split K, the ranges of a weight gradient, chunk counts, grids - is written there once, and all of these files launch through it.  The split-K rule and the chunk rule fix the order of floating-point sums,
-// so a walk and a layer agree bit for bit only while they share this code.
+// so a walk and a layer agree bit for bit only while they share this code.  What one differentiable convolution layer is in terms of these
+// launches (enc::Layer) follows in api_layer.hip.
 namespace enc {
 
 // the grid of the elementwise kernels (grid-stride loops over n items): blocks of 256 threads, at most 8192 of them
@@ -63,7 +64,7 @@ inline void launch_conv(const kpn_enc_conv_args& a, const ConvGeom& g, int stem,
     }
     if (a.ksplit > 1) KPN_LAUNCH(k_enc_combine, grid4((int64_t)g.ncls * g.M * a.cout), dim3(256), stream, a, g.deconv);
 }
-// the input gradient of a replication-padded stride-1 convolution (api_reppad.hip): the same GEMM, tiles, split K and combine, with
+// the input gradient of a replication-padded stride-1 convolution (enc::layer_dgrad): the same GEMM, tiles, split K and combine, with
 // the adjoint of the clamped load in place of the load.  `a`: g.a of conv_geom(N, H, W, layer cout, layer cin, k, k, 0) with src = dy,
 // (Hs, Ws) = (H, W), pad = k / 2 and the tflip copy of the weight
 inline void launch_conv_rp_adjoint(const kpn_enc_conv_args& a, const ConvGeom& g, void* stream) {

@@ -49,11 +49,9 @@ const char* desc_error(const kpn_res_encoder_desc* d) {
     return nullptr;
 }
 struct Layer {
-    int kind, cin, cout, k;
-    int Hi, Wi, Ho, Wo;             // the grids of the layer's input and output
-    enc::ConvGeom fwd, dx, wg;      // as api_reppad.hip / api_strided.hip make them; the stem has no dx
-    enc::WgradPlan wgp;
-    size_t packed;                  // offset (floats) in the packed weights: the forward copy, then the input-gradient copy
+    int kind;
+    enc::Layer e;                   // the layer itself (api_layer.hip), as the single layers make it
+    size_t packed;                  // offset (floats) in the packed weights: each layer as its own packer writes it
     int nchunks;                    // of the norm behind the layer (not OUT)
     size_t c, ss, mr;               // offsets (floats) in `state`: the layer's output and its norm's statistics (not OUT)
     size_t out_floats;
@@ -67,25 +65,14 @@ struct Plan {
     size_t b_buf[3], b_conv, b_wg, b_stats, b_coef, b_db;      // the backward's
     size_t bytes;
 };
-inline size_t packed_of(const Layer& l) { return (size_t)(l.fwd.packed + (l.kind == STEM ? 0 : l.dx.packed)); }
 Plan plan(const kpn_res_encoder_desc* d, int N, int H, int W) {
     Plan p{};
     auto add = [&](int kind, int cin, int cout, int k, int Hi, int Wi) {
         Layer l{};
-        l.kind = kind; l.cin = cin; l.cout = cout; l.k = k; l.Hi = Hi; l.Wi = Wi;
-        l.Ho = kind == DOWN ? Hi / 2 : (kind == UP ? 2 * Hi : Hi);
-        l.Wo = kind == DOWN ? Wi / 2 : (kind == UP ? 2 * Wi : Wi);
-        if (kind == UP) {
-            l.fwd = enc::conv_geom(N, Hi, Wi, cin, cout, 3, 3, 1);
-            l.dx = enc::conv_geom(N, Hi, Wi, cout, cin, 3, 3, 0);
-            l.wg = l.dx;                                           // the swapped roles
-        } else {
-            l.fwd = enc::conv_geom(N, l.Ho, l.Wo, cin, cout, k, k, 0);
-            if (kind != STEM) l.dx = enc::conv_geom(N, l.Ho, l.Wo, cout, cin, k, k, kind == DOWN);
-            l.wg = l.fwd;
-        }
-        l.wgp = enc::wgrad_plan(l.wg);
-        l.out_floats = (size_t)N * l.Ho * l.Wo * cout;
+        l.kind = kind;
+        const bool s2 = kind == DOWN || kind == UP;                // zero pad; the others pad by replication
+        l.e = enc::layer(enc::LayerSpec{cin, cout, k, s2 ? 2 : 1, k / 2, !s2, kind == UP, kind == STEM}, N, Hi, Wi);
+        l.out_floats = (size_t)l.e.My * cout;
         p.L.push_back(l);
     };
     int C = d->ngf, h = H, w = W;
@@ -98,22 +85,23 @@ Plan plan(const kpn_res_encoder_desc* d, int N, int H, int W) {
     const size_t blk = (size_t)N * p.Hb * p.Wb * p.Cb;
     size_t st = 0, pk = 0;
     for (Layer& l : p.L) {
-        l.packed = pk; pk += packed_of(l);
+        l.packed = pk; pk += l.e.packed_floats;
         if (l.kind != OUT) { l.c = st; st += l.out_floats; }
     }
     for (int k = 0; k <= d->n_blocks; ++k) { p.a.push_back(st); st += blk; }
     size_t stat = 0, fconv = 0, bconv = 0, wg = 0, coef = 0;
     for (Layer& l : p.L) {
-        fconv = std::max(fconv, (size_t)l.fwd.partial * sizeof(float));
-        if (l.kind != STEM) bconv = std::max(bconv, (size_t)l.dx.partial * sizeof(float));
-        wg = std::max(wg, (size_t)l.wgp.partial * sizeof(float));
+        fconv = std::max(fconv, (size_t)l.e.fwd.partial * sizeof(float));
+        bconv = std::max(bconv, (size_t)l.e.dx.partial * sizeof(float));
+        wg = std::max(wg, (size_t)l.e.wgp.partial * sizeof(float));
         if (l.kind == OUT) continue;
+        const int cout = l.e.s.cout;
         int64_t pd;
-        l.nchunks = enc::stats_chunks(N, l.Ho * l.Wo, l.cout, &pd);
-        l.ss = st; st += (size_t)2 * N * l.cout;
-        l.mr = st; st += (size_t)2 * N * l.cout;
+        l.nchunks = enc::stats_chunks(N, l.e.Ho * l.e.Wo, cout, &pd);
+        l.ss = st; st += (size_t)2 * N * cout;
+        l.mr = st; st += (size_t)2 * N * cout;
         stat = std::max(stat, (size_t)pd * sizeof(double));
-        coef = std::max(coef, (size_t)3 * N * l.cout * sizeof(float));
+        coef = std::max(coef, (size_t)3 * N * cout * sizeof(float));
     }
     p.packed_floats = pk; p.state_floats = st;
     // The backward's gradient buffers.  Two alternate down the layers (a layer reads R from one and writes dn, normalised in place, to
@@ -123,12 +111,13 @@ Plan plan(const kpn_res_encoder_desc* d, int N, int H, int W) {
     {
         int cur = 0;
         const int n = (int)p.L.size();
-        need[0] = (size_t)N * p.L[n - 1].Hi * p.L[n - 1].Wi * p.L[n - 1].cin;
+        auto in_floats = [&](const Layer& l) { return (size_t)N * l.e.Hi * l.e.Wi * l.e.s.cin; };
+        need[0] = in_floats(p.L[n - 1]);
         for (int i = n - 2; i >= 1; --i) {
             const Layer& l = p.L[i];
             if (l.kind == RES && (i - 1 - d->n_down) % 2 == 0) continue;        // the first convolution of a ResBlk: with the second
             cur ^= 1;
-            need[cur] = std::max(need[cur], (size_t)N * l.Hi * l.Wi * l.cin);
+            need[cur] = std::max(need[cur], in_floats(l));
         }
     }
     // the forward and the backward never run at once on a workspace: the larger of the two
@@ -140,28 +129,13 @@ Plan plan(const kpn_res_encoder_desc* d, int N, int H, int W) {
     p.b_wg = b.take(wg);
     p.b_stats = b.take(stat);
     p.b_coef = b.take(coef);
-    const Layer& o = p.L.back();
-    p.b_db = b.take((size_t)enc::dbias_chunks((int64_t)N * o.Ho * o.Wo) * o.cout * sizeof(double));
+    const enc::Layer& o = p.L.back().e;
+    p.b_db = b.take((size_t)enc::dbias_chunks(o.My) * o.s.cout * sizeof(double));
     p.bytes = std::max<size_t>(std::max(f.o, b.o), 256);
     return p;
 }
 inline Plan plan(const kpn_res_encoder_desc* d) { return plan(d, d->N, d->H, d->W); }
 inline int n_layers(const kpn_res_encoder_desc* d) { return 2 + d->n_down + 2 * d->n_blocks + d->n_up; }
-// the source side of a layer's forward GEMM and of the weight gradient of every kind but UP: what api_reppad.hip (rp::source) and
-// api_strided.hip (s2::strided_source / deconv_source) set for the same layer
-inline void source(kpn_enc_conv_args& a, const Layer& l, const float* src, const float* ss) {
-    a.Hs = l.Hi; a.Ws = l.Wi; a.src = src; a.src_cs = a.cin;
-    a.stride = l.kind == DOWN ? 2 : 1;
-    a.pad = l.kind == UP ? 0 : l.k / 2;
-    a.replicate = l.kind == STEM || l.kind == RES || l.kind == OUT;
-    if (l.kind == STEM) { a.Hraw = l.Hi; a.Wraw = l.Wi; a.ds = 0; a.stem_plain = 1; }
-    a.ss = ss; a.relu_in = ss != nullptr;
-}
-bool aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t u = 0;
-    for (const void* q : ps) u |= (uintptr_t)q;
-    return (u & 15) == 0;
-}
 }  // namespace rte
 
 #define KPN_RTE_REQUIRE_DESC(desc) do { if (const char* e_ = rte::desc_error(desc)) return fail(KPN_EINVAL, std::string("kpn_res_encoder_desc: ") + e_); } while (0)
@@ -184,12 +158,7 @@ extern "C" int kpn_res_encoder_pack_device(const kpn_res_encoder_desc* desc, con
     KPN_REQUIRE(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
     const rte::Plan p = rte::plan(desc, 1, 1 << desc->n_down, 1 << desc->n_down);
     for (size_t i = 0; i < p.L.size(); ++i) KPN_REQUIRE(weights[i], "weights: the weight of a layer is null");
-    for (size_t i = 0; i < p.L.size(); ++i) {
-        const rte::Layer& l = p.L[i];
-        // each layer as its own packer writes it (kpn_conv2d_rp_pack_device / kpn_conv2d_s2_pack_device)
-        enc::launch_pack(l.fwd, 0, weights[i], packed + l.packed, stream);
-        if (l.kind != rte::STEM) enc::launch_pack(l.dx, l.kind == rte::RES || l.kind == rte::OUT, weights[i], packed + l.packed + l.fwd.packed, stream);
-    }
+    for (size_t i = 0; i < p.L.size(); ++i) enc::layer_pack(p.L[i].e, weights[i], packed + p.L[i].packed, stream);
     return check_launch("kpn_res_encoder_pack_device");
 }
 extern "C" int kpn_res_encoder_forward(const kpn_res_encoder_desc* desc, const float* x, const float* packed, const float* const* bias,
@@ -199,25 +168,22 @@ extern "C" int kpn_res_encoder_forward(const kpn_res_encoder_desc* desc, const f
     const rte::Plan p = rte::plan(desc);
     const int n = (int)p.L.size(), N = desc->N;
     for (int i = 0; i < n; ++i) KPN_REQUIRE(bias[i], "bias: the bias of a layer is null");
-    KPN_REQUIRE(rte::aligned16({packed, y, state, workspace}), "packed / y / state / workspace must be 16-byte aligned");
+    KPN_REQUIRE(enc::aligned16({packed, y, state, workspace}), "packed / y / state / workspace must be 16-byte aligned");
     KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_res_encoder_workspace_bytes)");
     char* ws = static_cast<char*>(workspace);
     double* stat = reinterpret_cast<double*>(ws + p.f_stats);
     float* part = reinterpret_cast<float*>(ws + p.f_conv);
     auto conv = [&](int i, const float* src, const float* ss, float* dst) {
-        const rte::Layer& l = p.L[i];
-        kpn_enc_conv_args a = l.fwd.a;
-        rte::source(a, l, src, ss);
-        a.wp = packed + l.packed; a.bias = bias[i]; a.dst = dst; a.dst_cs = a.cout;
-        a.partial = l.fwd.partial ? part : nullptr;
-        enc::launch_conv(a, l.fwd, l.kind == rte::STEM, stream);
+        const enc::Layer& e = p.L[i].e;
+        enc::layer_forward(e, src, e.s.cin, ss, packed + p.L[i].packed, bias[i], dst, e.s.cout, nullptr, 0, part, stream);
     };
     auto stats = [&](int i) {
         const rte::Layer& l = p.L[i];
+        const int C = l.e.s.cout;
         kpn_enc_stats_args a{};
-        a.src = state + l.c; a.cs = l.cout; a.C = l.cout; a.HW = l.Ho * l.Wo; a.nchunks = l.nchunks; a.nimg = N;
+        a.src = state + l.c; a.cs = C; a.C = C; a.HW = l.e.Ho * l.e.Wo; a.nchunks = l.nchunks; a.nimg = N;
         a.partial = stat;
-        a.G = l.cout; a.eps = desc->eps;
+        a.G = C; a.eps = desc->eps;
         a.ss = state + l.ss; a.mr = state + l.mr;
         enc::launch_stats(a, stream);
     };
@@ -252,8 +218,8 @@ extern "C" int kpn_res_encoder_backward(const kpn_res_encoder_desc* desc, const 
     KPN_REQUIRE(x && dy && packed && state && dw && db && workspace, "null pointer");
     const rte::Plan p = rte::plan(desc);
     const int n = (int)p.L.size(), N = desc->N, nd = desc->n_down, nb = desc->n_blocks;
-    for (int i = 0; i < n; ++i) KPN_REQUIRE(rte::aligned16({dw[i], db[i]}), "dw / db must be 16-byte aligned");
-    KPN_REQUIRE(rte::aligned16({dy, packed, state, workspace}), "dy / packed / state / workspace must be 16-byte aligned");
+    for (int i = 0; i < n; ++i) KPN_REQUIRE(enc::aligned16({dw[i], db[i]}), "dw / db must be 16-byte aligned");
+    KPN_REQUIRE(enc::aligned16({dy, packed, state, workspace}), "dy / packed / state / workspace must be 16-byte aligned");
     KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_res_encoder_workspace_bytes)");
     char* ws = static_cast<char*>(workspace);
     float* buf[3] = {reinterpret_cast<float*>(ws + p.b_buf[0]), reinterpret_cast<float*>(ws + p.b_buf[1]), reinterpret_cast<float*>(ws + p.b_buf[2])};
@@ -268,49 +234,36 @@ extern "C" int kpn_res_encoder_backward(const kpn_res_encoder_desc* desc, const 
     hipError_t zero_err = hipSuccess;
     for (int i = 0; i < n - 1; ++i)
         if (db[i]) {
-            const hipError_t e = hipMemsetAsync(db[i], 0, (size_t)p.L[i].cout * sizeof(float), (hipStream_t)stream);
+            const hipError_t e = hipMemsetAsync(db[i], 0, (size_t)p.L[i].e.s.cout * sizeof(float), (hipStream_t)stream);
             if (e != hipSuccess && zero_err == hipSuccess) zero_err = e;
         }
     if (zero_err != hipSuccess) return fail(KPN_ELAUNCH, std::string("kpn_res_encoder_backward: zeroing a bias gradient failed: ") + hipGetErrorString(zero_err));
     // dW of layer i for R = dL/dc_i; its source is `src`, lazily normalised with `ss` or (ss = NULL) a materialised tensor
     auto wgrad = [&](int i, const float* src, const float* ss, const float* R) {
-        const rte::Layer& l = p.L[i];
-        if (!dw[i]) return;
-        kpn_enc_conv_args c = l.wg.a;
-        if (l.kind == rte::UP) {        // the swapped roles: A from R with stride 2, rhs = the layer's input
-            c.Hs = l.Ho; c.Ws = l.Wo; c.stride = 2; c.pad = 1; c.src = R; c.src_cs = c.cin;
-            enc::launch_wgrad(c, l.wg, l.wgp, 0, src, c.cout, wpart, dw[i], stream, ss);
-        } else {
-            rte::source(c, l, src, ss);
-            enc::launch_wgrad(c, l.wg, l.wgp, l.kind == rte::STEM, R, c.cout, wpart, dw[i], stream);
-        }
+        const enc::Layer& e = p.L[i].e;
+        if (dw[i]) enc::layer_wgrad(e, src, e.s.cin, ss, R, e.s.cout, wpart, dw[i], stream);
     };
     // dn = the input gradient of layer i for R [+ res]
     auto dgrad = [&](int i, const float* R, float* dn, const float* res) {
-        const rte::Layer& l = p.L[i];
-        kpn_enc_conv_args a = l.dx.a;
-        a.src = R; a.src_cs = a.cin;
-        a.wp = packed + l.packed + l.fwd.packed; a.dst = dn; a.dst_cs = a.cout; a.res = res; a.res_cs = a.cout;
-        a.partial = l.dx.partial ? cpart : nullptr;
-        if (l.kind == rte::DOWN) { a.Hs = l.Ho; a.Ws = l.Wo; a.stride = 1; a.pad = 0; enc::launch_conv(a, l.dx, 0, stream); }
-        else if (l.kind == rte::UP) { a.Hs = l.Ho; a.Ws = l.Wo; a.stride = 2; a.pad = 1; enc::launch_conv(a, l.dx, 0, stream); }
-        else { a.Hs = l.Hi; a.Ws = l.Wi; a.stride = 1; a.pad = l.k / 2; enc::launch_conv_rp_adjoint(a, l.dx, stream); }
+        const enc::Layer& e = p.L[i].e;
+        enc::layer_dgrad(e, R, e.s.cout, packed + p.L[i].packed, dn, e.s.cin, res, e.s.cin, cpart, stream);
     };
     // dst = the gradient of the norm behind layer i (with its ReLU or without) for the gradient g of its output; dst may be g
     auto norm_bwd = [&](int i, const float* g, int relu, float* dst) {
         const rte::Layer& l = p.L[i];
         kpn_enc_norm_bwd_args a{};
-        a.x = state + l.c; a.x_cs = l.cout; a.dy = g; a.ss = state + l.ss; a.mr = state + l.mr;
-        a.relu = relu; a.C = l.cout; a.HW = l.Ho * l.Wo; a.nchunks = l.nchunks; a.nimg = N; a.G = l.cout;
+        const int C = l.e.s.cout;
+        a.x = state + l.c; a.x_cs = C; a.dy = g; a.ss = state + l.ss; a.mr = state + l.mr;
+        a.relu = relu; a.C = C; a.HW = l.e.Ho * l.e.Wo; a.nchunks = l.nchunks; a.nimg = N; a.G = C;
         a.partial = stat; a.coef = coef; a.dx = dst;
         enc::launch_norm_bwd(a, stream);
     };
     int i = n - 1, cur = 0;
     const float* R = dy;
     {   // the output layer
-        const rte::Layer& l = p.L[i];
+        const enc::Layer& e = p.L[i].e;
         wgrad(i, state + p.L[i - 1].c, state + p.L[i - 1].ss, R);
-        if (db[i]) enc::launch_dbias(dy, (int64_t)N * l.Ho * l.Wo, l.cout, reinterpret_cast<double*>(ws + p.b_db), db[i], stream);
+        if (db[i]) enc::launch_dbias(dy, e.My, e.s.cout, reinterpret_cast<double*>(ws + p.b_db), db[i], stream);
         if (first < i) {
             dgrad(i, R, buf[0], nullptr);
             norm_bwd(i - 1, buf[0], 1, buf[0]);

@@ -46,6 +46,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "api_metrics.hip"
 #include "api_vgg.hip"
 #include "api_encoders.hip"
+#include "api_layer.hip"      // one convolution layer over the launch layer: the five files below name theirs
 #include "api_conv.hip"
 #include "api_strided.hip"
 #include "api_reppad.hip"

@@ -552,18 +552,11 @@ def conv2d_cache_clear():
         _ConvPackCache.entries.clear()
 
 
-def _conv_packed(weight, kind=None):
-    """the packed copies of a weight: of the stride-1 layer (kind None), of one of the kpn_conv2d_s2_* kinds (an integer) or of one of
-    the kpn_conv2d_rp_* kinds (("rp", kind))"""
-    if kind is None:
-        pack = ops.conv2d_pack
-    elif isinstance(kind, tuple):           # ("rp", KPN_RP_*)
-        pack = lambda w: ops.conv2d_rp_pack(w, kind[1])  # noqa: E731
-    else:
-        pack = lambda w: ops.conv2d_s2_pack(w, kind)  # noqa: E731
+def _conv_packed(weight, pack, tag):
+    """the packed copies of a weight, made by ``pack(weight)``; ``tag`` (hashable) tells the families and their kinds apart in the key"""
     if weight.is_inference():
         return pack(weight)
-    key = _tensor_key(weight) + (kind,)
+    key = _tensor_key(weight) + (tag,)
     C = _ConvPackCache
     with C.lock:
         e = C.entries.get(key[0])
@@ -581,12 +574,58 @@ def _conv_packed(weight, kind=None):
     return packed
 
 
+def _packed_conv(weight):
+    return _conv_packed(weight, ops.conv2d_pack, "conv")
+
+
+def _packed_s2(weight, kind):
+    return _conv_packed(weight, lambda w: ops.conv2d_s2_pack(w, kind), ("s2", kind))
+
+
+def _packed_rp(weight, kind):
+    return _conv_packed(weight, lambda w: ops.conv2d_rp_pack(w, kind), ("rp", kind))
+
+
+# What the three families' backward operators (kpnerf::conv2d_backward, conv2d_s2_backward, conv2d_rp_backward) and the autograd
+# backward of the four forward operators share.
+def _layer_backward(backward, x, dy, packed, args, has_bias, mask):
+    """the body of a backward operator: ``backward`` is the family's ops.*_backward, ``packed`` the packed copies (None without dx) and
+    ``args`` what that function takes between them and has_bias"""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = backward(x, dy, packed, *args, has_bias, want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    return _empty_for_none(dy, dx, dw, db)
+
+
+def _layer_backward_fake(x, weight, has_bias, mask, cout, dx_format=torch.channels_last):
+    e = x.new_empty(0)
+    return (torch.empty_like(x, memory_format=dx_format) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
+            x.new_empty(cout) if mask[2] and has_bias else e)
+
+
+def _layer_autograd(backward_op, what_attr, n_inputs):
+    """the autograd backward of a forward operator over (x, weight, bias, ...n_inputs in all): only the legs whose inputs need a gradient
+    run, through ``backward_op`` with ctx.<what_attr> as its fourth argument"""
+    nothing = (None,) * n_inputs
+
+    def bwd(ctx, dy):
+        if dy is None:
+            return nothing
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]
+        if not any(mask):
+            return nothing
+        dx, dw, db = backward_op(x, weight, dy, getattr(ctx, what_attr), ctx.has_bias, mask)
+        return _none_unless(mask, dx, dw, db) + nothing[3:]
+    return bwd
+
+
 @_lib.custom_op("kpnerf::conv2d_cl", mutates_args=(), device_types="cuda")
 def conv2d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], padding: int) -> torch.Tensor:
     """conv2d(x, weight, bias, stride=1, padding=padding) for a channels_last x (kpn_conv2d_forward): what torch.ops.kpnerf.conv2d
     runs after its memory-format conversion.  weight (cout, cin, k, k), k in {1, 3, 5}, 0 <= padding < k, cin and cout multiples of 4.
     Returns (N, cout, Ho, Wo) channels_last."""
-    return ops.conv2d_forward(x, _conv_packed(weight), bias, weight.shape[0], weight.shape[2], padding)
+    return ops.conv2d_forward(x, _packed_conv(weight), bias, weight.shape[0], weight.shape[2], padding)
 
 
 @conv2d_cl.register_fake
@@ -601,18 +640,13 @@ def conv2d_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, pad
                     mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dx, dweight, dbias) of kpnerf::conv2d_cl for the output gradient dy (kpn_conv2d_backward); mask = [dx, dweight, dbias]
     wanted: a leg that is not wanted is not launched and its result is an empty tensor."""
-    cout, cin, k, _ = weight.shape
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dx, dw, db = ops.conv2d_backward(x, dy, _conv_packed(weight) if mask[0] else None, cin, k, padding, has_bias,
-                                     want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
-    return _empty_for_none(dy, dx, dw, db)
+    return _layer_backward(ops.conv2d_backward, x, dy, _packed_conv(weight) if mask[0] else None, (weight.shape[1], weight.shape[2], padding),
+                           has_bias, mask)
 
 
 @conv2d_backward.register_fake
 def _(x, weight, dy, padding, has_bias, mask):
-    e = x.new_empty(0)
-    return (torch.empty_like(x) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
-            x.new_empty(weight.shape[0]) if mask[2] and has_bias else e)
+    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0], torch.preserve_format)
 
 
 def _conv2d_setup(ctx, inputs, output):
@@ -622,19 +656,7 @@ def _conv2d_setup(ctx, inputs, output):
     ctx.set_materialize_grads(False)
 
 
-def _conv2d_bwd(ctx, dy):
-    if dy is None:
-        return None, None, None, None
-    x, weight = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
-    if not any(mask):
-        return None, None, None, None
-    dx, dw, db = torch.ops.kpnerf.conv2d_backward(x, weight, dy, ctx.padding, ctx.has_bias, mask)
-    return _none_unless(mask, dx, dw, db) + (None,)
-
-
-conv2d_cl.register_autograd(_conv2d_bwd, setup_context=_conv2d_setup)
+conv2d_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_backward, "padding", 4), setup_context=_conv2d_setup)
 
 
 # torch.ops.kpnerf.conv2d(x, weight, bias, padding): x in any memory format.  A contiguous NCHW input is converted to channels_last
@@ -666,7 +688,7 @@ def conv2d_down2_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     cout multiples of 4) or k = 7 (x contiguous NCHW, cin <= 4) (kpn_conv2d_s2_forward): what torch.ops.kpnerf.conv2d_down2 runs
     after its memory-format conversion.  Returns (N, cout, Ho, Wo) channels_last."""
     kind = _down2_kind(weight)
-    return ops.conv2d_s2_forward(x, _conv_packed(weight, kind), bias, weight.shape[0], kind)
+    return ops.conv2d_s2_forward(x, _packed_s2(weight, kind), bias, weight.shape[0], kind)
 
 
 @conv2d_down2_cl.register_fake
@@ -682,7 +704,7 @@ def conv_transpose2d_up2_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optiona
     conversion.  Returns (N, cout, 2H, 2W) channels_last."""
     if weight.shape[-1] != 3:
         raise ValueError(f"conv_transpose2d_up2: kernel size {weight.shape[-1]} (3 only)")
-    return ops.conv2d_s2_forward(x, _conv_packed(weight, kl.S2_DECONV3), bias, weight.shape[1], kl.S2_DECONV3)
+    return ops.conv2d_s2_forward(x, _packed_s2(weight, kl.S2_DECONV3), bias, weight.shape[1], kl.S2_DECONV3)
 
 
 @conv_transpose2d_up2_cl.register_fake
@@ -697,18 +719,12 @@ def conv2d_s2_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, 
     """(dx, dweight, dbias) of kpnerf::conv2d_down2_cl / conv_transpose2d_up2_cl for the output gradient dy (kpn_conv2d_s2_backward);
     kind is the KPN_S2_* value; mask = [dx, dweight, dbias] wanted: a leg that is not wanted is not launched and its result is an
     empty tensor."""
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dx, dw, db = ops.conv2d_s2_backward(x, dy, _conv_packed(weight, kind) if mask[0] else None, x.shape, kind, has_bias,
-                                        want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
-    return _empty_for_none(dy, dx, dw, db)
+    return _layer_backward(ops.conv2d_s2_backward, x, dy, _packed_s2(weight, kind) if mask[0] else None, (x.shape, kind), has_bias, mask)
 
 
 @conv2d_s2_backward.register_fake
 def _(x, weight, dy, kind, has_bias, mask):
-    e = x.new_empty(0)
-    cout = weight.shape[1 if kind == kl.S2_DECONV3 else 0]
-    return (torch.empty_like(x, memory_format=torch.channels_last) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
-            x.new_empty(cout) if mask[2] and has_bias else e)
+    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[1 if kind == kl.S2_DECONV3 else 0])
 
 
 def _s2_setup(kind_of):
@@ -722,18 +738,7 @@ def _s2_setup(kind_of):
     return setup
 
 
-def _s2_bwd(ctx, dy):
-    if dy is None:
-        return None, None, None
-    x, weight = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
-    if not any(mask):
-        return None, None, None
-    dx, dw, db = torch.ops.kpnerf.conv2d_s2_backward(x, weight, dy, ctx.kind, ctx.has_bias, mask)
-    return _none_unless(mask, dx, dw, db)
-
-
+_s2_bwd = _layer_autograd(torch.ops.kpnerf.conv2d_s2_backward, "kind", 3)
 conv2d_down2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(_down2_kind))
 conv_transpose2d_up2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(lambda w: kl.S2_DECONV3))
 
@@ -759,17 +764,13 @@ _fragment.impl("conv_transpose2d_up2", _conv_transpose2d_up2, "CompositeImplicit
 # One operator for the three kinds of kpn_conv2d_rp_*, the kind following the weight: 3x3, 7x7, or - a 7x7 weight with at most 4 input
 # channels - the stem, which reads a contiguous NCHW tensor as it is and has no input gradient: it raises on an x that requires one.
 # The packed copies live in the cache of kpnerf::conv2d, keyed by weight and kind.
-def _rp_key(kind):
-    return ("rp", kind)         # beside None (stride 1) and the KPN_S2_* integers in the cache key
-
-
 @_lib.custom_op("kpnerf::conv2d_replicate_cl", mutates_args=(), device_types="cuda")
 def conv2d_replicate_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """conv2d(pad(x, k // 2, mode="replicate"), weight, bias) for weight (cout, cin, k, k), k = 3 or 7 (x channels_last, cin and cout
     multiples of 4) or k = 7 with cin <= 4 (x contiguous NCHW) (kpn_conv2d_rp_forward): what torch.ops.kpnerf.conv2d_replicate runs
     after its memory-format conversion.  Returns (N, cout, H, W) channels_last."""
     kind = ops.conv2d_rp_kind(weight.shape)
-    return ops.conv2d_rp_forward(x, _conv_packed(weight, _rp_key(kind)), bias, weight.shape[0], kind)
+    return ops.conv2d_rp_forward(x, _packed_rp(weight, kind), bias, weight.shape[0], kind)
 
 
 @conv2d_replicate_cl.register_fake
@@ -783,17 +784,12 @@ def conv2d_rp_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, 
                        mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dx, dweight, dbias) of kpnerf::conv2d_replicate_cl for the output gradient dy (kpn_conv2d_rp_backward); kind is the KPN_RP_*
     value; mask = [dx, dweight, dbias] wanted: a leg that is not wanted is not launched and its result is an empty tensor."""
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dx, dw, db = ops.conv2d_rp_backward(x, dy, _conv_packed(weight, _rp_key(kind)) if mask[0] else None, x.shape, kind, has_bias,
-                                        want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
-    return _empty_for_none(dy, dx, dw, db)
+    return _layer_backward(ops.conv2d_rp_backward, x, dy, _packed_rp(weight, kind) if mask[0] else None, (x.shape, kind), has_bias, mask)
 
 
 @conv2d_rp_backward.register_fake
 def _(x, weight, dy, kind, has_bias, mask):
-    e = x.new_empty(0)
-    return (torch.empty_like(x, memory_format=torch.channels_last) if mask[0] else e, torch.empty_like(weight) if mask[1] else e,
-            x.new_empty(weight.shape[0]) if mask[2] and has_bias else e)
+    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0])
 
 
 def _rp_setup(ctx, inputs, output):
@@ -805,19 +801,7 @@ def _rp_setup(ctx, inputs, output):
     ctx.set_materialize_grads(False)
 
 
-def _rp_bwd(ctx, dy):
-    if dy is None:
-        return None, None, None
-    x, weight = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]      # only the legs whose inputs need a gradient
-    if not any(mask):
-        return None, None, None
-    dx, dw, db = torch.ops.kpnerf.conv2d_rp_backward(x, weight, dy, ctx.kind, ctx.has_bias, mask)
-    return _none_unless(mask, dx, dw, db)
-
-
-conv2d_replicate_cl.register_autograd(_rp_bwd, setup_context=_rp_setup)
+conv2d_replicate_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_rp_backward, "kind", 3), setup_context=_rp_setup)
 
 
 # torch.ops.kpnerf.conv2d_replicate(x, weight, bias): x in any memory format, converted once (as kpnerf::conv2d does) - to channels_last,
@@ -915,7 +899,7 @@ def conv_block_cl(x: torch.Tensor, tensors: List[torch.Tensor], eps: float) -> T
     memory-format conversion.  y is (N, cout, H, W) channels_last with cout = 2 * conv1.weight.shape[0]; state is the side buffer of the
     backward."""
     legs = _block_legs(tensors)
-    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_conv_packed(w) for _, _, w in legs], 2 * legs[0][2].shape[0], eps)
+    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_packed_conv(w) for _, _, w in legs], 2 * legs[0][2].shape[0], eps)
 
 
 @conv_block_cl.register_fake
@@ -936,7 +920,7 @@ def conv_block_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: tor
     legs = _block_legs(tensors)
     dy = dy.contiguous(memory_format=torch.channels_last)
     want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
-    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_conv_packed(w) for _, _, w in legs], state, eps,
+    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_packed_conv(w) for _, _, w in legs], state, eps,
                                         want_dx=mask[0], want=want)
     return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
 

@@ -379,6 +379,29 @@ def check_bad_descriptors(L, B, name="noblocks"):
     assert np.array_equal(B.get(y), y0) and not any((B.get(v) == CANARY).all() for v in grads)
 
 
+def check_pack_is_the_single_layers_packs(L, B, name):
+    """kpn_res_encoder_pack_device writes, byte for byte, what kpn_conv2d_rp_pack_device / kpn_conv2d_s2_pack_device write for each layer's
+    weight, in layer order; kpn_res_encoder_packed_floats is the sum of the single layers' counts"""
+    c = CASES[name]
+    net = reference(name)[0]
+    params = Params(L, B, c, net)
+    parts, floats = [], 0
+    for (kind, cin, cout, k, _, _), m in zip(layers_of(c), convs_of(net)):
+        w = m.weight.detach().numpy()
+        if kind in ("down", "up"):
+            cd = dict(kind=sc.CONV3 if kind == "down" else sc.DECONV3, cin=cin, cout=cout, N=1, H=2, W=2, bias=True)
+            parts.append(B.get(sc.pack(L, B, cd, w)))
+            floats += L.kpn_conv2d_s2_packed_floats(ctypes.byref(sc.desc(cd)))
+        else:
+            cd = dict(kind=rc.STEM7 if kind == "stem" else (rc.CONV3 if k == 3 else rc.CONV7), cin=cin, cout=cout, N=1, H=1, W=1, bias=True)
+            parts.append(B.get(rc.pack(L, B, cd, w)))
+            floats += L.kpn_conv2d_rp_packed_floats(ctypes.byref(rc.desc(cd)))
+    assert sorted({l[0] for l in layers_of(c)}) == ["down", "out", "res", "stem", "up"]          # every layer kind
+    want = np.concatenate([p.reshape(-1) for p in parts])
+    assert L.kpn_res_encoder_packed_floats(ctypes.byref(desc(c))) == floats == want.size
+    assert np.array_equal(_bits(B.get(params.packed)), _bits(want))
+
+
 def layer_by_layer(L, B, name):
     """the forward of one case through the single layers of the C ABI (kpn_conv2d_rp_forward / kpn_conv2d_s2_forward /
     kpn_group_norm_forward per layer, one fp32 add per ResBlk): the dataflow of install_native_tex() -> (y NHWC, {"c0" .., "a0" ..: NHWC})"""

@@ -62,6 +62,10 @@ def test_abi_state_size_follows_the_descriptor(L):
         assert L.kpn_res_encoder_state_floats(ctypes.byref(ec.desc(c))) == ec.state_floats(c)
 
 
+def test_abi_pack_is_the_single_layers_packs_in_layer_order(L, B):
+    ec.check_pack_is_the_single_layers_packs(L, B, "narrow")
+
+
 # ---- torch.ops.kpnerf.res_encoder ----
 bits = lambda a: np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a).view(np.uint32)  # noqa: E731
 

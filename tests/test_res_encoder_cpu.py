@@ -78,6 +78,10 @@ def test_the_packed_weights_are_the_per_kind_packers_in_layer_order(L):
         assert np.array_equal(np.asarray(params.packed).view(np.uint32), want.view(np.uint32))
 
 
+def test_pack_is_the_single_layers_packs_in_layer_order(L):
+    ec.check_pack_is_the_single_layers_packs(L, B, "narrow")
+
+
 def test_fake_kernels_give_shapes_in_channels_last_and_there_is_no_cpu_kernel():
     import keypointnerf_amd.torch_ops  # noqa: F401
     from torch._subclasses.fake_tensor import FakeTensorMode
