@@ -58,6 +58,8 @@ extern "C" {
 /* still 10: a whole ResBlkEncoder as one differentiable operator (kpn_res_encoder_desc, kpn_res_encoder_layers,
  * kpn_res_encoder_workspace_bytes, kpn_res_encoder_state_floats, kpn_res_encoder_packed_floats, kpn_res_encoder_pack_device,
  * kpn_res_encoder_forward, kpn_res_encoder_backward) is additive within 10 in the same way */
+/* still 10: the arithmetic selector of the stride-1 convolution and the ConvBlock (KPN_CONV_F32 / KPN_CONV_BF16X3, kpn_conv2d_ex_*,
+ * kpn_conv_block_ex_*) is additive within 10 in the same way: kpn_conv2d_* and kpn_conv_block_* are its arith = KPN_CONV_F32 case */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -641,6 +643,40 @@ int kpn_conv2d_forward(const kpn_conv2d_desc* desc, const float* x, const float*
 int kpn_conv2d_backward(const kpn_conv2d_desc* desc, const float* x, const float* dy, const float* packed, float* dx, float* dw,
                         float* db, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The arithmetic of the three GEMMs (y, dx, dw) of a stride-1 convolution, chosen per call.  The kpn_conv2d_ex_* entry points are
+ * kpn_conv2d_* with `arith` behind the descriptor; with KPN_CONV_F32 they are the same code and give the same bits, packed buffer
+ * included.  Another value of arith is refused with KPN_EINVAL ("arith must be ..."; the size queries return 0) and launches nothing.
+ *   KPN_CONV_F32     v_mfma_f32_32x32x2_f32 as described above.
+ *   KPN_CONV_BF16X3  v_mfma_f32_32x32x16_bf16 (csrc/encoder_split_kernels.hip).  Every fp32 operand value v is carried as three bf16
+ *                    pieces, h = bf16(v), m = bf16(v - h), l = bf16(v - h - m) (round to nearest even; the residuals are exact in fp32),
+ *                    so |v - (h + m + l)| <= 2^-24 |v| over fp32's whole exponent range: no range guard and no scales, and scaling an
+ *                    operand by a power of two scales the result by it exactly (short of overflow and subnormals).  A product a * b
+ *                    is six piece products, accumulated in fp32 in this order per 16 K entries and accumulator:
+ *                        ah bh, ah bm, am bh, am bm, ah bl, al bh
+ *                    (what is left out is below 2^-24 of the product).  Activations are split in the kernel as they are staged, once
+ *                    per tile; weights at pack time: `packed` holds 6 bytes per weight (kpn_conv2d_ex_packed_floats counts floats of
+ *                    4 bytes), the forward copy then the input-gradient copy, each [chunk of 32 K][piece][8 K][cout_p][8 bf16].
+ *                    Tiles: 128 x 64 (pixels x channels), or 256 x 32 when cout <= 32, four wavefronts with two accumulators each,
+ *                    K chunk 32.  Split K: as kpn_conv2d_forward, from the per-image geometry with these tiles and chunks - an image's y
+ *                    and dx do not depend on its batch.  dw: the pixel index is the MFMA's K; after every 16 pixels the fp32
+ *                    accumulators are added to fp64 sums; the range rule is the one of kpn_conv2d_wgrad_ranges with (BM, BN) =
+ *                    (128, 64), or (256, 32) when cout <= 32.  db does not depend on arith.  No float atomics.
+ *                    Accuracy: that of the fp32 kernels against fp64 (tests/conv_arith_cases.py).
+ * `packed`, `workspace` and the range count belong to one arithmetic: query and pack with the arith of the call.  Packed sizes differ
+ * between the two (6 against 4 bytes per weight), but the calls do not take the size of `packed`: handing a pack of the other
+ * arithmetic is the caller's contract, as a pack of another descriptor is.
+ * Not served with KPN_CONV_BF16X3 (there is no _ex form): kpn_conv2d_s2_*, kpn_conv2d_rp_*, kpn_res_encoder_*, kpn_geo_encode,
+ * kpn_tex_encode, the VGG loss; there is no two-piece fp16 variant. */
+enum { KPN_CONV_F32 = 0, KPN_CONV_BF16X3 = 1 };
+size_t kpn_conv2d_ex_packed_floats(const kpn_conv2d_desc* desc, int32_t arith);
+int kpn_conv2d_ex_pack_device(const kpn_conv2d_desc* desc, int32_t arith, const float* w_oihw, float* packed, void* stream);
+size_t kpn_conv2d_ex_workspace_bytes(const kpn_conv2d_desc* desc, int32_t arith);
+int32_t kpn_conv2d_ex_wgrad_ranges(const kpn_conv2d_desc* desc, int32_t arith);
+int kpn_conv2d_ex_forward(const kpn_conv2d_desc* desc, int32_t arith, const float* x, const float* packed, const float* bias, float* y,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv2d_ex_backward(const kpn_conv2d_desc* desc, int32_t arith, const float* x, const float* dy, const float* packed, float* dx,
+                           float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The resolution-changing layers of the image encoders, forward and backward: the three kinds kpn_conv2d_* refuses.  groups = 1,
  * dilation = 1, zero padding, optional bias, fp32.  Activations are NHWC (torch channels_last) except the stem's input, which is
@@ -828,6 +864,18 @@ int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const float* x, cons
 int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
                             const float* state, float* dx, const kpn_conv_block_grads* grads, void* workspace, size_t workspace_bytes,
                             void* stream);
+/* The block with the arithmetic of its convolutions chosen per call (KPN_CONV_F32 / KPN_CONV_BF16X3 as kpn_conv2d_ex_*): every leg's
+ * y, dx and dw GEMMs run in `arith`; the norms, their gradients and the adds do not change.  params->packed[i] then holds what
+ * kpn_conv2d_ex_pack_device gives with the same arith.  The block equals, bit for bit, the layer-by-layer computation over
+ * kpn_conv2d_ex_* with that arith.  KPN_CONV_F32 is kpn_conv_block_*; an unknown arith is refused with KPN_EINVAL ("arith must be
+ * ...", the size queries return 0) and launches nothing. */
+size_t kpn_conv_block_ex_workspace_bytes(const kpn_conv_block_desc* desc, int32_t arith);
+size_t kpn_conv_block_ex_state_floats(const kpn_conv_block_desc* desc, int32_t arith);
+int kpn_conv_block_ex_forward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const kpn_conv_block_params* params, float* y,
+                              float* state, void* workspace, size_t workspace_bytes, void* stream);
+int kpn_conv_block_ex_backward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const float* dy,
+                               const kpn_conv_block_params* params, const float* state, float* dx, const kpn_conv_block_grads* grads,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A whole ResBlkEncoder(norm = "instance") (src/utils.py:199-259) for training, forward and backward, as one call each: replaces every

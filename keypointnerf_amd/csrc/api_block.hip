@@ -51,7 +51,9 @@ struct Plan {
     size_t b_dn, b_g2, b_g1, b_conv, b_wg, b_stats, b_coef; // the backward's
     size_t bytes;
 };
-Plan plan(const kpn_conv_block_desc* d) {
+// arith: the arithmetic of every leg's three GEMMs (KPN_CONV_F32 / KPN_CONV_BF16X3); the norms, the adds and the order of the legs do not
+// depend on it
+Plan plan(const kpn_conv_block_desc* d, int arith = KPN_CONV_F32) {
     Plan p{};
     const int c = d->cout;
     p.nlegs = d->cin != c ? 4 : 3;
@@ -63,7 +65,7 @@ Plan plan(const kpn_conv_block_desc* d) {
         Leg& l = p.leg[i];
         const int k = i < 3 ? 3 : 1;
         l.cin = cin[i]; l.cout = co[i]; l.G = std::min(32, l.cin);
-        l.e = enc::layer(enc::LayerSpec{l.cin, l.cout, k, 1, k / 2, 0, 0, 0}, d->N, d->H, d->W);
+        l.e = enc::layer(enc::LayerSpec{l.cin, l.cout, k, 1, k / 2, 0, 0, 0, arith}, d->N, d->H, d->W);
         l.nchunks = enc::stats_chunks(d->N, p.HW, l.cin, &l.stat_doubles);
         l.ss = st; st += (size_t)2 * d->N * l.cin;
         l.mr = st; st += (size_t)2 * d->N * l.G;
@@ -93,17 +95,21 @@ Plan plan(const kpn_conv_block_desc* d) {
 
 #define KPN_BLOCK_REQUIRE_DESC(desc) do { if (const char* e_ = blk::desc_error(desc)) return fail(KPN_EINVAL, std::string("kpn_conv_block_desc: ") + e_); } while (0)
 
-extern "C" size_t kpn_conv_block_workspace_bytes(const kpn_conv_block_desc* desc) {
-    return blk::desc_error(desc) ? 0 : blk::plan(desc).bytes;
+#define KPN_BLOCK_REQUIRE_ARITH(arith) do { if (const char* e_ = enc::arith_error(arith)) return fail(KPN_EINVAL, std::string("kpn_conv_block_ex: ") + e_); } while (0)
+
+// The four entry points with the arithmetic chosen by the caller; kpn_conv_block_* below are their arith = KPN_CONV_F32 case.
+extern "C" size_t kpn_conv_block_ex_workspace_bytes(const kpn_conv_block_desc* desc, int32_t arith) {
+    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).bytes;
 }
-extern "C" size_t kpn_conv_block_state_floats(const kpn_conv_block_desc* desc) {
-    return blk::desc_error(desc) ? 0 : blk::plan(desc).state_floats;
+extern "C" size_t kpn_conv_block_ex_state_floats(const kpn_conv_block_desc* desc, int32_t arith) {
+    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).state_floats;
 }
-extern "C" int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const float* x, const kpn_conv_block_params* params, float* y,
-                                      float* state, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int kpn_conv_block_ex_forward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const kpn_conv_block_params* params,
+                                         float* y, float* state, void* workspace, size_t workspace_bytes, void* stream) {
     KPN_BLOCK_REQUIRE_DESC(desc);
+    KPN_BLOCK_REQUIRE_ARITH(arith);
     KPN_REQUIRE(x && params && y && state && workspace, "null pointer");
-    const blk::Plan p = blk::plan(desc);
+    const blk::Plan p = blk::plan(desc, arith);
     for (int i = 0; i < p.nlegs; ++i) {
         KPN_REQUIRE(params->gamma[i] && params->beta[i] && params->packed[i], "params: gamma / beta / packed of a leg is null");
         KPN_REQUIRE(enc::aligned16({params->gamma[i], params->beta[i], params->packed[i]}), "params: gamma / beta / packed must be 16-byte aligned");
@@ -143,12 +149,13 @@ extern "C" int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const flo
     enc::launch_add_cs(state, p.cs, base, base_cs, y, c, p.P, p.cs, stream);
     return check_launch("kpn_conv_block_forward");
 }
-extern "C" int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
-                                       const float* state, float* dx, const kpn_conv_block_grads* grads, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
+extern "C" int kpn_conv_block_ex_backward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const float* dy,
+                                          const kpn_conv_block_params* params, const float* state, float* dx, const kpn_conv_block_grads* grads,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
     KPN_BLOCK_REQUIRE_DESC(desc);
+    KPN_BLOCK_REQUIRE_ARITH(arith);
     KPN_REQUIRE(x && dy && params && state && grads && workspace, "null pointer");
-    const blk::Plan p = blk::plan(desc);
+    const blk::Plan p = blk::plan(desc, arith);
     for (int i = 0; i < p.nlegs; ++i) {
         KPN_REQUIRE(params->gamma[i] && params->packed[i], "params: gamma / packed of a leg is null");
         KPN_REQUIRE(enc::aligned16({params->gamma[i], params->packed[i], grads->dgamma[i], grads->dbeta[i], grads->dw[i]}),
@@ -192,4 +199,16 @@ extern "C" int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const fl
     if (up2) leg(0, x, desc->cin, g1, c / 2, up1 ? dx : nullptr, down ? nullptr : dy, c);
     if (down) leg(3, x, desc->cin, dy, c, dx, dx, desc->cin);
     return check_launch("kpn_conv_block_backward");
+}
+
+extern "C" size_t kpn_conv_block_workspace_bytes(const kpn_conv_block_desc* desc) { return kpn_conv_block_ex_workspace_bytes(desc, KPN_CONV_F32); }
+extern "C" size_t kpn_conv_block_state_floats(const kpn_conv_block_desc* desc) { return kpn_conv_block_ex_state_floats(desc, KPN_CONV_F32); }
+extern "C" int kpn_conv_block_forward(const kpn_conv_block_desc* desc, const float* x, const kpn_conv_block_params* params, float* y,
+                                      float* state, void* workspace, size_t workspace_bytes, void* stream) {
+    return kpn_conv_block_ex_forward(desc, KPN_CONV_F32, x, params, y, state, workspace, workspace_bytes, stream);
+}
+extern "C" int kpn_conv_block_backward(const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
+                                       const float* state, float* dx, const kpn_conv_block_grads* grads, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return kpn_conv_block_ex_backward(desc, KPN_CONV_F32, x, dy, params, state, dx, grads, workspace, workspace_bytes, stream);
 }

@@ -26,3 +26,32 @@ struct conv_family {
     static enc::LayerSpec spec_of(const Desc* d) { return enc::LayerSpec{d->cin, d->cout, d->k, 1, d->pad, 0, 0, 0}; }
 };
 KPN_SINGLE_LAYER(conv_family, kpn_conv2d)
+
+// The same six with the arithmetic of the GEMMs chosen by the caller (include/kpnerf.h): arith = KPN_CONV_F32 is the code above, bit for
+// bit; KPN_CONV_BF16X3 runs encoder_split_kernels.hip, with its own tiles, packed size, split K and ranges.  An unknown arith is refused
+// (the size queries return 0) before anything is launched.
+#define KPN_CONV_EX_REQUIRE_ARITH(arith) do { if (const char* e_ = enc::arith_error(arith)) return fail(KPN_EINVAL, std::string("kpn_conv2d_ex: ") + e_); } while (0)
+extern "C" size_t kpn_conv2d_ex_packed_floats(const kpn_conv2d_desc* desc, int32_t arith) {
+    return enc::arith_error(arith) ? 0 : enc::single_packed_floats<conv_family>(desc, arith);
+}
+extern "C" int kpn_conv2d_ex_pack_device(const kpn_conv2d_desc* desc, int32_t arith, const float* w, float* packed, void* stream) {
+    KPN_CONV_EX_REQUIRE_ARITH(arith);
+    return enc::single_pack<conv_family>("kpn_conv2d", "kpn_conv2d_ex_pack_device", desc, w, packed, stream, arith);
+}
+extern "C" size_t kpn_conv2d_ex_workspace_bytes(const kpn_conv2d_desc* desc, int32_t arith) {
+    return enc::arith_error(arith) ? 0 : enc::single_workspace_bytes<conv_family>(desc, arith);
+}
+extern "C" int32_t kpn_conv2d_ex_wgrad_ranges(const kpn_conv2d_desc* desc, int32_t arith) {
+    return enc::arith_error(arith) ? 0 : enc::single_wgrad_ranges<conv_family>(desc, arith);
+}
+extern "C" int kpn_conv2d_ex_forward(const kpn_conv2d_desc* desc, int32_t arith, const float* x, const float* packed, const float* bias, float* y,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    KPN_CONV_EX_REQUIRE_ARITH(arith);
+    return enc::single_forward<conv_family>("kpn_conv2d", "kpn_conv2d_ex_forward", desc, x, packed, bias, y, workspace, workspace_bytes, stream, arith);
+}
+extern "C" int kpn_conv2d_ex_backward(const kpn_conv2d_desc* desc, int32_t arith, const float* x, const float* dy, const float* packed, float* dx,
+                                      float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    KPN_CONV_EX_REQUIRE_ARITH(arith);
+    return enc::single_backward<conv_family>("kpn_conv2d", "kpn_conv2d_ex_backward", desc, x, dy, packed, dx, dw, db, workspace, workspace_bytes,
+                                             stream, arith);
+}

@@ -16,19 +16,27 @@ namespace enc {
 inline dim3 grid4(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)); }
 
 // one k_enc_conv GEMM: cin -> cout over nimg * Ho * Wo rows (DECONV: (Ho, Wo) is the source grid, one GEMM per parity class)
+// The arithmetic of a GEMM (KPN_CONV_F32 / KPN_CONV_BF16X3, include/kpnerf.h) is part of its geometry: tile, K chunk, packed size, the
+// split-K rule's inputs and the weight-gradient plan follow from it, and every launch below dispatches on it.  KPN_CONV_BF16X3 exists
+// for the plain NHWC stride-1 GEMM only (encoder_split_kernels.hip): no stem, no deconv, no replication padding.
 struct ConvGeom {
     kpn_enc_conv_args a;   // what the geometry decides (sizes, cin_p, cout_p, nk, wofs, ksplit); the caller adds tensors, padding, epilogue
-    int bn, bm;            // tile: 64 x 64, or 128 x 32 for at most 32 output channels
+    int arith;
+    int bn, bm;            // tile: 64 x 64, or 128 x 32 for at most 32 output channels; KPN_CONV_BF16X3: 128 x 64, or 256 x 32
     int deconv, ncls;      // parity classes: 4 or 1
     int64_t packed;        // floats: the packed weight, every class
     int64_t M;             // GEMM rows
     int64_t partial;       // floats: the split-K scratch, 0 without a split
 };
-inline ConvGeom conv_geom(int nimg, int Ho, int Wo, int cin, int cout, int kh, int kw, int deconv) {
+inline ConvGeom conv_geom(int nimg, int Ho, int Wo, int cin, int cout, int kh, int kw, int deconv, int arith = KPN_CONV_F32) {
     ConvGeom g{};
     kpn_enc_conv_args& a = g.a;
     a.nimg = nimg; a.Ho = Ho; a.Wo = Wo; a.cin = cin; a.cout = cout; a.kh = kh; a.kw = kw;
-    g.bn = cout > 32 ? 64 : 32; g.bm = g.bn == 64 ? 64 : 128;
+    g.arith = arith;
+    const bool b3 = arith == KPN_CONV_BF16X3;
+    g.bn = cout > 32 ? 64 : 32; g.bm = (g.bn == 64 ? 64 : 128) * (b3 ? 2 : 1);
+    const int kc = b3 ? 32 : 16;                    // K chunk
+    const int cfl = b3 ? 48 : 16;                   // floats of the packed weight per chunk and output channel (bf16 x 3: 32 x 6 bytes)
     // the 3-channel stems pad to 4; api_conv.hip admits only cin % 4 == 0, for which cin_p == cin: one formula serves both
     a.cin_p = (cin + 3) / 4 * 4;
     a.cout_p = (cout + g.bn - 1) / g.bn * g.bn;
@@ -36,9 +44,9 @@ inline ConvGeom conv_geom(int nimg, int Ho, int Wo, int cin, int cout, int kh, i
     int nkmin = 1 << 30;
     for (int c = 0; c < g.ncls; ++c) {
         const int taps = deconv ? (1 + (c >> 1)) * (1 + (c & 1)) : kh * kw;
-        a.nk[c] = (taps * a.cin_p + 15) / 16;
+        a.nk[c] = (taps * a.cin_p + kc - 1) / kc;
         a.wofs[c] = g.packed;
-        g.packed += (int64_t)a.nk[c] * a.cout_p * 16;
+        g.packed += (int64_t)a.nk[c] * a.cout_p * cfl;
         nkmin = std::min(nkmin, a.nk[c]);
     }
     // split K by the per-image geometry only: an image's result must not depend on how many images are encoded with it
@@ -52,7 +60,10 @@ inline ConvGeom conv_geom(int nimg, int Ho, int Wo, int cin, int cout, int kh, i
 // `a`: g.a with the caller's fields filled in
 inline void launch_conv(const kpn_enc_conv_args& a, const ConvGeom& g, int stem, void* stream) {
     const dim3 grid((unsigned)((g.M + g.bm - 1) / g.bm * (a.cout_p / g.bn)), (unsigned)a.ksplit, (unsigned)g.ncls);
-    if (stem) {
+    if (g.arith == KPN_CONV_BF16X3) {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_conv_b3<128, 64>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_conv_b3<256, 32>), grid, dim3(256), stream, a);
+    } else if (stem) {
         if (g.bn == 64) KPN_LAUNCH((k_enc_conv<64, 64, true, false>), grid, dim3(256), stream, a);
         else KPN_LAUNCH((k_enc_conv<128, 32, true, false>), grid, dim3(256), stream, a);
     } else if (g.deconv) {
@@ -77,13 +88,19 @@ inline void launch_conv_rp_adjoint(const kpn_enc_conv_args& a, const ConvGeom& g
 inline void launch_pack(const ConvGeom& g, int tflip, const float* w, float* wp, void* stream) {
     for (int c = 0; c < g.ncls; ++c) {
         kpn_enc_pack_args pa{w, wp + g.a.wofs[c], g.a.cin, g.a.cin_p, g.a.cout, g.a.cout_p, g.a.kh, g.a.kw, g.a.nk[c], g.deconv, c, tflip};
+        if (g.arith == KPN_CONV_BF16X3) {       // one thread per 16-byte unit of each piece
+            const int64_t n = (int64_t)g.a.nk[c] * g.a.cout_p * 4;
+            KPN_LAUNCH(k_enc_pack_b3, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), stream, pa);
+            continue;
+        }
         const int64_t n = (int64_t)g.a.nk[c] * g.a.cout_p * 16;
         KPN_LAUNCH(k_enc_pack, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), stream, pa);
     }
 }
 // The weight gradient of the GEMM `g` (k_enc_wgrad on g's tile over (K rows, cout), then k_enc_wgrad_combine).  Its ranges: a range is
 // `cpr` chunks of 16 GEMM pixels, at least 20 (320 pixels: what a tile's store and combine are worth) and otherwise as many as leave
-// about 1024 workgroups, at most 64 ranges.  From the shape alone.
+// about 1024 workgroups, at most 64 ranges.  From the shape alone - and the arithmetic, whose tile (g.bm x g.bn) counts the tiles:
+// k_enc_wgrad_b3 takes 128 x 64 / 256 x 32 of (K rows, cout), so it has half the tiles and may take twice the ranges.
 struct WgradPlan {
     int krows;                     // kh * kw * cin: the rows of `partial` and of dW
     int tiles, nchunks, cpr, nranges;
@@ -111,7 +128,10 @@ inline void launch_wgrad(const kpn_enc_conv_args& c, const ConvGeom& g, const Wg
     a.rhs = rhs; a.rhs_cs = rhs_cs; a.rhs_ss = rhs_ss; a.rhs_relu = rhs_ss != nullptr; a.krows = p.krows; a.nchunks = p.nchunks; a.cpr = p.cpr; a.nranges = p.nranges;
     a.partial = partial; a.dw = dw;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.nranges);
-    if (stem) {
+    if (g.arith == KPN_CONV_BF16X3) {
+        if (g.bn == 64) KPN_LAUNCH((k_enc_wgrad_b3<128, 64>), grid, dim3(256), stream, a);
+        else KPN_LAUNCH((k_enc_wgrad_b3<256, 32>), grid, dim3(256), stream, a);
+    } else if (stem) {
         if (g.bn == 64) KPN_LAUNCH((k_enc_wgrad<64, 64, true>), grid, dim3(256), stream, a);
         else KPN_LAUNCH((k_enc_wgrad<128, 32, true>), grid, dim3(256), stream, a);
     } else {

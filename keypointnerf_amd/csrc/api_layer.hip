@@ -12,7 +12,10 @@
 //                                                                                       dw = A from x through the clamped load
 //   stem (k 7; zero pad with stride 2, or replicate): reads an NCHW tensor as it is (stem_plain), K rows tap * 4 + ci, no dx
 namespace enc {
-struct LayerSpec { int cin, cout, k, stride, pad, replicate, transposed, stem; };
+struct LayerSpec {
+    int cin, cout, k, stride, pad, replicate, transposed, stem;
+    int arith = KPN_CONV_F32;  // KPN_CONV_BF16X3: the zero-padded stride-1 layer only (the first row of the table above)
+};
 struct Layer {
     LayerSpec s;
     int N, Hi, Wi, Ho, Wo;     // the grids of the layer's input and output
@@ -35,9 +38,9 @@ inline Layer layer(const LayerSpec& s, int N, int Hi, int Wi) {
         l.fwd = conv_geom(N, Hi, Wi, s.cin, s.cout, s.k, s.k, 1);                      // x (H, W) -> y (2 H, 2 W)
         l.dx = conv_geom(N, Hi, Wi, s.cout, s.cin, s.k, s.k, 0);                       // dy (2 H, 2 W) -> dx (H, W), stride 2
     } else {
-        l.fwd = conv_geom(N, l.Ho, l.Wo, s.cin, s.cout, s.k, s.k, 0);
+        l.fwd = conv_geom(N, l.Ho, l.Wo, s.cin, s.cout, s.k, s.k, 0, s.arith);
         if (l.has_dx) l.dx = s.stride == 2 ? conv_geom(N, l.Ho, l.Wo, s.cout, s.cin, s.k, s.k, 1)      // dy (Ho, Wo) -> dx (2 Ho, 2 Wo)
-                                           : conv_geom(N, Hi, Wi, s.cout, s.cin, s.k, s.k, 0);
+                                           : conv_geom(N, Hi, Wi, s.cout, s.cin, s.k, s.k, 0, s.arith);
     }
     l.wg = s.transposed ? l.dx : l.fwd;
     l.wgp = wgrad_plan(l.wg);
@@ -123,22 +126,29 @@ inline SingleLayerWorkspace single_layer_workspace(const Layer& l) {
     return w;
 }
 inline int single_fail(const char* name, const char* e) { return fail(KPN_EINVAL, std::string(name) + "_desc: " + e); }
-template <class F> Layer single_layer(const typename F::Desc* d) { return layer(F::spec_of(d), d->N, d->H, d->W); }
-template <class F> size_t single_packed_floats(const typename F::Desc* desc) {
-    return F::weight_error(desc) ? 0 : pack_layer(F::spec_of(desc)).packed_floats;
+// `arith`: the arithmetic of the layer's GEMMs, checked by the caller (the _ex entry points of api_conv.hip; every other family passes
+// none and runs KPN_CONV_F32)
+inline const char* arith_error(int32_t arith) {
+    return arith == KPN_CONV_F32 || arith == KPN_CONV_BF16X3 ? nullptr : "arith must be KPN_CONV_F32 (0) or KPN_CONV_BF16X3 (1)";
 }
-template <class F> int single_pack(const char* name, const char* what, const typename F::Desc* desc, const float* w, float* packed, void* stream) {
+template <class F> LayerSpec single_spec(const typename F::Desc* d, int arith) { LayerSpec s = F::spec_of(d); s.arith = arith; return s; }
+template <class F> Layer single_layer(const typename F::Desc* d, int arith) { return layer(single_spec<F>(d, arith), d->N, d->H, d->W); }
+template <class F> size_t single_packed_floats(const typename F::Desc* desc, int arith = KPN_CONV_F32) {
+    return F::weight_error(desc) ? 0 : pack_layer(single_spec<F>(desc, arith)).packed_floats;
+}
+template <class F> int single_pack(const char* name, const char* what, const typename F::Desc* desc, const float* w, float* packed, void* stream,
+                                   int arith = KPN_CONV_F32) {
     if (const char* e = F::weight_error(desc)) return single_fail(name, e);
     KPN_REQUIRE(w && packed, "null pointer");
     KPN_REQUIRE(((uintptr_t)packed & 15) == 0, "packed must be 16-byte aligned");
-    layer_pack(pack_layer(F::spec_of(desc)), w, packed, stream);
+    layer_pack(pack_layer(single_spec<F>(desc, arith)), w, packed, stream);
     return check_launch(what);
 }
-template <class F> size_t single_workspace_bytes(const typename F::Desc* desc) {
-    return F::desc_error(desc) ? 0 : single_layer_workspace(single_layer<F>(desc)).bytes;
+template <class F> size_t single_workspace_bytes(const typename F::Desc* desc, int arith = KPN_CONV_F32) {
+    return F::desc_error(desc) ? 0 : single_layer_workspace(single_layer<F>(desc, arith)).bytes;
 }
-template <class F> int32_t single_wgrad_ranges(const typename F::Desc* desc) {
-    return F::desc_error(desc) ? 0 : single_layer<F>(desc).wgp.nranges;
+template <class F> int32_t single_wgrad_ranges(const typename F::Desc* desc, int arith = KPN_CONV_F32) {
+    return F::desc_error(desc) ? 0 : single_layer<F>(desc, arith).wgp.nranges;
 }
 // the alignment and workspace requirements of the forward (dy NULL, lead "") and the backward (lead "dy / ")
 template <class F> int single_require(const char* name, const Layer& l, const SingleLayerWorkspace& w, const char* lead, const void* x,
@@ -153,11 +163,12 @@ template <class F> int single_require(const char* name, const Layer& l, const Si
     return KPN_OK;
 }
 template <class F> int single_forward(const char* name, const char* what, const typename F::Desc* desc, const float* x, const float* packed,
-                                      const float* bias, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+                                      const float* bias, float* y, void* workspace, size_t workspace_bytes, void* stream,
+                                      int arith = KPN_CONV_F32) {
     if (const char* e = F::desc_error(desc)) return single_fail(name, e);
     KPN_REQUIRE(x && packed && y && workspace, "null pointer");
     KPN_REQUIRE((bias != nullptr) == (desc->has_bias != 0), "bias must be given exactly when has_bias is set");
-    const Layer l = single_layer<F>(desc);
+    const Layer l = single_layer<F>(desc, arith);
     const SingleLayerWorkspace w = single_layer_workspace(l);
     if (const int rc = single_require<F>(name, l, w, "", x, nullptr, packed, workspace, workspace_bytes)) return rc;
     float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.o_fwd);
@@ -166,10 +177,10 @@ template <class F> int single_forward(const char* name, const char* what, const 
 }
 template <class F> int single_backward(const char* name, const char* what, const typename F::Desc* desc, const float* x, const float* dy,
                                        const float* packed, float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
+                                       void* stream, int arith = KPN_CONV_F32) {
     if (const char* e = F::desc_error(desc)) return single_fail(name, e);
     KPN_REQUIRE(dy && workspace, "null pointer");
-    const Layer l = single_layer<F>(desc);
+    const Layer l = single_layer<F>(desc, arith);
     if constexpr (F::nchw_stem) KPN_REQUIRE(!dx || l.has_dx, std::string("dx must be NULL for ") + F::stem_name + " (the stem has no input gradient)");
     KPN_REQUIRE(!dx || packed, "packed is null (the input gradient reads it)");
     KPN_REQUIRE(!dw || x, "x is null (the weight gradient reads it)");

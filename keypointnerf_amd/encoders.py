@@ -355,7 +355,19 @@ def _rebind_forward(module, key, candidate, ineligible, make_forward):
 
 
 # ---- training convolutions natively: torch.ops.kpnerf.conv2d behind the nn.Conv2d instances of a module tree ----
-def _conv_ineligible(m):
+# The installers of the stride-1 convolutions and of the ConvBlocks take ``arith``: "f32" (the default: the fp32 MFMA kernels) or "bf16x3"
+# (every operand as three bf16 pieces on the 16-bit MFMA, csrc/encoder_split_kernels.hip; torch.ops.kpnerf.conv2d_arith /
+# conv_block_arith).  The stems, the stride-2, transposed and replication-padded layers have no split kernel and stay on their fp32 ones.
+_ARITH = {"f32": 0, "bf16x3": 1}
+
+
+def _arith_code(arith):
+    if arith not in _ARITH:
+        raise ValueError(f'arith must be "f32" or "bf16x3", got {arith!r}')
+    return _ARITH[arith]
+
+
+def _conv_ineligible(m, arith=0):
     """None if kpn_conv2d_* serves this nn.Conv2d, else the reason it is left on torch"""
     k, s, p, d = _pair(m.kernel_size), _pair(m.stride), m.padding, _pair(m.dilation)
     if isinstance(p, str):
@@ -373,12 +385,12 @@ def _conv_ineligible(m):
         return f"kernel_size={k} (1, 3 or 5, square)"
     if p[0] != p[1] or not 0 <= p[0] <= k[0] - 1:
         return f"padding={p} (0 .. k - 1, the same on both axes)"
-    if m.in_channels % 4 or m.out_channels % 4 or not ops.conv2d_supported(m.in_channels, m.out_channels, k[0]):
+    if m.in_channels % 4 or m.out_channels % 4 or not ops.conv2d_supported(m.in_channels, m.out_channels, k[0], arith):
         return f"channels {m.in_channels} -> {m.out_channels} (multiples of 4, at most 1024)"
     return None
 
 
-def install_native_convs(module):
+def install_native_convs(module, arith="f32"):
     """Opt-in: rebinds ``forward`` on every eligible ``nn.Conv2d`` instance under ``module`` to torch.ops.kpnerf.conv2d, forward and
     backward in HIP (kpn_conv2d_forward / kpn_conv2d_backward).  Eligible: groups = 1, dilation = 1, stride 1, a square kernel of
     1, 3 or 5, zero padding 0 .. k - 1 (``padding_mode="zeros"``), channel counts that are multiples of 4.  Every other layer
@@ -386,16 +398,21 @@ def install_native_convs(module):
     calls the module's own forward for anything else; its result is channels_last.  The module tree, the parameter names and the
     state_dict are untouched.  Independent of ``install_encoders``: both may be installed on one ``net`` (the whole-network
     native forward still wins where it is served).  Returns (served, left): the names served, and {name: reason} of the
-    nn.Conv2d layers left alone."""
+    nn.Conv2d layers left alone.  ``arith="bf16x3"``: every served layer runs torch.ops.kpnerf.conv2d_arith on three bf16 pieces per
+    operand (kpn_conv2d_ex_*); the same layers are eligible."""
+    a = _arith_code(arith)
+
     def make_forward(_prev):
         def forward(self, x):
             if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
                     and self.weight.is_cuda and self.weight.dtype == torch.float32):
                 return _prev(x)
+            if a:
+                return torch.ops.kpnerf.conv2d_arith(x, self.weight, self.bias, _pair(self.padding)[0], a)
             return torch.ops.kpnerf.conv2d(x, self.weight, self.bias, _pair(self.padding)[0])
         return forward
 
-    return _rebind_forward(module, "_kpnerf_conv_saved", lambda m: type(m) is torch.nn.Conv2d, lambda m, name: _conv_ineligible(m),
+    return _rebind_forward(module, "_kpnerf_conv_saved", lambda m: type(m) is torch.nn.Conv2d, lambda m, name: _conv_ineligible(m, a),
                            make_forward)
 
 
@@ -486,13 +503,13 @@ def _block_ineligible(m, name):
     return None
 
 
-def _fused_block_ineligible(m, name):
+def _fused_block_ineligible(m, name, arith=0):
     """_block_ineligible, and that kpn_conv_block_* serves the widths and every norm has one eps"""
     why = _block_ineligible(m, name)
     if why is not None:
         return why
     cin, cout = m.bn1.num_channels, 2 * m.conv1.out_channels
-    if not ops.conv_block_supported(cin, cout):
+    if not ops.conv_block_supported(cin, cout, arith):
         return f"channels {cin} -> {cout} (the single-operator block serves at most 1024 output channels behind a downsample leg)"
     eps = {float(getattr(m, f"bn{i}").eps) for i in range(1, 5 if cin != cout else 4)}
     if len(eps) != 1:
@@ -500,7 +517,7 @@ def _fused_block_ineligible(m, name):
     return None
 
 
-def install_native_blocks(module, fused=False):
+def install_native_blocks(module, fused=False, arith="f32"):
     """Opt-in: rebinds ``forward`` on every ConvBlock under ``module`` whose structure is the reference's (src/utils.py:416-474; the
     check the native encoder makes) to the same dataflow on the project's kernels: each ``bn -> nl -> conv`` leg, the downsample leg
     included, is torch.ops.kpnerf.group_norm(relu=True) followed by torch.ops.kpnerf.conv2d; ``torch.cat`` and the residual add
@@ -512,7 +529,13 @@ def install_native_blocks(module, fused=False):
     autograd node per block, no aten operator inside it - the norms and the ReLUs run in the loads of the convolutions, forward and
     backward, the convolutions write their slices of the concatenation, the residual is added once - and x plus 3/4 of an
     output-sized tensor kept for the backward instead of every leg's input and normalised input.  Its forward has the bits of the
-    unfused path.  ``NativeTraining.fused_block_calls`` counts these calls (``block_calls`` the unfused ones)."""
+    unfused path.  ``NativeTraining.fused_block_calls`` counts these calls (``block_calls`` the unfused ones).
+
+    ``arith="bf16x3"``: the convolutions of every served block run on three bf16 pieces per operand - torch.ops.kpnerf.conv2d_arith per leg,
+    or torch.ops.kpnerf.conv_block_arith with ``fused=True`` (whose forward again has the bits of the unfused path in that arithmetic).  The
+    norms do not change."""
+    a = _arith_code(arith)
+
     def make_fused(_prev):
         def forward(self, x):
             if not _native_input(x, *self.parameters()):
@@ -521,11 +544,15 @@ def install_native_blocks(module, fused=False):
             legs = [(self.bn1, self.conv1), (self.bn2, self.conv2), (self.bn3, self.conv3)]
             if self.downsample is not None:
                 legs.append((self.bn4, self.downsample[2]))
-            return torch.ops.kpnerf.conv_block(x, [t for bn, conv in legs for t in (bn.weight, bn.bias, conv.weight)], self.bn1.eps)
+            tensors = [t for bn, conv in legs for t in (bn.weight, bn.bias, conv.weight)]
+            if a:
+                return torch.ops.kpnerf.conv_block_arith(x, tensors, self.bn1.eps, a)
+            return torch.ops.kpnerf.conv_block(x, tensors, self.bn1.eps)
         return forward
 
     if fused:
-        return _rebind_forward(module, "_kpnerf_block_saved", lambda m: type(m).__name__ == "ConvBlock", _fused_block_ineligible, make_fused)
+        return _rebind_forward(module, "_kpnerf_block_saved", lambda m: type(m).__name__ == "ConvBlock",
+                               lambda m, name: _fused_block_ineligible(m, name, a), make_fused)
 
     def make_forward(_prev):
         def forward(self, x):
@@ -535,6 +562,8 @@ def install_native_blocks(module, fused=False):
 
             def leg(bn, conv, t, pad):
                 t = torch.ops.kpnerf.group_norm(t, bn.weight, bn.bias, bn.num_groups, bn.eps, True)
+                if a:
+                    return torch.ops.kpnerf.conv2d_arith(t, conv.weight, None, pad, a)
                 return torch.ops.kpnerf.conv2d(t, conv.weight, None, pad)
 
             o1 = leg(self.bn1, self.conv1, x, 1)
@@ -711,7 +740,7 @@ def _geo_ineligible(m, name):
 _GEO_PARTS = ("strided", "convs", "norms", "blocks", "hourglass")
 
 
-def install_native_geo(module, fused_blocks=False):
+def install_native_geo(module, fused_blocks=False, arith="f32"):
     """Opt-in: trains every HGFilterV2 under ``module`` (``module`` itself included) on the project's kernels.  An HGFilterV2 whose
     structure is the reference's (src/utils.py:322-414: its children for any ``n_stack`` >= 1, ``norm="group"``, ``hd`` either way) gets
     ``install_native_strided``, ``install_native_convs``, ``install_native_norms``, ``install_native_blocks`` and
@@ -723,7 +752,14 @@ def install_native_geo(module, fused_blocks=False):
     parameter names and the state_dict are untouched.  Returns {installer: (served, left)} for "geo" and the five installers, the
     names relative to ``module``; a layer that one of the five leaves because it is another's (the stride-2 stem among the
     nn.Conv2d) is not listed as left.  ``fused_blocks=True`` installs the ConvBlocks as ``install_native_blocks(fused=True)`` does:
-    one torch.ops.kpnerf.conv_block per block, and no ``torch.cat`` or residual add left inside a block."""
+    one torch.ops.kpnerf.conv_block per block, and no ``torch.cat`` or residual add left inside a block.
+
+    ``arith="bf16x3"``: the stride-1 convolutions and the ConvBlocks (``install_native_convs`` / ``install_native_blocks`` with the same
+    keyword) run on three bf16 pieces per operand; the stem and the transposed convolution of ``unpack1`` have no such kernel and stay on
+    their fp32 ones.  The report then has one more entry, ``"arith": {"bf16x3": [names], "f32": [names]}``: the served convolution
+    layers and blocks on each arithmetic.  Any other value raises ValueError; the default leaves the report as it was."""
+    _arith_code(arith)
+
     def make_forward(_prev):
         def forward(self, x):
             if not _native_input(x, *self.parameters()) or (((x.shape[2] - 1) // 2 + 1) % 2 or ((x.shape[3] - 1) // 2 + 1) % 2):
@@ -753,8 +789,8 @@ def install_native_geo(module, fused_blocks=False):
     report = {k: ([], {}) for k in _GEO_PARTS}
     subs = dict(module.named_modules())
     for name in served:
-        for part, fn in zip(_GEO_PARTS, (install_native_strided, install_native_convs, install_native_norms,
-                                         lambda m: install_native_blocks(m, fused=fused_blocks), install_native_hourglass)):
+        for part, fn in zip(_GEO_PARTS, (install_native_strided, lambda m: install_native_convs(m, arith=arith), install_native_norms,
+                                         lambda m: install_native_blocks(m, fused=fused_blocks, arith=arith), install_native_hourglass)):
             s_, l_ = fn(subs[name])
             pre = name + "." if name else ""
             report[part][0].extend(pre + n for n in s_)
@@ -764,6 +800,11 @@ def install_native_geo(module, fused_blocks=False):
         for n in [n for n in report[part][1] if n in everything]:
             del report[part][1][n]
     report["geo"] = (served, left)
+    if arith != "f32":
+        # a convolution inside a served block is the block's: listed once, under the block
+        blocks = report["blocks"][0]
+        own = [n for n in report["convs"][0] if not any(n.startswith(b + ".") for b in blocks)]
+        report["arith"] = {arith: sorted(own + blocks), "f32": sorted(report["strided"][0])}
     return report
 
 

@@ -81,6 +81,10 @@ class AdamArgs(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
 
 
+# the arithmetic of the stride-1 convolution's GEMMs (kpn_conv2d_ex_*, kpn_conv_block_ex_*)
+CONV_F32, CONV_BF16X3 = 0, 1
+
+
 class Conv2dDesc(ctypes.Structure):
     """struct kpn_conv2d_desc"""
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "cin", "cout", "k", "pad", "has_bias")]
@@ -234,6 +238,13 @@ _SIGNATURES = {
     "kpn_conv2d_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dDesc)]),
     "kpn_conv2d_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv2d_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    # the same six with the arithmetic (CONV_F32 / CONV_BF16X3) behind the descriptor
+    "kpn_conv2d_ex_packed_floats": (c_sz, [ctypes.POINTER(Conv2dDesc), c_i32]),
+    "kpn_conv2d_ex_pack_device": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_i32, c_p, c_p, c_p]),
+    "kpn_conv2d_ex_workspace_bytes": (c_sz, [ctypes.POINTER(Conv2dDesc), c_i32]),
+    "kpn_conv2d_ex_wgrad_ranges": (c_i32, [ctypes.POINTER(Conv2dDesc), c_i32]),
+    "kpn_conv2d_ex_forward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_i32, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_conv2d_ex_backward": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv2d_s2_packed_floats": (c_sz, [ctypes.POINTER(Conv2dS2Desc)]),
     "kpn_conv2d_s2_pack_device": (ctypes.c_int, [ctypes.POINTER(Conv2dS2Desc), c_p, c_p, c_p]),
     "kpn_conv2d_s2_workspace_bytes": (c_sz, [ctypes.POINTER(Conv2dS2Desc)]),
@@ -255,6 +266,12 @@ _SIGNATURES = {
     "kpn_conv_block_forward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p, c_p, c_sz, c_p]),
     "kpn_conv_block_backward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_p, c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p,
                                                ctypes.POINTER(ConvBlockGrads), c_p, c_sz, c_p]),
+    "kpn_conv_block_ex_workspace_bytes": (c_sz, [ctypes.POINTER(ConvBlockDesc), c_i32]),
+    "kpn_conv_block_ex_state_floats": (c_sz, [ctypes.POINTER(ConvBlockDesc), c_i32]),
+    "kpn_conv_block_ex_forward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_i32, c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p, c_p, c_sz,
+                                                 c_p]),
+    "kpn_conv_block_ex_backward": (ctypes.c_int, [ctypes.POINTER(ConvBlockDesc), c_i32, c_p, c_p, ctypes.POINTER(ConvBlockParams), c_p, c_p,
+                                                  ctypes.POINTER(ConvBlockGrads), c_p, c_sz, c_p]),
     "kpn_res_encoder_layers": (c_i32, [ctypes.POINTER(ResEncoderDesc)]),
     "kpn_res_encoder_workspace_bytes": (c_sz, [ctypes.POINTER(ResEncoderDesc)]),
     "kpn_res_encoder_state_floats": (c_sz, [ctypes.POINTER(ResEncoderDesc)]),

@@ -942,6 +942,44 @@ def _conv_desc(N, H, W, cin, cout, k, padding, has_bias):
     return d
 
 
+# The arithmetic of the convolution's GEMMs (include/kpnerf.h): ``arith`` = kl.CONV_F32 (0, the default: v_mfma_f32_32x32x2_f32) or
+# kl.CONV_BF16X3 (1: three bf16 pieces per operand on v_mfma_f32_32x32x16_bf16, csrc/encoder_split_kernels.hip).  A packed weight, a
+# workspace and a block's packed legs belong to one arithmetic.
+class _ArithLibrary:
+    """kpn_conv2d_<f> and kpn_conv_block_<f> of the library as their _ex forms with one arith; everything else is the library's"""
+
+    def __init__(self, L, arith):
+        self._L, self._arith = L, arith
+
+    def __getattr__(self, name):
+        for fam in ("kpn_conv2d_", "kpn_conv_block_"):
+            if name.startswith(fam) and not name[len(fam):].startswith(("s2_", "rp_", "ex_")):
+                fn, arith = getattr(self._L, fam + "ex_" + name[len(fam):]), self._arith
+
+                def call(desc, *a):
+                    return fn(desc, arith, *a)
+                call.argtypes = [fn.argtypes[0]] + list(fn.argtypes[2:])
+                setattr(self, name, call)       # looked up once per library and name
+                return call
+        return getattr(self._L, name)
+
+
+_ARITH_LIBRARIES = {}
+
+
+def _conv_library(arith):
+    """the library whose kpn_conv2d_* / kpn_conv_block_* run in ``arith``: the plain entry points for CONV_F32"""
+    if arith not in (kl.CONV_F32, kl.CONV_BF16X3):
+        raise ValueError(f"arith must be CONV_F32 ({kl.CONV_F32}) or CONV_BF16X3 ({kl.CONV_BF16X3}), got {arith!r}")
+    L = kl.get_library()
+    if arith == kl.CONV_F32:
+        return L
+    key = (id(L), arith)
+    if key not in _ARITH_LIBRARIES:
+        _ARITH_LIBRARIES[key] = _ArithLibrary(L, arith)
+    return _ARITH_LIBRARIES[key]
+
+
 def _conv_weight(w):
     if not isinstance(w, torch.Tensor) or not _on_gpu(w):
         raise RuntimeError("weight must be a tensor on the GPU; keypointnerf_amd has no CPU path")
@@ -950,15 +988,15 @@ def _conv_weight(w):
     return w.contiguous()
 
 
-def conv2d_supported(cin, cout, k):
+def conv2d_supported(cin, cout, k, arith=0):
     """whether kpn_conv2d_* serves a stride-1 convolution of these channel counts and this square kernel"""
-    return kl.get_library().kpn_conv2d_packed_floats(ctypes.byref(_conv_desc(1, 1, 1, cin, cout, k, 0, 0))) > 0
+    return _conv_library(arith).kpn_conv2d_packed_floats(ctypes.byref(_conv_desc(1, 1, 1, cin, cout, k, 0, 0))) > 0
 
 
-def conv2d_pack(weight):
+def conv2d_pack(weight, arith=0):
     """The two packed copies of an OIHW weight that conv2d_forward (first) and the input gradient of conv2d_backward (second:
-    transposed and flipped) read (kpn_conv2d_pack_device)."""
-    L = kl.get_library()
+    transposed and flipped) read (kpn_conv2d_pack_device), for the calls with the same ``arith``."""
+    L = _conv_library(arith)
     w = _conv_weight(weight.detach())
     d = _conv_desc(1, 1, 1, w.shape[1], w.shape[0], w.shape[2], 0, 0)
     n = _desc_size(L, d, "kpn_conv2d_packed_floats", "kpn_conv2d_pack_device", f"conv2d: unsupported weight {tuple(w.shape)}")
@@ -967,10 +1005,10 @@ def conv2d_pack(weight):
     return packed
 
 
-def conv2d_forward(x, packed, bias, cout, k, padding):
-    """conv2d(x, w, bias, stride=1, padding=padding) for packed = conv2d_pack(w) (kpn_conv2d_forward).  x: (N, cin, H, W)
+def conv2d_forward(x, packed, bias, cout, k, padding, arith=0):
+    """conv2d(x, w, bias, stride=1, padding=padding) for packed = conv2d_pack(w, arith) (kpn_conv2d_forward).  x: (N, cin, H, W)
     channels_last; returns (N, cout, Ho, Wo) channels_last."""
-    L = kl.get_library()
+    L = _conv_library(arith)
     x = _channels_last(x, "x")
     N, cin, H, W = x.shape
     d = _conv_desc(N, H, W, cin, cout, k, padding, bias is not None)
@@ -986,11 +1024,11 @@ def conv2d_forward(x, packed, bias, cout, k, padding):
     return y.permute(0, 3, 1, 2)
 
 
-def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want_dw=True, want_db=True):
+def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want_dw=True, want_db=True, arith=0):
     """(dx, dw, db) of conv2d_forward for the output gradient dy (N, cout, Ho, Wo) channels_last (kpn_conv2d_backward); a
     gradient that is not wanted is None and its leg is not launched.  x (channels_last) is read for dw only and packed for dx
     only: either may be None when its leg is off.  dx is channels_last, dw OIHW."""
-    L = kl.get_library()
+    L = _conv_library(arith)
     dy = _channels_last(dy, "dy")
     N, cout, Ho, Wo = dy.shape
     H, W = Ho - 2 * padding + k - 1, Wo - 2 * padding + k - 1
@@ -1288,9 +1326,9 @@ def _block_desc(N, H, W, cin, cout, eps):
     return d
 
 
-def conv_block_supported(cin, cout):
+def conv_block_supported(cin, cout, arith=0):
     """whether kpn_conv_block_* serves a ConvBlock of these widths"""
-    return kl.get_library().kpn_conv_block_workspace_bytes(ctypes.byref(_block_desc(1, 1, 1, cin, cout, 1e-5))) > 0
+    return _conv_library(arith).kpn_conv_block_workspace_bytes(ctypes.byref(_block_desc(1, 1, 1, cin, cout, 1e-5))) > 0
 
 
 def _block_widths(cin, cout):
@@ -1315,10 +1353,11 @@ def _block_params(L, cin, cout, norms, packed, device, keep):
     return pr
 
 
-def conv_block_forward(x, norms, packed, cout, eps):
+def conv_block_forward(x, norms, packed, cout, eps, arith=0):
     """ConvBlock(cin, cout)(x) (kpn_conv_block_forward).  x: (N, cin, H, W) channels_last.  Returns (y (N, cout, H, W) channels_last,
-    state): state holds the outputs of conv1 and conv2 and the statistics of every norm, which conv_block_backward reads."""
-    L = kl.get_library()
+    state): state holds the outputs of conv1 and conv2 and the statistics of every norm, which conv_block_backward reads.  ``packed``
+    is [conv2d_pack(weight, arith)] with the same ``arith``."""
+    L = _conv_library(arith)
     x = _channels_last(x, "x")
     N, cin, H, W = x.shape
     d = _block_desc(N, H, W, cin, cout, eps)
@@ -1331,11 +1370,11 @@ def conv_block_forward(x, norms, packed, cout, eps):
     return y, state
 
 
-def conv_block_backward(x, dy, norms, packed, state, eps, want_dx=True, want=None):
+def conv_block_backward(x, dy, norms, packed, state, eps, want_dx=True, want=None, arith=0):
     """(dx, [(dgamma, dbeta, dw)] per leg) of conv_block_forward for the output gradient dy (N, cout, H, W) channels_last
     (kpn_conv_block_backward).  ``want`` is [(dgamma, dbeta, dw) wanted] per leg (default: all); what is not wanted is None, and a leg
     that nothing wanted needs is not launched.  dx is channels_last, dw OIHW."""
-    L = kl.get_library()
+    L = _conv_library(arith)
     x, dy = _channels_last(x, "x"), _channels_last(dy, "dy")
     N, cin, H, W = x.shape
     cout = dy.shape[1]

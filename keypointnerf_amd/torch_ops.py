@@ -43,6 +43,9 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.group_norm(x, weight?, bias?, groups, eps, relu) -> y   GroupNorm / InstanceNorm2d [+ ReLU] (C a power of two in
                                  4 .. 1024), channels-last result, DIFFERENTIABLE w.r.t. x, weight and bias (kpn_group_norm_forward /
                                  _backward); y is not kept for the backward and may be overwritten in place
+    torch.ops.kpnerf.conv2d_arith(x, weight, bias?, padding, arith) / conv_block_arith(x, tensors, eps, arith)   conv2d / conv_block
+                                 (below) with the arithmetic of the convolutions' GEMMs as an argument: 0 = fp32 MFMA (the same
+                                 bits), 1 = three bf16 pieces per operand (kpn_conv2d_ex_* / kpn_conv_block_ex_*)
     torch.ops.kpnerf.conv_block(x, tensors, eps) -> y   a whole ConvBlock(cin, cout, norm="group") as ONE autograd node: tensors =
                                  [bn1.weight, bn1.bias, conv1.weight, ... bn3 ..., conv3.weight (, bn4.weight, bn4.bias, downsample
                                  weight)]; channels-last result, DIFFERENTIABLE w.r.t. x and every tensor (kpn_conv_block_forward /
@@ -574,8 +577,12 @@ def _conv_packed(weight, pack, tag):
     return packed
 
 
-def _packed_conv(weight):
-    return _conv_packed(weight, ops.conv2d_pack, "conv")
+def _packed_conv(weight, arith=0):
+    """the packed copies of a stride-1 weight for ``arith``: the arithmetic is part of the cache key, so a weight used under both has two
+    entries' worth of packs, one resident at a time per weight"""
+    if arith == 0:
+        return _conv_packed(weight, ops.conv2d_pack, "conv")
+    return _conv_packed(weight, lambda w: ops.conv2d_pack(w, arith), ("conv", arith))
 
 
 def _packed_s2(weight, kind):
@@ -962,6 +969,130 @@ def _conv_block(x, tensors, eps):
 
 _fragment.define("conv_block(Tensor x, Tensor[] tensors, float eps) -> Tensor")
 _fragment.impl("conv_block", _conv_block, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.conv2d_arith / conv_block_arith: the two operators above with the arithmetic of their GEMMs as an argument ----
+# arith = 0 (CONV_F32) computes what kpnerf::conv2d / kpnerf::conv_block compute, bit for bit; arith = 1 (CONV_BF16X3) runs the
+# convolutions on three bf16 pieces per operand (kpn_conv2d_ex_*, kpn_conv_block_ex_*).  The existing schemas stay as they are; these
+# are operators of their own, with the same autograd structure, the same fake kernels and the same pack cache (arith is in its key).
+@_lib.custom_op("kpnerf::conv2d_arith_cl", mutates_args=(), device_types="cuda")
+def conv2d_arith_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], padding: int, arith: int) -> torch.Tensor:
+    """kpnerf::conv2d_cl in the arithmetic ``arith`` (kpn_conv2d_ex_forward)"""
+    return ops.conv2d_forward(x, _packed_conv(weight, arith), bias, weight.shape[0], weight.shape[2], padding, arith=arith)
+
+
+@conv2d_arith_cl.register_fake
+def _(x, weight, bias, padding, arith):
+    N, _, H, W = x.shape
+    cout, _, k, _ = weight.shape
+    return x.new_empty(N, H + 2 * padding - k + 1, W + 2 * padding - k + 1, cout).permute(0, 3, 1, 2)
+
+
+@_lib.custom_op("kpnerf::conv2d_arith_backward", mutates_args=(), device_types="cuda")
+def conv2d_arith_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, padding: int, arith: int, has_bias: bool,
+                          mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """kpnerf::conv2d_backward in the arithmetic ``arith`` (kpn_conv2d_ex_backward)"""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx, dw, db = ops.conv2d_backward(x, dy, _packed_conv(weight, arith) if mask[0] else None, weight.shape[1], weight.shape[2], padding,
+                                     has_bias, want_dx=mask[0], want_dw=mask[1], want_db=mask[2], arith=arith)
+    return _empty_for_none(dy, dx, dw, db)
+
+
+@conv2d_arith_backward.register_fake
+def _(x, weight, dy, padding, arith, has_bias, mask):
+    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0], torch.preserve_format)
+
+
+def _conv2d_arith_setup(ctx, inputs, output):
+    x, weight, bias, padding, arith = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.padding, ctx.arith, ctx.has_bias = padding, arith, bias is not None
+    ctx.set_materialize_grads(False)
+
+
+def _conv2d_arith_bwd(ctx, dy):
+    nothing = (None,) * 5
+    if dy is None:
+        return nothing
+    x, weight = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]
+    if not any(mask):
+        return nothing
+    dx, dw, db = torch.ops.kpnerf.conv2d_arith_backward(x, weight, dy, ctx.padding, ctx.arith, ctx.has_bias, mask)
+    return _none_unless(mask, dx, dw, db) + nothing[3:]
+
+
+conv2d_arith_cl.register_autograd(_conv2d_arith_bwd, setup_context=_conv2d_arith_setup)
+
+
+def _conv2d_arith(x, weight, bias, padding, arith):
+    return torch.ops.kpnerf.conv2d_arith_cl(x.contiguous(memory_format=torch.channels_last), weight, bias, padding, arith)
+
+
+_fragment.define("conv2d_arith(Tensor x, Tensor weight, Tensor? bias, int padding, int arith) -> Tensor")
+_fragment.impl("conv2d_arith", _conv2d_arith, "CompositeImplicitAutograd")
+
+
+@_lib.custom_op("kpnerf::conv_block_arith_cl", mutates_args=(), device_types="cuda")
+def conv_block_arith_cl(x: torch.Tensor, tensors: List[torch.Tensor], eps: float, arith: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kpnerf::conv_block_cl with every convolution in the arithmetic ``arith`` (kpn_conv_block_ex_forward)"""
+    legs = _block_legs(tensors)
+    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], 2 * legs[0][2].shape[0], eps,
+                                  arith=arith)
+
+
+@conv_block_arith_cl.register_fake
+def _(x, tensors, eps, arith):
+    return torch.ops.kpnerf.conv_block_cl(x, tensors, eps)          # the shapes do not depend on the arithmetic
+
+
+@_lib.custom_op("kpnerf::conv_block_arith_backward", mutates_args=(), device_types="cuda")
+def conv_block_arith_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: torch.Tensor, dy: torch.Tensor, eps: float, arith: int,
+                              mask: List[bool]) -> List[torch.Tensor]:
+    """kpnerf::conv_block_backward with every convolution in the arithmetic ``arith`` (kpn_conv_block_ex_backward)"""
+    legs = _block_legs(tensors)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
+    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], state, eps,
+                                        want_dx=mask[0], want=want, arith=arith)
+    return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
+
+
+@conv_block_arith_backward.register_fake
+def _(x, tensors, state, dy, eps, arith, mask):
+    return [torch.empty_like(x) if mask[0] else x.new_empty(0)] + [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask[1:])]
+
+
+def _conv_block_arith_setup(ctx, inputs, output):
+    x, tensors, eps, arith = inputs
+    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
+    ctx.eps, ctx.arith = eps, arith
+    ctx.set_materialize_grads(False)
+
+
+def _conv_block_arith_bwd(ctx, dy, _d_state):
+    x, state, *tensors = ctx.saved_tensors
+    none = (None, [None] * len(tensors), None, None)
+    if dy is None:
+        return none
+    mask = [bool(ctx.needs_input_grad[0])] + [bool(b) for b in ctx.needs_input_grad[1]]
+    if not any(mask):
+        return none
+    out = torch.ops.kpnerf.conv_block_arith_backward(x, list(tensors), state, dy, ctx.eps, ctx.arith, mask)
+    out = _none_unless(mask, *out)
+    return out[0], list(out[1:]), None, None
+
+
+conv_block_arith_cl.register_autograd(_conv_block_arith_bwd, setup_context=_conv_block_arith_setup)
+
+
+def _conv_block_arith(x, tensors, eps, arith):
+    return torch.ops.kpnerf.conv_block_arith_cl(x.contiguous(memory_format=torch.channels_last), tensors, eps, arith)[0]
+
+
+_fragment.define("conv_block_arith(Tensor x, Tensor[] tensors, float eps, int arith) -> Tensor")
+_fragment.impl("conv_block_arith", _conv_block_arith, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.res_encoder: a whole ResBlkEncoder, DIFFERENTIABLE w.r.t. every parameter, one autograd node ----

@@ -2,7 +2,7 @@
 module, the per-layer native path (encoders.install_native_blocks / install_native_geo) and the single-operator blocks
 (``fused=True`` / ``fused_blocks=True``, torch.ops.kpnerf.conv_block) - and records the peak memory of one training step of the network.
 
-    python scripts/bench_block_fused.py [--views 3] [--size 512] [--reps 20] [--inner 5] [--root CHECKOUT] [--out FILE.md]
+    python scripts/bench_block_fused.py [--views 3] [--size 512] [--reps 20] [--inner 5] [--arith bf16x3] [--root CHECKOUT] [--out FILE.md]
 
 blocks: ConvBlock(256, 256) and ConvBlock(128, 256) on N = views channels_last tensors of 64 x 64 and 16 x 16 (the sizes of
         profiles/norm_backward.md).
@@ -13,7 +13,8 @@ memory: torch.cuda.max_memory_allocated over one forward + backward of the netwo
 The arms alternate within every repetition: a repetition times `inner` back-to-back steps of one arm between two device events, then
 the next arm; the figures are the median and the range over the repetitions.  ``--root`` imports keypointnerf_amd and tests from another
 checkout of the project (one built there), e.g. the parent commit for a baseline in the same call; a checkout without the
-single-operator block is measured without that arm.  Needs a GPU.
+single-operator block is measured without that arm.  ``--arith bf16x3`` adds one more arm to both tables: the single-operator blocks with
+their convolutions on three bf16 pieces per operand (``arith="bf16x3"``).  Needs a GPU.
 """
 import argparse
 import copy
@@ -81,6 +82,10 @@ def bench_blocks(args, encoders, has_fused):
             if has_fused:
                 assert encoders.install_native_blocks(fused, fused=True)[0] == [""]
                 arms.append(("install_native_blocks(fused=True)", step_of(fused, x, [g])))
+            if args.arith:
+                split = copy.deepcopy(plain)
+                assert encoders.install_native_blocks(split, fused=True, arith=args.arith)[0] == [""]
+                arms.append((f'install_native_blocks(fused=True, arith="{args.arith}")', step_of(split, x, [g])))
             rows.append(dict(block=f"ConvBlock({cin}, {cout})", size=f"{hw}x{hw}", us={n: {k: v * 1000.0 for k, v in r.items()}
                                                                                      for n, r in alternate(arms, args.reps, args.inner).items()}))
             print(json.dumps(rows[-1]), flush=True)
@@ -98,6 +103,10 @@ def bench_net(args, encoders, has_fused):
         nets.append(("install_native_geo(fused_blocks=True)", copy.deepcopy(plain)))
         report = encoders.install_native_geo(nets[2][1], fused_blocks=True)
         assert not any(left for _, left in report.values()), report
+    if args.arith:
+        nets.append((f'install_native_geo(fused_blocks=True, arith="{args.arith}")', copy.deepcopy(plain)))
+        report = encoders.install_native_geo(nets[-1][1], fused_blocks=True, arith=args.arith)
+        assert not any(report[k][1] for k in report if k != "arith"), report
     x = eg.net_input(eg.case_image((args.views, 3, args.size, args.size), 1).cuda(), 1).contiguous(memory_format=cl)
     gen = torch.Generator(device="cuda").manual_seed(0)
     gs = [torch.randn(args.views, 64, hw // 4, hw // 4, device="cuda", generator=gen).contiguous(memory_format=cl),
@@ -123,6 +132,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--arith", choices=("bf16x3",), default=None)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)

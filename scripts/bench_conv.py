@@ -1,7 +1,7 @@
 """Times the native convolution (kpn_conv2d_forward / kpn_conv2d_backward) against torch.nn.functional.conv2d and
 aten.convolution_backward (MIOpen), both on channels_last tensors, at the shapes the geometry encoder runs.
 
-    python scripts/bench_conv.py [--views 3] [--size 512] [--ds 1] [--all] [--reps 10] [--inner 5] [--out FILE.md]
+    python scripts/bench_conv.py [--views 3] [--size 512] [--ds 1] [--all] [--arith bf16x3] [--reps 10] [--inner 5] [--out FILE.md]
 
 The shape list restates the host walk of csrc/api_encoders.hip (enc::geo_walk / conv_block / hourglass): every stride-1
 convolution with a 1x1, 3x3 or 5x5 kernel, with the number of layers that share the shape.  By default the hourglass, top_m_0, the
@@ -9,6 +9,11 @@ two heads and conv_out are timed (the bulk of the arithmetic); --all adds the Co
 
 Per shape and leg (forward, dX, dW + db) the two arms alternate: each repetition times `inner` back-to-back calls of one arm between
 two device events, then the other arm; the figure is the median over the repetitions, in microseconds per call.  Needs a GPU.
+
+--arith bf16x3 adds a third arm between the two: the same calls with arith = CONV_BF16X3 (kpn_conv2d_ex_*, three bf16 pieces per operand
+on the 16-bit MFMA); the three arms alternate within every repetition.  The table then carries, per leg, native fp32 / native bf16x3 /
+torch, and per native arm the achieved TF-equivalent of the three GEMMs together (fp32 FLOP of the layer, 2 N H W cin cout k^2 per GEMM,
+over the time of the leg; dW + db counts the GEMM alone), to be read against 155 TF (fp32 MFMA) and 417 TF-equivalent (six bf16 MFMAs).
 """
 import argparse
 import collections
@@ -76,6 +81,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--ds", type=int, default=1)
     ap.add_argument("--all", action="store_true")
+    ap.add_argument("--arith", choices=("bf16x3",), default=None)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -89,8 +95,14 @@ def main():
     N, hw = args.views, args.size >> args.ds
     gen = torch.Generator(device="cuda").manual_seed(0)
     rows, lines = [], []
-    lines.append(f"| shape (N = {N}) | layers | ranges | fwd native / torch (us) | dX native / torch | dW+db native / torch | sum native / torch | ratio |")
-    lines.append("|---|---|---|---|---|---|---|---|")
+    A3 = kl.CONV_BF16X3
+    if args.arith:
+        lines.append(f"| shape (N = {N}) | layers | ranges f32, bf16x3 | fwd f32 / bf16x3 / torch (us) | dX f32 / bf16x3 / torch | dW+db f32 / bf16x3 / torch | "
+                     "sum f32 / bf16x3 / torch | bf16x3 / f32 | bf16x3 / torch | TF-eq fwd, dX, dW: f32 | TF-eq fwd, dX, dW: bf16x3 |")
+        lines.append("|---|---|---|---|---|---|---|---|---|---|---|")
+    else:
+        lines.append(f"| shape (N = {N}) | layers | ranges | fwd native / torch (us) | dX native / torch | dW+db native / torch | sum native / torch | ratio |")
+        lines.append("|---|---|---|---|---|---|---|---|")
     for (H, W, cin, cout, k, pad, bias), count in geo_conv_shapes(hw, hw, everything=args.all).items():
         cl = torch.channels_last
         x = torch.randn(N, cin, H, W, device="cuda", generator=gen).contiguous(memory_format=cl)
@@ -112,26 +124,59 @@ def main():
         dev["fwd"] = float((y_n - y_t).abs().max() / y_t.abs().max())
         dev["dx"] = float((arms["dx"][0]()[0] - arms["dx"][1]()[0]).abs().max() / arms["dx"][1]()[0].abs().max())
         dev["dw"] = float((arms["dw"][0]()[1] - arms["dw"][1]()[1]).abs().max() / arms["dw"][1]()[1].abs().max())
-        med = {}
+        med, med3 = {}, {}
+        if args.arith:
+            packed3 = ops.conv2d_pack(w, arith=A3)
+            ranges3 = L.kpn_conv2d_ex_wgrad_ranges(ctypes.byref(ops._conv_desc(N, H, W, cin, cout, k, pad, bias)), A3)
+            arms3 = {
+                "fwd": lambda: ops.conv2d_forward(x, packed3, b, cout, k, pad, arith=A3),
+                "dx": lambda: ops.conv2d_backward(None, dy, packed3, cin, k, pad, bias, True, False, False, arith=A3),
+                "dw": lambda: ops.conv2d_backward(x, dy, None, cin, k, pad, bias, False, True, True, arith=A3),
+            }
+            dev3 = {"fwd": float((arms3["fwd"]() - y_t).abs().max() / y_t.abs().max()),
+                    "dx": float((arms3["dx"]()[0] - arms["dx"][1]()[0]).abs().max() / arms["dx"][1]()[0].abs().max()),
+                    "dw": float((arms3["dw"]()[1] - arms["dw"][1]()[1]).abs().max() / arms["dw"][1]()[1].abs().max())}
         for leg, (native, torch_arm) in arms.items():
+            trio = [native] + ([arms3[leg]] if args.arith else []) + [torch_arm]
             for _ in range(3):
-                native(), torch_arm()
+                for fn in trio:
+                    fn()
             torch.cuda.synchronize()
-            tn, tt = [], []
-            for _ in range(args.reps):
-                tn.append(timed(native, args.inner))
-                tt.append(timed(torch_arm, args.inner))
-            med[leg] = (statistics.median(tn), statistics.median(tt))
+            ts = [[] for _ in trio]
+            for _ in range(args.reps):                      # the arms alternate within every repetition
+                for t, fn in zip(ts, trio):
+                    t.append(timed(fn, args.inner))
+            med[leg] = (statistics.median(ts[0]), statistics.median(ts[-1]))
+            if args.arith:
+                med3[leg] = statistics.median(ts[1])
         sn, st = sum(v[0] for v in med.values()), sum(v[1] for v in med.values())
         name = f"{k}x{k} {cin}->{cout} @ {H}x{W}" + (" +b" if bias else "")
         rows.append(dict(shape=name, N=N, H=H, W=W, cin=cin, cout=cout, k=k, pad=pad, bias=bias, layers=count, wgrad_ranges=ranges,
                          us={leg: {"native": v[0], "torch": v[1]} for leg, v in med.items()}, max_rel_dev=dev))
-        lines.append(f"| {name} | {count} | {ranges} | " + " | ".join(f"{med[leg][0]:.1f} / {med[leg][1]:.1f}" for leg in ("fwd", "dx", "dw")) +
-                     f" | {sn:.1f} / {st:.1f} | {sn / st:.2f} |")
+        if args.arith:
+            s3 = sum(med3.values())
+            flop = 2.0 * N * H * W * cin * cout * k * k
+            tf = lambda us: flop / (us * 1e-6) / 1e12  # noqa: E731
+            rows[-1].update(wgrad_ranges_bf16x3=ranges3, max_rel_dev_bf16x3=dev3)
+            for leg in med:
+                rows[-1]["us"][leg]["bf16x3"] = med3[leg]
+            rows[-1]["tf_equivalent"] = {leg: {"f32": tf(med[leg][0]), "bf16x3": tf(med3[leg])} for leg in med}
+            lines.append(f"| {name} | {count} | {ranges}, {ranges3} | " +
+                         " | ".join(f"{med[leg][0]:.1f} / {med3[leg]:.1f} / {med[leg][1]:.1f}" for leg in ("fwd", "dx", "dw")) +
+                         f" | {sn:.1f} / {s3:.1f} / {st:.1f} | {s3 / sn:.2f} | {s3 / st:.2f} | " +
+                         ", ".join(f"{tf(med[leg][0]):.0f}" for leg in ("fwd", "dx", "dw")) + " | " +
+                         ", ".join(f"{tf(med3[leg]):.0f}" for leg in ("fwd", "dx", "dw")) + " |")
+        else:
+            lines.append(f"| {name} | {count} | {ranges} | " + " | ".join(f"{med[leg][0]:.1f} / {med[leg][1]:.1f}" for leg in ("fwd", "dx", "dw")) +
+                         f" | {sn:.1f} / {st:.1f} | {sn / st:.2f} |")
         print(lines[-1], flush=True)
     tot_n = sum(r["layers"] * sum(v["native"] for v in r["us"].values()) for r in rows)
     tot_t = sum(r["layers"] * sum(v["torch"] for v in r["us"].values()) for r in rows)
     lines.append(f"\nAll listed layers, forward + dX + dW + db, weighted by the number of layers: native {tot_n / 1000:.2f} ms, torch {tot_t / 1000:.2f} ms.")
+    if args.arith:
+        tot_3 = sum(r["layers"] * sum(v["bf16x3"] for v in r["us"].values()) for r in rows)
+        lines.append(f"The same with arith = bf16x3: {tot_3 / 1000:.2f} ms.  Largest deviation of that arm from torch, relative to the largest value: " +
+                     ", ".join(f"{leg} {max(r['max_rel_dev_bf16x3'][leg] for r in rows):.1e}" for leg in ("fwd", "dx", "dw")) + ".")
     lines.append(f"Largest deviation between the arms, relative to the largest value: " +
                  ", ".join(f"{leg} {max(r['max_rel_dev'][leg] for r in rows):.1e}" for leg in ("fwd", "dx", "dw")) + ".")
     text = "\n".join(lines)

@@ -2,7 +2,7 @@
 3 x 3 x 512^2 source set (network input 256^2 for the geometry encoder, ds = 1).
 
     python scripts/bench_geo_training.py layers [--reps 10] [--inner 5] [--out FILE.md]
-    python scripts/bench_geo_training.py net    [--reps 10] [--out FILE.md]
+    python scripts/bench_geo_training.py net    [--reps 10] [--fused-blocks] [--arith bf16x3] [--out FILE.md]
 
 layers: the three new layer kinds at the shapes of the geometry encoder (conv1, unpack1.conv) and of the texture encoder (its three
         stride-2 convolutions and two transposed ones), torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2 under autograd against
@@ -10,7 +10,8 @@ layers: the three new layer kinds at the shapes of the geometry encoder (conv1, 
         yields every gradient the layer has (the stem: dW and db only, on both arms).
 net:    tests/encoder_golden.HGFilterV2 with encoders.install_native_geo against the untouched module on channels_last tensors
         (and, for the record, against the module with channels_last weights and against NCHW tensors), forward + backward to
-        every parameter gradient.
+        every parameter gradient.  --fused-blocks installs the ConvBlocks as single operators; --arith bf16x3 adds an arm with the
+        stride-1 convolutions and the blocks on three bf16 pieces per operand (install_native_geo(arith="bf16x3")).
 
 The two arms alternate: each repetition times `inner` back-to-back calls of one arm between two device events, then the other arm;
 the figure is the median over the repetitions.  Run each mode under a time limit of its own.  Needs a GPU.
@@ -98,8 +99,9 @@ def bench_net(args):
     native = eg.stand_in_geo(1).train().cuda()
     plain = copy.deepcopy(native)                               # the untouched module
     plain_cl = copy.deepcopy(native).to(memory_format=cl)       # ... and with its weights channels_last as well
-    report = encoders.install_native_geo(native)
+    report = encoders.install_native_geo(native, fused_blocks=args.fused_blocks)
     left = {k: v[1] for k, v in report.items() if v[1]}
+    how = "install_native_geo" + ("(fused_blocks=True)" if args.fused_blocks else "")
     x_nchw = eg.net_input(eg.case_image((args.views, 3, args.size, args.size), 1).cuda(), 1).contiguous()
     x = x_nchw.contiguous(memory_format=cl)
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -114,7 +116,12 @@ def bench_net(args):
         with torch.no_grad():
             return net(x)
 
-    arms = (("native (install_native_geo), channels_last tensors", native, x, gs),
+    split = ()
+    if args.arith:
+        net3 = copy.deepcopy(plain)
+        encoders.install_native_geo(net3, fused_blocks=args.fused_blocks, arith=args.arith)
+        split = ((f"native ({how}, arith={args.arith}), channels_last tensors", net3, x, gs),)
+    arms = ((f"native ({how}), channels_last tensors", native, x, gs),) + split + (
             ("torch, untouched module, channels_last tensors", plain, x, gs),
             ("torch, weights channels_last too", plain_cl, x, gs),
             ("torch, untouched module, NCHW tensors", plain, x_nchw, gs_nchw))
@@ -142,6 +149,8 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--fused-blocks", action="store_true")
+    ap.add_argument("--arith", choices=("bf16x3",), default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
