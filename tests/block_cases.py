@@ -4,7 +4,7 @@ the C ABI that runs on host arrays (the emulator build) and on device tensors (t
 Reference: tests.encoder_golden.ConvBlock with seeded weights, seeded normal x and seed gradient g, on the CPU in fp64: y, dX, every
 parameter gradient, and the outputs of conv1 and conv2 (what `state` keeps).  A ConvBlock is a chain of seven ops, so e_ref per tensor
 is the larger deviation of two CPU fp32 runs from fp64, one contiguous and one channels_last (tests/test_gpu_norm.py).  The bar, for
-every element: |native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) (tests/conv_cases.py).  Every case first asserts, on the
+every element: |native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) (tests/parity.py).  Every case first asserts, on the
 reference alone, that every norm's smallest |pre-activation| exceeds 8 e_ref of that pre-activation: no rounding can flip a ReLU mask.
 """
 import copy
@@ -16,7 +16,8 @@ import torch
 
 from keypointnerf_amd import lib as kl
 from tests import conv_cases as cc
-from tests.conv_cases import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
+from tests import parity
+from tests.parity import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
 
 EPS = 1e-5
 # what each case can catch:
@@ -115,12 +116,7 @@ def reference(name):
     return net, x, g, r64, e_ref
 
 
-def check(label, native, f64, e_ref):
-    assert np.isfinite(np.asarray(native)).all(), label
-    r = ratio(native, f64, e_ref)
-    print(f"[block parity] {label}: ratio {r:.3f} (e_ref {e_ref:.3e}, bar {FACTOR:g})")
-    assert r <= FACTOR, (label, r, e_ref)
-    return r
+check = functools.partial(parity.check, tag="block")
 
 
 # ---- the C ABI ----

@@ -15,7 +15,7 @@ import torch
 from keypointnerf_amd import lib as kl
 from tests import block_cases as bc
 from tests import conv_cases as cc
-from tests.conv_cases import CANARY, DeviceArrays, HostArrays, check, nchw, nhwc  # noqa: F401
+from tests.parity import CANARY, DeviceArrays, HostArrays, bits, check, nchw, nhwc  # noqa: F401
 
 F32, B3 = kl.CONV_F32, kl.CONV_BF16X3
 _FAMILIES = ("kpn_conv2d_", "kpn_conv_block_")
@@ -61,14 +61,8 @@ def dx_ksplit(c):
     return expected_ksplit(c["H"], c["W"], c["k"] ** 2 * c["cout"], c["cin"])
 
 
-def expected_ranges(c):
-    """the range rule of kpn_conv2d_wgrad_ranges over the bf16 x 3 tile -> (ranges, chunks, chunks per range)"""
-    Ho, Wo = cc.out_hw(c)
-    chunks = -(-c["N"] * Ho * Wo // 16)
-    bm, bn = tile(c["cout"])
-    tiles = -(-c["k"] * c["k"] * c["cin"] // bm) * -(-c["cout"] // bn)
-    cpr = max(20, -(-chunks // max(1, min(64, 1024 // tiles))))
-    return -(-chunks // cpr), chunks, cpr
+# the range rule of kpn_conv2d_wgrad_ranges over the bf16 x 3 tile -> (ranges, chunks, chunks per range)
+expected_ranges = functools.partial(cc.expected_ranges, tile=tile)
 
 
 # ---- the cases the new kernels' own rules need; each is stated from its rule and asserted against it in check_own_rules ----
@@ -108,13 +102,7 @@ def reference(name, seed=0):
     """conv_cases.reference for its cases and, computed in the same way, for the own ones"""
     if name in cc.CASES:
         return cc.reference(name, seed)
-    c = OWN_CASES[name]
-    x, w, b, g = cc.inputs(c, seed)
-    r64, r32 = cc._torch_run(c, x, w, b, g, torch.float64), cc._torch_run(c, x, w, b, g, torch.float32)
-    e_ref = {k: float(np.abs(r32[k].astype(np.float64) - r64[k]).max()) for k in r64}
-    for v in r64.values():
-        v.setflags(write=False)
-    return (x, w, b, g), r64, e_ref
+    return cc.reference_of(OWN_CASES[name], seed)
 
 
 def run(L, B, name, scale_x=1.0, scale_g=1.0):
@@ -144,10 +132,6 @@ def check_case(L, B, name):
             continue
         ratios[k] = check(f"{name} arith {L.arith} {k}", out[k], r64[k], e_ref[k])
     return ratios
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def check_f32_through_ex_has_the_bits_of_the_plain_entry_points(L, B, name):

@@ -4,7 +4,7 @@ and one driver of the C ABI that runs on host arrays (the emulator build) and on
 Reference: seeded normal x (+ offset), gamma, beta and seed gradient g give y, dX, dgamma, dbeta from
 torch.nn.functional.group_norm (+ relu) and torch.autograd.grad on the CPU in fp64.  e_ref is the max deviation of the same
 computation in CPU fp32 from that, per tensor.  The bar, for every element: |native - fp64| <= 4 e_ref + spacing(float32(max|fp64|))
-- the project's standing rule and factor (tests/conv_cases.py).  ReLU cases first assert, on the reference alone, that the smallest
+- the project's standing rule and factor (tests/parity.py).  ReLU cases first assert, on the reference alone, that the smallest
 |pre-activation| exceeds 8 e_ref(y): no rounding can flip a mask.
 """
 import ctypes
@@ -15,7 +15,8 @@ import torch
 import torch.nn.functional as F
 
 from keypointnerf_amd import lib as kl
-from tests.conv_cases import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
+from tests import parity
+from tests.parity import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
 
 EPS = 1e-5
 # what each case can catch:
@@ -90,12 +91,7 @@ def reference(name, relu):
     return (x, gamma, beta, g), r64, e_ref
 
 
-def check(label, native, f64, e_ref):
-    assert np.isfinite(np.asarray(native)).all(), label
-    r = ratio(native, f64, e_ref)
-    print(f"[norm parity] {label}: ratio {r:.3f} (e_ref {e_ref:.3e}, bar {FACTOR:g})")
-    assert r <= FACTOR, (label, r, e_ref)
-    return r
+check = functools.partial(parity.check, tag="norm")
 
 
 def workspace(L, B, c, relu=0):

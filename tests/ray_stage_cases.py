@@ -17,7 +17,7 @@ import torch
 
 from keypointnerf_amd import lib as kl
 from oracle import oracle
-from tests.conv_cases import CANARY, DeviceArrays, HostArrays, ratio  # noqa: F401  (the runners take the array classes from here)
+from tests.parity import CANARY, DeviceArrays, HostArrays, bits, ratio  # noqa: F401  (the runners take the array classes from here)
 from tests.test_oracle_vs_golden import assert_samples_close
 
 # e_ref is torch's fp32 on the host of the run and so moves with its torch, SIMD path and libm (measured: 9.1e-8 on one host, 2.3e-8 on
@@ -31,10 +31,6 @@ def put_raw(B, a):
     """an array of any dtype (pixels are int32) on the build's side of the ABI"""
     a = np.ascontiguousarray(a)
     return a.copy() if isinstance(B, HostArrays) else torch.from_numpy(a.copy()).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 # ------------------------------------------------------------------------------------------------

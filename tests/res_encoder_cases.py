@@ -4,7 +4,7 @@ of the C ABI that runs on host arrays (the emulator build) and on device tensors
 Reference: tests.encoder_golden.ResBlkEncoder made with eg.seeded(..., seed).train(), a seeded normal x (seed 72) and seed gradient g
 (seed 73), on the CPU in fp64: y, every parameter gradient, every convolution output c_i and every a_k (what `state` keeps).  e_ref per
 tensor is the larger deviation of two CPU fp32 runs from fp64, one contiguous and one channels_last.  The bar, for every element:
-|native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) (tests/conv_cases.py).  Every case first asserts, on the reference alone, that
+|native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) (tests/parity.py).  Every case first asserts, on the reference alone, that
 the smallest |InstanceNorm output| in front of a ReLU exceeds 8x the largest fp32 deviation of those outputs: no rounding can flip a
 ReLU mask (the check of tests/test_gpu_reppad.narrow_margin, over every norm of the case).
 """
@@ -18,11 +18,13 @@ import torch.nn as nn
 
 from keypointnerf_amd import lib as kl
 from tests import encoder_golden as eg
+from tests import layer_op_checks as loc
 from tests import norm_cases as nc
 from tests import reppad_cases as rc
 from tests import strided_cases as sc
+from tests import parity
 from tests import test_gpu_reppad as tr
-from tests.conv_cases import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
+from tests.parity import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
 
 EPS = 1e-5
 SEED_X, SEED_G = 72, 73
@@ -119,8 +121,8 @@ def encoder_run(net, c, x, g, memory_format=torch.contiguous_format):
 def margin(net, x):
     """(smallest |InstanceNorm output| in front of a ReLU of the fp64 module, largest fp32 deviation of those outputs over both memory
     formats): tests/test_gpu_reppad.narrow_margin over every norm of this encoder"""
-    pre64 = tr._norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format)
-    pre32 = [tr._norm_outputs(copy.deepcopy(net), x, mf) for mf in (torch.contiguous_format, torch.channels_last)]
+    pre64 = loc.norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format, tr.relu_norms)
+    pre32 = [loc.norm_outputs(copy.deepcopy(net), x, mf, tr.relu_norms) for mf in (torch.contiguous_format, torch.channels_last)]
     return (min(float(p.abs().min()) for p in pre64.values()), max(float((r[n].double() - p).abs().max()) for r in pre32 for n, p in pre64.items()),
             len(pre64))
 
@@ -148,12 +150,7 @@ def reference(name):
     return net, x, g, r64, e_ref
 
 
-def check(label, native, f64, e_ref):
-    assert np.isfinite(np.asarray(native)).all(), label
-    r = ratio(native, f64, e_ref)
-    print(f"[res encoder parity] {label}: ratio {r:.3f} (e_ref {e_ref:.3e}, bar {FACTOR:g})")
-    assert r <= FACTOR, (label, r, e_ref)
-    return r
+check = functools.partial(parity.check, tag="res encoder")
 
 
 # ---- the C ABI ----

@@ -5,7 +5,7 @@ library) alike.
 Reference: seeded normal x, low, skip and seed gradients give y and the gradients of torch.nn.functional.avg_pool2d(x, 2, stride=2)
 and skip + torch.nn.functional.interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) through torch.autograd.grad on the
 CPU in fp64.  e_ref is the max deviation of the same computation in CPU fp32 from that, per tensor.  The bar, for every element:
-|native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) - the project's standing rule and factor (tests/conv_cases.py).
+|native - fp64| <= 4 e_ref + spacing(float32(max|fp64|)) - the project's standing rule and factor (tests/parity.py).
 """
 import ctypes
 import functools
@@ -15,7 +15,8 @@ import torch
 import torch.nn.functional as F
 
 from keypointnerf_amd import lib as kl
-from tests.conv_cases import CANARY, FACTOR, DeviceArrays, HostArrays, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
+from tests import parity
+from tests.parity import CANARY, FACTOR, DeviceArrays, HostArrays, bits, nchw, nhwc, ratio  # noqa: F401  (one bar, one pair of array kinds)
 
 # low sizes; what each case can catch:
 CASES = {
@@ -75,12 +76,7 @@ def reference(name):
     return t, r64, e_ref
 
 
-def check(label, native, f64, e_ref):
-    assert np.isfinite(np.asarray(native)).all(), label
-    r = ratio(native, f64, e_ref)
-    print(f"[resample parity] {label}: ratio {r:.3f} (e_ref {e_ref:.3e}, bar {FACTOR:g})")
-    assert r <= FACTOR, (label, r, e_ref)
-    return r
+check = functools.partial(parity.check, tag="resample")
 
 
 def _low(c):
@@ -127,10 +123,6 @@ def run(L, B, name, c=None, t=None):
     t = reference(name)[0] if t is None else t
     return {"pool_y": pool_forward(L, B, c, nhwc(t["x"])), "pool_dx": pool_backward(L, B, c, nhwc(t["g_low"])),
             "up_y": up_forward(L, B, c, nhwc(t["low"]), nhwc(t["skip"])), "up_dlow": up_backward(L, B, c, nhwc(t["g_high"]))}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 # ---- the properties both builds are held to (tests/test_resample_cpu.py on the emulator, tests/test_gpu_resample.py on the device) ----

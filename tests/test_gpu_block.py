@@ -7,9 +7,9 @@ import copy
 import numpy as np
 import pytest
 import torch
-from torch.utils._python_dispatch import TorchDispatchMode
 
 from tests import block_cases as bc
+from tests.parity import Spy
 
 pytestmark = pytest.mark.gpu
 
@@ -133,16 +133,6 @@ def test_fused_forward_has_the_bits_of_the_unfused_native_path(name):
     assert torch.equal(plain, fused)
 
 
-class _Spy(TorchDispatchMode):
-    def __init__(self):
-        super().__init__()
-        self.names = []
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        self.names.append(func.name())
-        return func(*args, **(kwargs or {}))
-
-
 INSIDE_A_BLOCK = ("aten::cat", "aten::add", "aten::convolution", "aten::native_group_norm", "aten::relu", "aten::threshold_backward",
                   "aten::_convolution", "aten::miopen_convolution", "aten::cudnn_convolution")
 
@@ -153,7 +143,7 @@ def test_a_fused_block_is_one_operator_forward_and_one_backward(name):
     dev, x, g = _case_on_device(name)
     assert encoders.install_native_blocks(dev, fused=True) == ([""], {})
     calls = encoders.NativeTraining.fused_block_calls, encoders.NativeTraining.block_calls
-    with _Spy() as spy:
+    with Spy() as spy:
         y = dev(x)
         torch.autograd.grad(y, [x] + _tensors(dev), g)
     assert (encoders.NativeTraining.fused_block_calls, encoders.NativeTraining.block_calls) == (calls[0] + 1, calls[1])
@@ -245,10 +235,11 @@ def test_a_narrow_hgfilter_trains_with_fused_blocks():
     condition on the reference alone.  No torch.cat is left (every one the network has sits in a ConvBlock), and every block is one
     kpnerf::conv_block_cl with one kpnerf::conv_block_backward."""
     from keypointnerf_amd import encoders
+    from tests import layer_op_checks as loc
     from tests import strided_cases as sc
     from tests import test_gpu_strided as tgs
     net, x, gs = tgs.narrow_case()
-    margin, e_pre = tgs.narrow_margin(net, x)
+    margin, e_pre = loc.narrow_margin(net, x, loc.group_norms, tgs.NARROW_NORMS)
     assert margin > 8.0 * e_pre, (margin, e_pre)
     r64 = tgs._param_grads(copy.deepcopy(net).double(), x.double(), [g.double() for g in gs])
     runs32 = [tgs._param_grads(copy.deepcopy(net), x.contiguous(memory_format=mf), gs) for mf in (torch.contiguous_format, torch.channels_last)]
@@ -260,7 +251,7 @@ def test_a_narrow_hgfilter_trains_with_fused_blocks():
     assert len(report["blocks"][0]) == n_blocks == 8 and list(dev.state_dict().keys()) == keys
     N_ = encoders.NativeTraining
     calls = N_.geo_calls, N_.fused_block_calls, N_.block_calls
-    with tgs._Spy() as spy:
+    with Spy() as spy:
         got = tgs._param_grads(dev, x.cuda(), [g.cuda() for g in gs])
     assert (N_.geo_calls, N_.fused_block_calls, N_.block_calls) == (calls[0] + 1, calls[1] + n_blocks, calls[2])
     bad = sorted({n for n in spy.names if n.startswith(tgs.FORBIDDEN + ("aten::cat",))})

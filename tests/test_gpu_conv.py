@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import conv_cases as cc
+from tests import layer_op_checks as loc
 
 pytestmark = pytest.mark.gpu
 
@@ -53,24 +54,14 @@ def test_abi_wgrad_range_counts_follow_the_stated_rule(L):
 
 
 # ---- torch.ops.kpnerf.conv2d ----
-def _op_run(name, channels_last=True, need=(True, True, True)):
-    import keypointnerf_amd.torch_ops  # noqa: F401
-    c = cc.CASES[name]
-    (x, w, b, g), _, _ = cc.reference(name)
-    xd = x.cuda().contiguous(memory_format=torch.channels_last) if channels_last else x.cuda().contiguous()
-    xd.requires_grad_(need[0])
-    wd = w.cuda().requires_grad_(need[1])
-    bd = None if b is None else b.cuda().requires_grad_(need[2])
-    y = torch.ops.kpnerf.conv2d(xd, wd, bd, c["pad"])
-    if y.requires_grad:
-        (y * g.cuda()).sum().backward()
-    return y.detach(), xd, wd, bd
+def _op(c):
+    return c, lambda x, w, b: torch.ops.kpnerf.conv2d(x, w, b, c["pad"])
 
 
 @pytest.mark.parametrize("name", sorted(cc.CASES))
 def test_op_autograd_against_fp64(name):
     _, r64, e_ref = cc.reference(name)
-    y, xd, wd, bd = _op_run(name)
+    y, xd, wd, bd = loc.op_run(cc.FAMILY, _op, name)
     assert y.is_contiguous(memory_format=torch.channels_last) and xd.grad.is_contiguous(memory_format=torch.channels_last)
     cc.check(f"op {name} y", y.cpu().numpy(), r64["y"], e_ref["y"])
     cc.check(f"op {name} dx", xd.grad.cpu().numpy(), r64["dx"], e_ref["dx"])
@@ -80,28 +71,7 @@ def test_op_autograd_against_fp64(name):
 
 
 def test_op_launches_only_the_legs_that_need_a_gradient(monkeypatch):
-    from keypointnerf_amd import ops
-    seen = []
-    real = ops.conv2d_backward
-
-    def spy(*a, **kw):
-        seen.append((kw["want_dx"], kw["want_dw"], kw["want_db"]))
-        return real(*a, **kw)
-
-    monkeypatch.setattr(ops, "conv2d_backward", spy)
-    name = "k3_4to8"
-    _, r64, e_ref = cc.reference(name)
-    _, xd, wd, bd = _op_run(name, need=(True, False, False))            # a frozen layer: dX alone
-    assert seen == [(True, False, False)] and wd.grad is None and bd.grad is None
-    cc.check("x only dx", xd.grad.cpu().numpy(), r64["dx"], e_ref["dx"])
-    _, xd, wd, bd = _op_run(name, need=(False, True, False))            # a first layer with a frozen bias: dW alone
-    assert seen[1:] == [(False, True, False)] and xd.grad is None and bd.grad is None
-    cc.check("weight only dw", wd.grad.cpu().numpy(), r64["dw"], e_ref["dw"])
-    _, xd, wd, bd = _op_run(name, need=(False, True, True))
-    assert seen[2:] == [(False, True, True)] and xd.grad is None
-    cc.check("weight and bias db", bd.grad.cpu().numpy(), r64["db"], e_ref["db"])
-    y, xd, wd, bd = _op_run(name, need=(False, False, False))           # nothing: no graph, no backward call
-    assert not y.requires_grad and len(seen) == 3
+    loc.check_op_launches_only_needed_legs(monkeypatch, cc.FAMILY, _op, "conv2d_backward", ("k3_4to8",), name_in_label=False)
 
 
 def test_op_pack_cache_is_reused_and_rebuilt_after_an_in_place_update():
@@ -135,11 +105,7 @@ def test_op_pack_cache_is_reused_and_rebuilt_after_an_in_place_update():
 
 
 def test_op_nchw_input_gives_the_channels_last_bits():
-    for name in ("k5_12to36", "k3_p2"):
-        a, b = _op_run(name, channels_last=True), _op_run(name, channels_last=False)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1].grad, b[1].grad) and torch.equal(a[2].grad, b[2].grad)
-        assert b[0].is_contiguous(memory_format=torch.channels_last)
-        assert b[1].grad.is_contiguous()                                # the gradient of an NCHW leaf comes back NCHW
+    loc.check_op_nchw_bits(cc.FAMILY, _op, ("k5_12to36", "k3_p2"))
 
 
 def test_op_fake_kernel_shapes_and_refusals():

@@ -7,10 +7,11 @@ import copy
 import pytest
 import torch
 import torch.nn as nn
-from torch.utils._python_dispatch import TorchDispatchMode
 
 from tests import encoder_golden as eg
+from tests import layer_op_checks as loc
 from tests import reppad_cases as rc
+from tests.parity import Spy
 
 pytestmark = pytest.mark.gpu
 
@@ -60,38 +61,23 @@ def test_abi_bad_calls_are_refused_with_a_message_and_launch_nothing(L, B):
 
 
 # ---- torch.ops.kpnerf.conv2d_replicate ----
-def _op_case(name):
+def _op(c):
     """the case as the operator sees it: the kind follows the weight, so the 7x7 weight with 4 input channels of rp7_2x2 is a stem there
     (NCHW input, no input gradient) - the ABI serves it under either kind"""
     from keypointnerf_amd import ops
-    c = rc.CASES[name]
-    return dict(c, kind=ops.conv2d_rp_kind(rc.w_shape(c)))
-
-
-def _op_run(name, channels_last=True, need=(True, True, True)):
-    import keypointnerf_amd.torch_ops  # noqa: F401
-    c = _op_case(name)
-    (x, w, b, g), _, _ = rc.reference(name)
-    xd = x.cuda().contiguous(memory_format=torch.channels_last) if channels_last else x.cuda().contiguous()
-    xd.requires_grad_(need[0] and c["kind"] != rc.STEM7)
-    wd = w.cuda().requires_grad_(need[1])
-    bd = None if b is None else b.cuda().requires_grad_(need[2])
-    y = torch.ops.kpnerf.conv2d_replicate(xd, wd, bd)
-    if y.requires_grad:
-        (y * g.cuda()).sum().backward()
-    return y.detach(), xd, wd, bd
+    return dict(c, kind=ops.conv2d_rp_kind(rc.w_shape(c))), lambda x, w, b: torch.ops.kpnerf.conv2d_replicate(x, w, b)
 
 
 @pytest.mark.parametrize("name", sorted(rc.CASES))
 def test_op_autograd_gives_the_bits_of_the_abi(L, B, name):
     """the operator under autograd runs the very ABI calls: y, dX, dW, db equal the driver's bits (and so meet the bar against fp64)"""
-    c = _op_case(name)
+    c, _ = _op(rc.CASES[name])
     assert (c["kind"] != rc.CASES[name]["kind"]) == (name == "rp7_2x2")
     (x, w, b, g), _, _ = rc.reference(name)
     packed = rc.pack(L, B, c, w.numpy())
     y_abi = rc.forward(L, B, c, rc.x_layout(c, x), packed, None if b is None else b.numpy())
     abi = rc.backward(L, B, c, rc.x_layout(c, x), rc.nhwc(g), packed)
-    y, xd, wd, bd = _op_run(name)
+    y, xd, wd, bd = loc.op_run(rc.FAMILY, _op, name)
     assert y.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(y.cpu(), torch.from_numpy(rc.nchw(y_abi)))
     assert torch.equal(wd.grad.cpu(), torch.from_numpy(abi["dw"]))
@@ -102,41 +88,11 @@ def test_op_autograd_gives_the_bits_of_the_abi(L, B, name):
 
 
 def test_op_launches_only_the_legs_that_need_a_gradient(monkeypatch):
-    from keypointnerf_amd import ops
-    seen = []
-    real = ops.conv2d_rp_backward
-
-    def spy(*a, **kw):
-        seen.append((kw["want_dx"], kw["want_dw"], kw["want_db"]))
-        return real(*a, **kw)
-
-    monkeypatch.setattr(ops, "conv2d_rp_backward", spy)
-    for name in ("rp3_4to8", "rp7_8to4"):
-        del seen[:]
-        _, r64, e_ref = rc.reference(name)
-        _, xd, wd, bd = _op_run(name, need=(True, False, False))            # a frozen layer: dX alone
-        assert seen == [(True, False, False)] and wd.grad is None and bd.grad is None
-        rc.check(f"{name} x only dx", xd.grad.cpu().numpy(), r64["dx"], e_ref["dx"])
-        _, xd, wd, bd = _op_run(name, need=(False, True, False))            # dW alone
-        assert seen[1:] == [(False, True, False)] and xd.grad is None and bd.grad is None
-        rc.check(f"{name} weight only dw", wd.grad.cpu().numpy(), r64["dw"], e_ref["dw"])
-        _, xd, wd, bd = _op_run(name, need=(False, True, True))
-        assert seen[2:] == [(False, True, True)] and xd.grad is None
-        rc.check(f"{name} weight and bias db", bd.grad.cpu().numpy(), r64["db"], e_ref["db"])
-        y, _, _, _ = _op_run(name, need=(False, False, False))             # nothing: no graph, no backward call
-        assert not y.requires_grad and len(seen) == 3
-    del seen[:]
-    _, _, wd, bd = _op_run("rp7stem_3to16", need=(False, False, True))    # the stem with a frozen weight: db alone
-    assert seen == [(False, False, True)] and wd.grad is None and bd.grad is not None
+    loc.check_op_launches_only_needed_legs(monkeypatch, rc.FAMILY, _op, "conv2d_rp_backward", ("rp3_4to8", "rp7_8to4"), stem_name="rp7stem_3to16")
 
 
 def test_op_nchw_input_gives_the_channels_last_bits():
-    for name in ("rp3_12to36", "rp7_8to4", "rp7stem_3to16"):
-        a, b = _op_run(name, channels_last=True), _op_run(name, channels_last=False)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[2].grad, b[2].grad)
-        assert b[0].is_contiguous(memory_format=torch.channels_last)
-        if rc.CASES[name]["kind"] != rc.STEM7:
-            assert torch.equal(a[1].grad, b[1].grad) and b[1].grad.is_contiguous()      # the gradient of an NCHW leaf comes back NCHW
+    loc.check_op_nchw_bits(rc.FAMILY, _op, ("rp3_12to36", "rp7_8to4", "rp7stem_3to16"))
 
 
 def test_the_stem_op_raises_on_an_input_that_requires_a_gradient():
@@ -161,7 +117,7 @@ def narrow_case(seed=NARROW_SEED):
     return net, torch.randn(2, 3, 12, 8, generator=torch.Generator().manual_seed(72)), torch.randn(2, 4, 6, 4, generator=torch.Generator().manual_seed(73))
 
 
-def _relu_norms(net):
+def relu_norms(net):
     """the InstanceNorm2d layers with a ReLU behind them: all of the encoder's own, and the first of each ResBlk"""
     out = {}
     for parent_name, parent in net.named_modules():
@@ -171,47 +127,6 @@ def _relu_norms(net):
                 if type(m) is nn.InstanceNorm2d and isinstance(nxt, nn.ReLU):
                     out[f"{parent_name}.{n}"] = m
     return out
-
-
-def _norm_outputs(net, x, memory_format):
-    pre, hooks = {}, []
-    for n, m in _relu_norms(net).items():
-        hooks.append(m.register_forward_hook(lambda m, i, o, n=n: pre.__setitem__(n, o.detach().clone())))
-    with torch.no_grad():
-        net(x.contiguous(memory_format=memory_format))
-    for h in hooks:
-        h.remove()
-    return pre
-
-
-def narrow_margin(net, x):
-    """(smallest |InstanceNorm output| in front of a ReLU of the fp64 module, largest fp32 deviation of those outputs over both memory
-    formats)"""
-    pre64 = _norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format)
-    pre32 = [_norm_outputs(copy.deepcopy(net), x, mf) for mf in (torch.contiguous_format, torch.channels_last)]
-    assert len(pre64) == NARROW_NORMS and sum(p.numel() for p in pre64.values()) == NARROW_VALUES
-    margin = min(float(p.abs().min()) for p in pre64.values())
-    return margin, max(float((r[n].double() - p).abs().max()) for r in pre32 for n, p in pre64.items())
-
-
-def _param_grads(net, x, g):
-    """-> {"y": output, parameter name: gradient}; x needs no gradient (the stem has none to give)"""
-    y = net(x)
-    params = dict(net.named_parameters())
-    grads = torch.autograd.grad([y], list(params.values()), [g])
-    out = {"y": y.detach()}
-    out.update(dict(zip(params, grads)))
-    return out
-
-
-class _Spy(TorchDispatchMode):
-    def __init__(self):
-        super().__init__()
-        self.names = []
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        self.names.append(func.name())
-        return func(*args, **(kwargs or {}))
 
 
 FORBIDDEN = ("aten::convolution", "aten::_convolution", "aten::miopen_convolution", "aten::cudnn_convolution", "aten::replication_pad2d",
@@ -227,11 +142,11 @@ def test_a_narrow_resblk_encoder_trains_on_the_native_kernels_alone():
     no aten convolution, replication pad, batch / instance norm or ReLU runs."""
     from keypointnerf_amd import encoders
     net, x, g = narrow_case()
-    margin, e_pre = narrow_margin(net, x)
+    margin, e_pre = loc.narrow_margin(net, x, relu_norms, NARROW_NORMS, NARROW_VALUES)
     print(f"[narrow ResBlkEncoder] min|InstanceNorm output| {margin:.3e} against 8 e_ref = {8 * e_pre:.3e}")
     assert margin > 8.0 * e_pre, (margin, e_pre)
-    r64 = _param_grads(copy.deepcopy(net).double(), x.double(), g.double())
-    runs32 = [_param_grads(copy.deepcopy(net), x.contiguous(memory_format=mf), g) for mf in (torch.contiguous_format, torch.channels_last)]
+    r64 = loc.param_grads(copy.deepcopy(net).double(), x.double(), g.double())
+    runs32 = [loc.param_grads(copy.deepcopy(net), x.contiguous(memory_format=mf), g) for mf in (torch.contiguous_format, torch.channels_last)]
     dev = copy.deepcopy(net).cuda()
     keys, names = list(dev.state_dict().keys()), [n for n, _ in dev.named_parameters()]
     report = encoders.install_native_tex(dev)
@@ -239,8 +154,8 @@ def test_a_narrow_resblk_encoder_trains_on_the_native_kernels_alone():
     assert len(report["strided"][0]) == 3 and len(report["norms"][0]) == 8
     assert list(dev.state_dict().keys()) == keys and [n for n, _ in dev.named_parameters()] == names
     calls = encoders.NativeTraining.tex_calls
-    with _Spy() as spy:
-        got = _param_grads(dev, x.cuda(), g.cuda())
+    with Spy() as spy:
+        got = loc.param_grads(dev, x.cuda(), g.cuda())
     assert encoders.NativeTraining.tex_calls == calls + 1
     bad = sorted({n for n in spy.names if n.startswith(FORBIDDEN)})
     assert not bad, bad
@@ -269,8 +184,8 @@ def test_the_full_width_resblk_encoder_runs_and_repeats_on_the_native_kernels():
     assert report["tex"] == ([""], {}) and all(not left for _, left in report.values()), report
     N = encoders.NativeTraining
     before = (N.tex_calls, N.strided_calls, N.norm_calls)
-    with _Spy() as spy:
-        runs = [_param_grads(dev, x.cuda(), g.cuda()) for _ in range(2)]
+    with Spy() as spy:
+        runs = [loc.param_grads(dev, x.cuda(), g.cuda()) for _ in range(2)]
     after = (N.tex_calls, N.strided_calls, N.norm_calls)
     assert tuple(a - b for a, b in zip(after, before)) == (2, 2 * 5, 0)                 # the fused calls bypass the rebound norms
     bad = sorted({n for n in spy.names if n.startswith(FORBIDDEN)})

@@ -8,10 +8,11 @@ import ctypes
 import numpy as np
 import pytest
 import torch
-from torch.utils._python_dispatch import TorchDispatchMode
 
+from tests import layer_op_checks as loc
 from tests import res_encoder_cases as ec
 from tests import test_gpu_reppad as tr
+from tests.parity import Spy
 
 pytestmark = pytest.mark.gpu
 
@@ -173,20 +174,6 @@ def test_fused_forward_has_the_bits_of_the_per_layer_native_path(L, B, name):
     assert torch.equal(plain, fused)
 
 
-class _Spy(TorchDispatchMode):
-    """the operator names, and for aten::add the largest tensor argument"""
-
-    def __init__(self):
-        super().__init__()
-        self.names, self.adds = [], []
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        self.names.append(func.name())
-        if func.name().startswith("aten::add"):
-            self.adds.append(max([a.numel() for a in args if isinstance(a, torch.Tensor)] + [0]))
-        return func(*args, **(kwargs or {}))
-
-
 @pytest.mark.parametrize("name", ["narrow", "up2"])
 def test_a_fused_encoder_is_one_operator_forward_and_one_backward_and_meets_the_bar(name):
     """install_native_tex(fused=True) against the CPU fp64 module: the output and every parameter gradient within the bar; under a
@@ -202,8 +189,8 @@ def test_a_fused_encoder_is_one_operator_forward_and_one_backward_and_meets_the_
     assert list(dev.state_dict().keys()) == keys and [n for n, _ in dev.named_parameters()] == names
     N_ = encoders.NativeTraining
     calls = N_.fused_tex_calls, N_.tex_calls, N_.strided_calls, N_.norm_calls
-    with _Spy() as spy:
-        got = tr._param_grads(dev, x.cuda(), g.cuda())
+    with Spy() as spy:
+        got = loc.param_grads(dev, x.cuda(), g.cuda())
     assert (N_.fused_tex_calls, N_.tex_calls, N_.strided_calls, N_.norm_calls) == (calls[0] + 1,) + calls[1:]
     bad = sorted({n for n in spy.names if n.startswith(tr.FORBIDDEN)})
     assert not bad, bad

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import layer_op_checks as loc
 from tests import resample_cases as rc
 
 pytestmark = pytest.mark.gpu
@@ -168,19 +169,6 @@ def test_wiring_without_a_relu_to_flip():
     assert "forward" not in dev.__dict__ and "_kpnerf_hourglass_saved" not in dev.__dict__
 
 
-def _norm_outputs(net, x, memory_format):
-    """{norm name: its output before the in-place ReLU}"""
-    pre, hooks = {}, []
-    for n, m in net.named_modules():
-        if isinstance(m, torch.nn.GroupNorm):
-            hooks.append(m.register_forward_hook(lambda m, i, o, n=n: pre.__setitem__(n, o.detach().clone())))
-    with torch.no_grad():
-        net(x.contiguous(memory_format=memory_format))
-    for h in hooks:
-        h.remove()
-    return pre
-
-
 @pytest.mark.parametrize("depth,shape,seed", [(2, (1, 16, 8, 8), 2), (1, (2, 16, 4, 6), 1)])
 def test_the_real_hourglass_trains_on_the_native_kernels(depth, shape, seed):
     """tests/encoder_golden.HourGlass with install_native_hourglass + install_native_blocks against the CPU fp64 module.  e_ref per
@@ -194,8 +182,8 @@ def test_the_real_hourglass_trains_on_the_native_kernels(depth, shape, seed):
     x, g = torch.randn(*shape, generator=gen), torch.randn(*shape, generator=gen)
     formats = (torch.contiguous_format, torch.channels_last)
     dev_err = lambda a, b: float((a.double() - b).abs().max())
-    pre64 = _norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format)
-    pre32 = [_norm_outputs(copy.deepcopy(net), x, mf) for mf in formats]
+    pre64 = loc.norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format)
+    pre32 = [loc.norm_outputs(copy.deepcopy(net), x, mf) for mf in formats]
     assert len(pre64) == 3 * (3 * depth + 1)                            # bn1 .. bn3 of every block; bn4 never runs
     margin = min(float(p.abs().min()) for p in pre64.values())
     e_pre = max(dev_err(r[n], p) for r in pre32 for n, p in pre64.items())

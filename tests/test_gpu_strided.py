@@ -4,14 +4,16 @@ encoders.install_native_strided on a small stack and encoders.install_native_geo
 Cases, reference and bar: tests/strided_cases.py - every comparison is against the CPU fp64 result,
 |native - fp64| <= 4 e_ref + 1 ulp(max|fp64|) per tensor, e_ref the deviation of CPU fp32 torch from the same fp64 result."""
 import copy
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
-from torch.utils._python_dispatch import TorchDispatchMode
 
 from tests import encoder_golden as eg
+from tests import layer_op_checks as loc
 from tests import strided_cases as sc
+from tests.parity import Spy
 from tests.resample_cases import seed_parameters
 
 pytestmark = pytest.mark.gpu
@@ -63,21 +65,7 @@ def test_abi_bad_calls_are_refused_with_a_message_and_launch_nothing(L, B):
 
 # ---- torch.ops.kpnerf.conv2d_down2 / conv_transpose2d_up2 ----
 def _op(c):
-    return torch.ops.kpnerf.conv_transpose2d_up2 if c["kind"] == sc.DECONV3 else torch.ops.kpnerf.conv2d_down2
-
-
-def _op_run(name, channels_last=True, need=(True, True, True)):
-    import keypointnerf_amd.torch_ops  # noqa: F401
-    c = sc.CASES[name]
-    (x, w, b, g), _, _ = sc.reference(name)
-    xd = x.cuda().contiguous(memory_format=torch.channels_last) if channels_last else x.cuda().contiguous()
-    xd.requires_grad_(need[0] and c["kind"] != sc.STEM7)
-    wd = w.cuda().requires_grad_(need[1])
-    bd = None if b is None else b.cuda().requires_grad_(need[2])
-    y = _op(c)(xd, wd, bd)
-    if y.requires_grad:
-        (y * g.cuda()).sum().backward()
-    return y.detach(), xd, wd, bd
+    return c, (torch.ops.kpnerf.conv_transpose2d_up2 if c["kind"] == sc.DECONV3 else torch.ops.kpnerf.conv2d_down2)
 
 
 @pytest.mark.parametrize("name", sorted(sc.CASES))
@@ -88,7 +76,7 @@ def test_op_autograd_gives_the_bits_of_the_abi(L, B, name):
     packed = sc.pack(L, B, c, w.numpy())
     y_abi = sc.forward(L, B, c, sc.x_layout(c, x), packed, None if b is None else b.numpy())
     abi = sc.backward(L, B, c, sc.x_layout(c, x), sc.nhwc(g), packed)
-    y, xd, wd, bd = _op_run(name)
+    y, xd, wd, bd = loc.op_run(sc.FAMILY, _op, name)
     assert y.is_contiguous(memory_format=torch.channels_last)
     assert torch.equal(y.cpu(), torch.from_numpy(sc.nchw(y_abi)))
     assert torch.equal(wd.grad.cpu(), torch.from_numpy(abi["dw"]))
@@ -99,41 +87,11 @@ def test_op_autograd_gives_the_bits_of_the_abi(L, B, name):
 
 
 def test_op_launches_only_the_legs_that_need_a_gradient(monkeypatch):
-    from keypointnerf_amd import ops
-    seen = []
-    real = ops.conv2d_s2_backward
-
-    def spy(*a, **kw):
-        seen.append((kw["want_dx"], kw["want_dw"], kw["want_db"]))
-        return real(*a, **kw)
-
-    monkeypatch.setattr(ops, "conv2d_s2_backward", spy)
-    for name in ("s2_4to8", "up_8to4"):
-        del seen[:]
-        _, r64, e_ref = sc.reference(name)
-        _, xd, wd, bd = _op_run(name, need=(True, False, False))            # a frozen layer: dX alone
-        assert seen == [(True, False, False)] and wd.grad is None and bd.grad is None
-        sc.check(f"{name} x only dx", xd.grad.cpu().numpy(), r64["dx"], e_ref["dx"])
-        _, xd, wd, bd = _op_run(name, need=(False, True, False))            # dW alone
-        assert seen[1:] == [(False, True, False)] and xd.grad is None and bd.grad is None
-        sc.check(f"{name} weight only dw", wd.grad.cpu().numpy(), r64["dw"], e_ref["dw"])
-        _, xd, wd, bd = _op_run(name, need=(False, True, True))
-        assert seen[2:] == [(False, True, True)] and xd.grad is None
-        sc.check(f"{name} weight and bias db", bd.grad.cpu().numpy(), r64["db"], e_ref["db"])
-        y, _, _, _ = _op_run(name, need=(False, False, False))             # nothing: no graph, no backward call
-        assert not y.requires_grad and len(seen) == 3
-    del seen[:]
-    _, _, wd, bd = _op_run("stem_3to64", need=(False, False, True))       # the stem with a frozen weight: db alone
-    assert seen == [(False, False, True)] and wd.grad is None and bd.grad is not None
+    loc.check_op_launches_only_needed_legs(monkeypatch, sc.FAMILY, _op, "conv2d_s2_backward", ("s2_4to8", "up_8to4"), stem_name="stem_3to64")
 
 
 def test_op_nchw_input_gives_the_channels_last_bits():
-    for name in ("s2_12to36", "up_36to12", "stem_odd"):
-        a, b = _op_run(name, channels_last=True), _op_run(name, channels_last=False)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[2].grad, b[2].grad)
-        assert b[0].is_contiguous(memory_format=torch.channels_last)
-        if sc.CASES[name]["kind"] != sc.STEM7:
-            assert torch.equal(a[1].grad, b[1].grad) and b[1].grad.is_contiguous()      # the gradient of an NCHW leaf comes back NCHW
+    loc.check_op_nchw_bits(sc.FAMILY, _op, ("s2_12to36", "up_36to12", "stem_odd"))
 
 
 def test_the_stem_op_raises_on_an_input_that_requires_a_gradient():
@@ -154,15 +112,7 @@ def _stack(seed=4):
     return seed_parameters(net, seed)
 
 
-def _param_grads(net, x, gs):
-    """-> {"y<i>": output, parameter name: gradient or None}; x needs no gradient (the stem has none to give)"""
-    ys = net(x)
-    ys = list(ys) if isinstance(ys, (list, tuple)) else [ys]
-    params = dict(net.named_parameters())
-    grads = torch.autograd.grad(ys, list(params.values()), gs, allow_unused=True)
-    out = {f"y{i}": y.detach() for i, y in enumerate(ys)}
-    out.update(dict(zip(params, grads)))
-    return out
+_param_grads = functools.partial(loc.param_grads, allow_unused=True)      # the blocks that keep their width never run their bn4
 
 
 def test_install_native_strided_serves_the_eligible_layers_and_matches_fp64():
@@ -223,39 +173,6 @@ def narrow_case(seed=NARROW_SEED):
     return net, torch.randn(1, 3, 16, 16, generator=gen), [torch.randn(1, 16, 4, 4, generator=gen), torch.randn(1, 8, 16, 16, generator=gen)]
 
 
-def _norm_outputs(net, x, memory_format):
-    """{norm name: its output before the ReLU behind it}"""
-    pre, hooks = {}, []
-    for n, m in net.named_modules():
-        if isinstance(m, nn.GroupNorm):
-            hooks.append(m.register_forward_hook(lambda m, i, o, n=n: pre.__setitem__(n, o.detach().clone())))
-    with torch.no_grad():
-        net(x.contiguous(memory_format=memory_format))
-    for h in hooks:
-        h.remove()
-    return pre
-
-
-def narrow_margin(net, x):
-    """(smallest |GroupNorm output| of the fp64 module, largest fp32 deviation of those outputs over both memory formats)"""
-    formats = (torch.contiguous_format, torch.channels_last)
-    pre64 = _norm_outputs(copy.deepcopy(net).double(), x.double(), torch.contiguous_format)
-    pre32 = [_norm_outputs(copy.deepcopy(net), x, mf) for mf in formats]
-    assert len(pre64) == NARROW_NORMS
-    margin = min(float(p.abs().min()) for p in pre64.values())
-    return margin, max(float((r[n].double() - p).abs().max()) for r in pre32 for n, p in pre64.items())
-
-
-class _Spy(TorchDispatchMode):
-    def __init__(self):
-        super().__init__()
-        self.names = []
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        self.names.append(func.name())
-        return func(*args, **(kwargs or {}))
-
-
 FORBIDDEN = ("aten::convolution", "aten::convolution_backward", "aten::native_group_norm", "aten::avg_pool2d", "aten::upsample_bicubic2d",
              "aten::relu", "aten::threshold_backward", "aten::cudnn_convolution", "aten::miopen_convolution", "aten::_convolution")
 
@@ -268,7 +185,7 @@ def test_a_narrow_hgfilter_trains_on_the_native_kernels_alone():
     Under a dispatch spy over forward and backward no aten convolution, group norm, pool, bicubic upsample or ReLU runs."""
     from keypointnerf_amd import encoders
     net, x, gs = narrow_case()
-    margin, e_pre = narrow_margin(net, x)
+    margin, e_pre = loc.narrow_margin(net, x, loc.group_norms, NARROW_NORMS)
     print(f"[narrow HGFilterV2] min|GroupNorm output| {margin:.3e} against 8 e_ref = {8 * e_pre:.3e}")
     assert margin > 8.0 * e_pre, (margin, e_pre)
     r64 = _param_grads(copy.deepcopy(net).double(), x.double(), [g.double() for g in gs])
@@ -281,7 +198,7 @@ def test_a_narrow_hgfilter_trains_on_the_native_kernels_alone():
     assert sorted(report["convs"][0]) == sorted(n for n, m in dev.named_modules() if type(m) is nn.Conv2d and n != "conv1")
     assert list(dev.state_dict().keys()) == keys and [n for n, _ in dev.named_parameters()] == names
     calls = encoders.NativeTraining.geo_calls
-    with _Spy() as spy:
+    with Spy() as spy:
         got = _param_grads(dev, x.cuda(), [g.cuda() for g in gs])
     assert encoders.NativeTraining.geo_calls == calls + 1
     bad = sorted({n for n in spy.names if n.startswith(FORBIDDEN)})

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from keypointnerf_amd import lib as kl
-from tests.conv_cases import DeviceArrays, HostArrays
+from tests.parity import DeviceArrays, HostArrays, bits
 
 #        V, image,    geo0,     geo1,     tex
 CASES = {"odd": (2, (19, 23), (9, 11), (7, 5), (10, 13)),
@@ -28,10 +28,6 @@ def _env(backend):
         return sh.simt_lib(), HostArrays()
     assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
     return kl.get_library(), DeviceArrays()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def inputs(case, seed=0):
