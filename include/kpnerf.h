@@ -60,6 +60,9 @@ extern "C" {
  * kpn_res_encoder_forward, kpn_res_encoder_backward) is additive within 10 in the same way */
 /* still 10: the arithmetic selector of the stride-1 convolution and the ConvBlock (KPN_CONV_F32 / KPN_CONV_BF16X3, kpn_conv2d_ex_*,
  * kpn_conv_block_ex_*) is additive within 10 in the same way: kpn_conv2d_* and kpn_conv_block_* are its arith = KPN_CONV_F32 case */
+/* still 10: a whole HGFilterV2 as one differentiable operator (kpn_hg_filter_desc, kpn_hg_filter_params, kpn_hg_filter_grads,
+ * kpn_hg_filter_tensors, kpn_hg_filter_workspace_bytes, kpn_hg_filter_state_floats, kpn_hg_filter_packed_floats,
+ * kpn_hg_filter_pack_device, kpn_hg_filter_forward, kpn_hg_filter_backward) is additive within 10 in the same way */
 #define KPN_ABI_VERSION 10
 #define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
 #define KPN_MAX_VIEWS 16
@@ -923,6 +926,82 @@ int kpn_res_encoder_forward(const kpn_res_encoder_desc* desc, const float* x, co
                             float* state, void* workspace, size_t workspace_bytes, void* stream);
 int kpn_res_encoder_backward(const kpn_res_encoder_desc* desc, const float* x, const float* dy, const float* packed, const float* state,
                              float* const* dw, float* const* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A whole HGFilterV2(n_stack = 1, hd = False, norm = "group") (src/utils.py:322-414) for training, forward and backward, as one call
+ * each: replaces the stem, every ConvBlock, the HourGlass with its pools and bicubic upsamples, unpack1 / conv_out, conv_last0 / bn_end0 /
+ * l0, every fused norm + ReLU, and the sums autograd makes where a tensor has two consumers.
+ * Layers: conv1 (7x7, stride 2, pad 3, in_ch -> c_stem, bias) + bn1 + ReLU; ConvBlocks conv2 (c_stem -> c2), [avg-pool 2], conv3
+ * (c2 -> c3), conv4 (c3 -> c4); HourGlass(depth, c4); ConvBlock top_m_0 (c4 -> c4); conv_last0 (1x1, c4 -> c4, bias) + bn_end0 + ReLU;
+ * l0 (1x1, c4 -> out_ch, bias).  The hd branch off the conv2 output: unpack1 = ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1,
+ * c2 -> c_hd, no bias) + GroupNorm + ReLU, conv_out (5x5, pad 2, c_hd -> out_ch_hd, bias).  Every norm is GroupNorm(min(32, C), C) with
+ * parameters and the one eps.  The reference's instance is c_stem 64, c2 128, c3 128, c4 256, depth 4, c_hd 32.
+ * x is the NCHW image (N, in_ch, H, W), read as it is (KPN_S2_STEM7); out (N, H/4, W/4, out_ch) and x_hd (N, H, W, out_ch_hd) are NHWC,
+ * dense, fp32.
+ * Scope: in_ch in 1 .. 4; every ConvBlock one that kpn_conv_block_* serves (so c_stem, c2 / 2 .. c4 / 4 powers of two >= 4); c_hd a
+ * power of two in 4 .. 1024; out_ch, out_ch_hd multiples of 4 in 4 .. 1024; depth in 1 .. 8; H, W even with H / 2 and W / 2 divisible
+ * by 2^(depth + 1); N in 1 .. 65535; every tensor below 2^31 elements; eps > 0; every pointer but x 16-byte aligned.  Anything else
+ * is refused with KPN_EINVAL (the size queries return 0), kpn_last_error() names the field, and nothing is launched.  Kernels:
+ * csrc/encoder_kernels.hip; dataflow: csrc/api_geo_train.hip.
+ *   tensors (kpn_hg_filter_tensors of them), in this order: conv1 weight, bias; bn1 weight, bias; per ConvBlock in dataflow order -
+ *            conv2, conv3, conv4, then per HourGlass level from the outermost in b1, b2, then the next level (b2_plus at the innermost),
+ *            b3; top_m_0 - and per leg (bn1 / conv1, bn2 / conv2, bn3 / conv3 and, for cin != cout, bn4 / downsample) the norm's weight,
+ *            its bias and the convolution's weight, 9 or 12 tensors; unpack1.conv weight; unpack1.norm weight, bias; conv_out weight,
+ *            bias; conv_last0 weight, bias; bn_end0 weight, bias; l0 weight, bias.  Weights as the module holds them (OIHW; IOHW for
+ *            unpack1.conv).
+ *   params:  tensors[i] in that order - the forward and the backward read the norm parameters and the biases from it and never the plain
+ *            convolution weights, whose entries may be NULL - and packed (kpn_hg_filter_packed_floats / _pack_device, which read only the
+ *            widths, depth and in_ch / out_ch*): per convolution weight, in tensor order, what the layer's own packer writes
+ *            (kpn_conv2d_s2_pack_device for conv1 and unpack1.conv, kpn_conv2d_pack_device for the others).
+ *   forward: the dataflow of kpn_geo_encode with nothing released.  relu(bn1(conv1)) is materialised (it is a block input); unpack1.norm
+ *            + ReLU runs inside the loads of conv_out and bn_end0 + ReLU inside the loads of l0; each HourGlass level's b1 output is
+ *            overwritten in place by the skip sum.  out and x_hd have the bits of the same network computed operator by operator
+ *            (kpn_conv2d_s2_forward, kpn_group_norm_forward(relu = 1), kpn_conv_block_forward, kpn_avg_pool2_forward,
+ *            kpn_upsample2x_add_forward, kpn_conv2d_forward).
+ *   state (kpn_hg_filter_state_floats; written by the forward, read by the backward), in this order, with (h1, w1) = (H/2, W/2),
+ *            (h2, w2) = (H/4, W/4), S(block) = kpn_conv_block_state_floats of that block and stats(C) = 2 N C + 2 N min(32, C) (scale,
+ *            shift, mean, rstd):
+ *              conv1 output (N, h1, w1, c_stem); stats(c_stem) of bn1; relu(bn1(.)) (N, h1, w1, c_stem); S(conv2); the conv2 output
+ *              (N, h1, w1, c2); the unpack1.conv output (N, H, W, c_hd); stats(c_hd) of unpack1.norm; the pooled conv2 output
+ *              (N, h2, w2, c2); S(conv3); the conv3 output (N, h2, w2, c3); S(conv4); the conv4 output (N, h2, w2, c4); per HourGlass
+ *              level from the outermost, on the level's grid (h, w): S(b1); the level's output b1(inp) + U(low3) (N, h, w, c4); the
+ *              pooled input (N, h/2, w/2, c4); S(b2); the b2 output; the next level (or S(b2_plus) and its output); S(b3); then
+ *              S(top_m_0); the top_m_0 output (N, h2, w2, c4); the conv_last0 output (N, h2, w2, c4); stats(c4) of bn_end0.
+ *            kpn_hg_filter_state_floats is the sum of these.  out, x_hd, the b3 outputs, the un-summed b1 outputs and every normalised
+ *            tensor but relu(bn1(.)) are not kept.
+ *   backward: d_out (N, H/4, W/4, out_ch) and d_x_hd (N, H, W, out_ch_hd), NHWC; either may be NULL (that branch contributes nothing), not
+ *            both.  grads[i] per tensor in tensor order, each of which may be NULL: nothing is written for a NULL result, only the legs
+ *            that a wanted gradient needs are launched, and the walk ends at the lowest layer whose gradient is wanted.  Results are
+ *            overwritten, not accumulated.  There is no input gradient (the stem has none).  Every layer's gradients are those of its own
+ *            single-layer backward (kpn_conv2d_backward, kpn_conv2d_s2_backward, kpn_group_norm_backward, kpn_conv_block_backward,
+ *            kpn_upsample2x_add_backward), the norm and the ReLU recomputed in the loads of the weight gradients of conv_out and l0, the
+ *            norm gradients in place.  Where a tensor has two consumers - the input of an HourGlass level (b1 and the pool), the conv2
+ *            output (unpack1.conv and the pool) - the other consumer's gradient is written first and complete, then
+ *            0.25 g_low[y / 2][x / 2] is added onto it (k_enc_pool2_bwd_acc): one fp32 add of two finished values, the bits of
+ *            kpn_avg_pool2_backward followed by a tensor add in either order.
+ * `workspace` (kpn_hg_filter_workspace_bytes; 0 = unsupported descriptor) serves the forward and the backward alike.
+ * No float atomics: every result is bit-identical from run to run, and an image's results do not depend on its batch. */
+typedef struct kpn_hg_filter_desc {
+    int32_t N, H, W, in_ch, c_stem, c2, c3, c4, depth, c_hd, out_ch_hd, out_ch;
+    float eps;
+} kpn_hg_filter_desc;
+typedef struct kpn_hg_filter_params {
+    const float* const* tensors;      /* kpn_hg_filter_tensors entries, in tensor order */
+    const float* packed;              /* kpn_hg_filter_pack_device */
+} kpn_hg_filter_params;
+typedef struct kpn_hg_filter_grads {
+    float* const* tensors;            /* kpn_hg_filter_tensors entries, in tensor order; any may be NULL */
+} kpn_hg_filter_grads;
+int32_t kpn_hg_filter_tensors(const kpn_hg_filter_desc* desc);
+size_t kpn_hg_filter_workspace_bytes(const kpn_hg_filter_desc* desc);
+size_t kpn_hg_filter_state_floats(const kpn_hg_filter_desc* desc);
+size_t kpn_hg_filter_packed_floats(const kpn_hg_filter_desc* desc);
+int kpn_hg_filter_pack_device(const kpn_hg_filter_desc* desc, const float* const* tensors, float* packed, void* stream);
+int kpn_hg_filter_forward(const kpn_hg_filter_desc* desc, const float* x, const kpn_hg_filter_params* params, float* out, float* x_hd,
+                          float* state, void* workspace, size_t workspace_bytes, void* stream);
+int kpn_hg_filter_backward(const kpn_hg_filter_desc* desc, const float* x, const float* d_out, const float* d_x_hd,
+                           const kpn_hg_filter_params* params, const float* state, const kpn_hg_filter_grads* grads, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -91,32 +91,10 @@ Plan plan(const kpn_conv_block_desc* d, int arith = KPN_CONV_F32) {
     p.bytes = std::max<size_t>(std::max(f.o, b.o), 256);
     return p;
 }
-}  // namespace blk
-
-#define KPN_BLOCK_REQUIRE_DESC(desc) do { if (const char* e_ = blk::desc_error(desc)) return fail(KPN_EINVAL, std::string("kpn_conv_block_desc: ") + e_); } while (0)
-
-#define KPN_BLOCK_REQUIRE_ARITH(arith) do { if (const char* e_ = enc::arith_error(arith)) return fail(KPN_EINVAL, std::string("kpn_conv_block_ex: ") + e_); } while (0)
-
-// The four entry points with the arithmetic chosen by the caller; kpn_conv_block_* below are their arith = KPN_CONV_F32 case.
-extern "C" size_t kpn_conv_block_ex_workspace_bytes(const kpn_conv_block_desc* desc, int32_t arith) {
-    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).bytes;
-}
-extern "C" size_t kpn_conv_block_ex_state_floats(const kpn_conv_block_desc* desc, int32_t arith) {
-    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).state_floats;
-}
-extern "C" int kpn_conv_block_ex_forward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const kpn_conv_block_params* params,
-                                         float* y, float* state, void* workspace, size_t workspace_bytes, void* stream) {
-    KPN_BLOCK_REQUIRE_DESC(desc);
-    KPN_BLOCK_REQUIRE_ARITH(arith);
-    KPN_REQUIRE(x && params && y && state && workspace, "null pointer");
-    const blk::Plan p = blk::plan(desc, arith);
-    for (int i = 0; i < p.nlegs; ++i) {
-        KPN_REQUIRE(params->gamma[i] && params->beta[i] && params->packed[i], "params: gamma / beta / packed of a leg is null");
-        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->beta[i], params->packed[i]}), "params: gamma / beta / packed must be 16-byte aligned");
-    }
-    KPN_REQUIRE(enc::aligned16({x, y, state, workspace}), "x / y / state / workspace must be 16-byte aligned");
-    KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
-    char* ws = static_cast<char*>(workspace);
+// The launches of a block's forward for a plan of its descriptor: arguments checked by the caller, `ws` the block's workspace (p.bytes).
+// kpn_conv_block_ex_forward and the operators that contain blocks (api_geo_train.hip) run this one body
+void forward(const Plan& p, const kpn_conv_block_desc* desc, const float* x, const kpn_conv_block_params* params, float* y, float* state,
+             char* ws, void* stream) {
     double* stat = reinterpret_cast<double*>(ws + p.f_stats);
     float* part = reinterpret_cast<float*>(ws + p.f_conv);
     const int N = desc->N, c = desc->cout;
@@ -147,24 +125,10 @@ extern "C" int kpn_conv_block_ex_forward(const kpn_conv_block_desc* desc, int32_
     stats(2, state + c / 2, p.cs);
     conv(2, state + c / 2, p.cs, y + p.cs, c, base + p.cs, base_cs);
     enc::launch_add_cs(state, p.cs, base, base_cs, y, c, p.P, p.cs, stream);
-    return check_launch("kpn_conv_block_forward");
 }
-extern "C" int kpn_conv_block_ex_backward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const float* dy,
-                                          const kpn_conv_block_params* params, const float* state, float* dx, const kpn_conv_block_grads* grads,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
-    KPN_BLOCK_REQUIRE_DESC(desc);
-    KPN_BLOCK_REQUIRE_ARITH(arith);
-    KPN_REQUIRE(x && dy && params && state && grads && workspace, "null pointer");
-    const blk::Plan p = blk::plan(desc, arith);
-    for (int i = 0; i < p.nlegs; ++i) {
-        KPN_REQUIRE(params->gamma[i] && params->packed[i], "params: gamma / packed of a leg is null");
-        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->packed[i], grads->dgamma[i], grads->dbeta[i], grads->dw[i]}),
-                    "params / grads: gamma / packed / dgamma / dbeta / dw must be 16-byte aligned");
-    }
-    KPN_REQUIRE(p.nlegs == 4 || !(grads->dgamma[3] || grads->dbeta[3] || grads->dw[3]), "grads of the downsample leg given for cin == cout");
-    KPN_REQUIRE(enc::aligned16({x, dy, state, dx, workspace}), "x / dy / state / dx / workspace must be 16-byte aligned");
-    KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
-    char* ws = static_cast<char*>(workspace);
+// The launches of a block's backward, in the same way
+void backward(const Plan& p, const kpn_conv_block_desc* desc, const float* x, const float* dy, const kpn_conv_block_params* params,
+              const float* state, float* dx, const kpn_conv_block_grads* grads, char* ws, void* stream) {
     float* dn = reinterpret_cast<float*>(ws + p.b_dn);
     float* g1 = reinterpret_cast<float*>(ws + p.b_g1);       // what leg 2 hands to leg 1 (c / 2 channels)
     float* g2 = reinterpret_cast<float*>(ws + p.b_g2);       // what leg 3 hands to leg 2 (c / 4 channels)
@@ -198,6 +162,51 @@ extern "C" int kpn_conv_block_ex_backward(const kpn_conv_block_desc* desc, int32
     if (up3) leg(1, state, p.cs, g2, c / 4, up2 ? g1 : nullptr, dy, c);
     if (up2) leg(0, x, desc->cin, g1, c / 2, up1 ? dx : nullptr, down ? nullptr : dy, c);
     if (down) leg(3, x, desc->cin, dy, c, dx, dx, desc->cin);
+}
+}  // namespace blk
+
+#define KPN_BLOCK_REQUIRE_DESC(desc) do { if (const char* e_ = blk::desc_error(desc)) return fail(KPN_EINVAL, std::string("kpn_conv_block_desc: ") + e_); } while (0)
+
+#define KPN_BLOCK_REQUIRE_ARITH(arith) do { if (const char* e_ = enc::arith_error(arith)) return fail(KPN_EINVAL, std::string("kpn_conv_block_ex: ") + e_); } while (0)
+
+// The four entry points with the arithmetic chosen by the caller; kpn_conv_block_* below are their arith = KPN_CONV_F32 case.
+extern "C" size_t kpn_conv_block_ex_workspace_bytes(const kpn_conv_block_desc* desc, int32_t arith) {
+    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).bytes;
+}
+extern "C" size_t kpn_conv_block_ex_state_floats(const kpn_conv_block_desc* desc, int32_t arith) {
+    return blk::desc_error(desc) || enc::arith_error(arith) ? 0 : blk::plan(desc, arith).state_floats;
+}
+extern "C" int kpn_conv_block_ex_forward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const kpn_conv_block_params* params,
+                                         float* y, float* state, void* workspace, size_t workspace_bytes, void* stream) {
+    KPN_BLOCK_REQUIRE_DESC(desc);
+    KPN_BLOCK_REQUIRE_ARITH(arith);
+    KPN_REQUIRE(x && params && y && state && workspace, "null pointer");
+    const blk::Plan p = blk::plan(desc, arith);
+    for (int i = 0; i < p.nlegs; ++i) {
+        KPN_REQUIRE(params->gamma[i] && params->beta[i] && params->packed[i], "params: gamma / beta / packed of a leg is null");
+        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->beta[i], params->packed[i]}), "params: gamma / beta / packed must be 16-byte aligned");
+    }
+    KPN_REQUIRE(enc::aligned16({x, y, state, workspace}), "x / y / state / workspace must be 16-byte aligned");
+    KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
+    blk::forward(p, desc, x, params, y, state, static_cast<char*>(workspace), stream);
+    return check_launch("kpn_conv_block_forward");
+}
+extern "C" int kpn_conv_block_ex_backward(const kpn_conv_block_desc* desc, int32_t arith, const float* x, const float* dy,
+                                          const kpn_conv_block_params* params, const float* state, float* dx, const kpn_conv_block_grads* grads,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    KPN_BLOCK_REQUIRE_DESC(desc);
+    KPN_BLOCK_REQUIRE_ARITH(arith);
+    KPN_REQUIRE(x && dy && params && state && grads && workspace, "null pointer");
+    const blk::Plan p = blk::plan(desc, arith);
+    for (int i = 0; i < p.nlegs; ++i) {
+        KPN_REQUIRE(params->gamma[i] && params->packed[i], "params: gamma / packed of a leg is null");
+        KPN_REQUIRE(enc::aligned16({params->gamma[i], params->packed[i], grads->dgamma[i], grads->dbeta[i], grads->dw[i]}),
+                    "params / grads: gamma / packed / dgamma / dbeta / dw must be 16-byte aligned");
+    }
+    KPN_REQUIRE(p.nlegs == 4 || !(grads->dgamma[3] || grads->dbeta[3] || grads->dw[3]), "grads of the downsample leg given for cin == cout");
+    KPN_REQUIRE(enc::aligned16({x, dy, state, dx, workspace}), "x / dy / state / dx / workspace must be 16-byte aligned");
+    KPN_REQUIRE(workspace_bytes >= p.bytes, "workspace too small (kpn_conv_block_workspace_bytes)");
+    blk::backward(p, desc, x, dy, params, state, dx, grads, static_cast<char*>(workspace), stream);
     return check_launch("kpn_conv_block_backward");
 }
 

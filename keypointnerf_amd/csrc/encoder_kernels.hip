@@ -22,7 +22,8 @@
 // Beside it: k_enc_stats_partial / k_enc_stats_final (GroupNorm / InstanceNorm statistics in fp64 partial sums, reduced in a
 // fixed order and folded with gamma / beta into the scale / shift the next loads use), k_enc_affine (normalise [+ ReLU]
 // [+ residual] where the value is needed as a tensor), k_enc_add_cs (the sum of two channel slices), k_enc_norm_bwd_partial / _final / _dx (the gradient of statistics +
-// affine, api_norm.hip), k_enc_pool2 / k_enc_pool2_bwd (avg_pool2d(x, 2, 2) and its gradient), k_enc_upadd (bicubic x2,
+// affine, api_norm.hip), k_enc_pool2 / k_enc_pool2_bwd (avg_pool2d(x, 2, 2) and its gradient; k_enc_pool2_bwd_acc adds that gradient onto a
+// finished one: the fan-in sums of api_geo_train.hip), k_enc_upadd (bicubic x2,
 // align_corners = True, ATen's coefficients with A = -0.75 and clamped taps, fused with the up1 + up2 add of HourGlass._forward;
 // out of place or in place, with or without the added tensor), k_enc_up2_bwd (its gradient with respect to the low tensor, a gather
 // with the forward's own weights; api_resample.hip) and k_enc_pack.  No float
@@ -542,6 +543,22 @@ __global__ __launch_bounds__(256) void k_enc_pool2_bwd(const float* dy, float* d
         kpn_f32x4 v;
         for (int e = 0; e < 4; ++e) v[e] = KMUL(0.25f, g[e]);
         *reinterpret_cast<kpn_f32x4*>(dx + i * 4) = v;
+    }
+}
+
+// k_enc_pool2_bwd added onto a finished gradient of the same high tensor: dst[n][y][x][c] += 0.25 dy[n][y / 2][x / 2][c].  Where a
+// tensor feeds a pool and one other consumer (the input of an HourGlass level, the conv2 output of HGFilterV2) this is the fan-in sum:
+// one fp32 add of two complete values, the product having the bits k_enc_pool2_bwd writes.  One float4 per thread, no atomics.
+__global__ __launch_bounds__(256) void k_enc_pool2_bwd_acc(const float* dy, float* dst, int nimg, int Ho, int Wo, int C) {
+    const int c4 = C / 4, H = 2 * Ho, W = 2 * Wo;
+    const int64_t total = (int64_t)nimg * H * W * c4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4) * 4;
+        const int x = (int)((i / c4) % W), y = (int)((i / c4 / W) % H), n = (int)(i / c4 / W / H);
+        const kpn_f32x4 g = *KPN_GLOBAL4(dy + (((size_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * C + c);
+        kpn_f32x4 v = *KPN_GLOBAL4(dst + i * 4);
+        for (int e = 0; e < 4; ++e) v[e] = KADD(v[e], KMUL(0.25f, g[e]));
+        *reinterpret_cast<kpn_f32x4*>(dst + i * 4) = v;
     }
 }
 

@@ -55,6 +55,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #include "api_block.hip"
 #include "api_tex_train.hip"
 #include "api_resample.hip"
+#include "api_geo_train.hip"  // the blocks, the layers and the resampling steps above as one HGFilterV2
 #include "api_params.hip"
 
 extern "C" int kpn_abi_version(void) { return KPN_ABI_VERSION; }

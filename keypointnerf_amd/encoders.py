@@ -434,6 +434,7 @@ class NativeTraining:
     geo_calls = 0
     tex_calls = 0
     fused_tex_calls = 0
+    fused_geo_calls = 0
 
 
 def _pow2_channels(C):
@@ -740,7 +741,66 @@ def _geo_ineligible(m, name):
 _GEO_PARTS = ("strided", "convs", "norms", "blocks", "hourglass")
 
 
-def install_native_geo(module, fused_blocks=False, arith="f32"):
+def _fused_geo_plan(m):
+    """([(module, parameter name)] in the tensor order of torch.ops.kpnerf.hg_filter, depth, eps) if kpn_hg_filter_* serves this HGFilterV2
+    (one that _geo_ineligible has passed), else the reason it stays on the per-layer path"""
+    if m.n_stack != 1:
+        return f"n_stack={m.n_stack} (the single-operator network has one stack)"
+    if m.hd:
+        return "hd=True (the single-operator network pools in front of conv3)"
+    why = _hourglass_ineligible(m.m0)
+    if why is not None:
+        return f"m0: {why}"
+    hg = m.m0
+    blocks = [("conv2", m.conv2), ("conv3", m.conv3), ("conv4", m.conv4)]
+    blocks += [(f"m0.b{j}_{k}", hg._modules[f"b{j}_{k}"]) for k in range(hg.depth, 0, -1) for j in (1, 2)]
+    blocks += [("m0.b2_plus_1", hg._modules["b2_plus_1"])] + [(f"m0.b3_{k}", hg._modules[f"b3_{k}"]) for k in range(1, hg.depth + 1)]
+    blocks.append(("top_m_0", m.top_m_0))
+    refs = [(m.conv1, "weight"), (m.conv1, "bias"), (m.bn1, "weight"), (m.bn1, "bias")]
+    norms, widths = [("bn1", m.bn1), ("unpack1.norm", m.unpack1.norm), ("bn_end0", m.bn_end0)], []
+    for name, b in blocks:
+        why = _fused_block_ineligible(b, name)
+        if why is not None:
+            return f"{name}: {why}"
+        cin, cout = b.bn1.num_channels, 2 * b.conv1.out_channels
+        widths.append((cin, cout))
+        legs = [(b.bn1, b.conv1), (b.bn2, b.conv2), (b.bn3, b.conv3)] + ([(b.bn4, b.downsample[2])] if cin != cout else [])
+        for i, (bn, conv) in enumerate(legs):
+            norms.append((f"{name}.bn{i + 1}", bn))
+            refs += [(bn, "weight"), (bn, "bias"), (conv, "weight")]
+    un, tail = m.unpack1, [m.conv_out, m.conv_last0, m.l0]
+    refs += [(un.conv, "weight"), (un.norm, "weight"), (un.norm, "bias"), (m.conv_out, "weight"), (m.conv_out, "bias"),
+             (m.conv_last0, "weight"), (m.conv_last0, "bias"), (m.bn_end0, "weight"), (m.bn_end0, "bias"), (m.l0, "weight"), (m.l0, "bias")]
+    if un.conv.bias is not None:
+        return "unpack1.conv has a bias"
+    if m.conv1.bias is None or any(c.bias is None for c in tail):
+        return "a convolution without bias among conv1, conv_out, conv_last0, l0"
+    for n, norm in norms:
+        if norm.weight is None or norm.num_groups != min(32, norm.num_channels):
+            return f"{n}: GroupNorm({norm.num_groups}, {norm.num_channels}) (min(32, C) groups with parameters)"
+    eps = {float(norm.eps) for _, norm in norms}
+    if len(eps) != 1:
+        return f"the norms have different eps {sorted(eps)}"
+    k = [(c, _pair(c.kernel_size), _pair(c.stride), _pair(c.padding)) for c in [m.conv1] + tail]
+    if [t[1:] for t in k] != [((7, 7), (2, 2), (3, 3)), ((5, 5), (1, 1), (2, 2)), ((1, 1), (1, 1), (0, 0)), ((1, 1), (1, 1), (0, 0))] \
+            or any(c.groups != 1 or _pair(c.dilation) != (1, 1) or c.padding_mode != "zeros" for c, *_ in k):
+        return "conv1, conv_out, conv_last0 or l0 is not the reference's layer (7x7 stride 2, 5x5 pad 2, 1x1, 1x1)"
+    if _strided_ineligible(un.conv) is not None:
+        return f"unpack1.conv: {_strided_ineligible(un.conv)}"
+    c4 = widths[2][1]
+    chain = [m.conv1.out_channels, widths[0][1], widths[1][1], c4]
+    if [w[0] for w in widths[:3]] != chain[:3] or any(w != (c4, c4) for w in widths[3:]) or hg.features != c4 \
+            or un.conv.in_channels != chain[1] or m.conv_out.in_channels != un.conv.out_channels \
+            or (m.conv_last0.in_channels, m.conv_last0.out_channels, m.l0.in_channels) != (c4, c4, c4):
+        return "the widths of the layers do not chain as the reference's do"
+    cfg = (m.conv1.in_channels, chain[0], chain[1], chain[2], c4, hg.depth, un.conv.out_channels, m.conv_out.out_channels, m.l0.out_channels)
+    why = ops.hg_filter_refusal(cfg)
+    if why is not None:
+        return f"the single-operator network does not serve it: {why}"
+    return refs, hg.depth, eps.pop()
+
+
+def install_native_geo(module, fused_blocks=False, arith="f32", fused=False):
     """Opt-in: trains every HGFilterV2 under ``module`` (``module`` itself included) on the project's kernels.  An HGFilterV2 whose
     structure is the reference's (src/utils.py:322-414: its children for any ``n_stack`` >= 1, ``norm="group"``, ``hd`` either way) gets
     ``install_native_strided``, ``install_native_convs``, ``install_native_norms``, ``install_native_blocks`` and
@@ -757,11 +817,34 @@ def install_native_geo(module, fused_blocks=False, arith="f32"):
     ``arith="bf16x3"``: the stride-1 convolutions and the ConvBlocks (``install_native_convs`` / ``install_native_blocks`` with the same
     keyword) run on three bf16 pieces per operand; the stem and the transposed convolution of ``unpack1`` have no such kernel and stay on
     their fp32 ones.  The report then has one more entry, ``"arith": {"bf16x3": [names], "f32": [names]}``: the served convolution
-    layers and blocks on each arithmetic.  Any other value raises ValueError; the default leaves the report as it was."""
+    layers and blocks on each arithmetic.  Any other value raises ValueError; the default leaves the report as it was.
+
+    ``fused=True``: the rebound forward of every served HGFilterV2 that kpn_hg_filter_* serves - ``n_stack == 1``, ``hd`` false, one
+    ``eps`` over all norms, ``min(32, C)`` groups on every norm, widths the descriptor accepts - is one torch.ops.kpnerf.hg_filter call
+    instead (kpn_hg_filter_forward / _backward): one autograd node per network and no aten operator inside it - the norms and ReLUs of
+    ``unpack1`` and ``bn_end0`` run in the loads of the next convolution, the sums where a tensor feeds two consumers run in the
+    backward's kernels - with x and one ``state`` buffer kept for the backward.  Its outputs and parameter gradients have the bits of the
+    ``fused_blocks=True`` path.  Such a network gets none of the five installers on its subtree.  Input that is not a CUDA fp32
+    (N, C, H, W) tensor with H and W divisible by 2^(depth + 2), or that requires a gradient (the stem has no native input gradient),
+    goes to the original forward.  A network the operator does not serve stays on the per-layer path exactly as without the keyword;
+    the report gains ``"fused"``: (the names on the operator, {name: reason} of those left on the per-layer path).
+    ``NativeTraining.fused_geo_calls`` counts the operator's calls (``geo_calls`` the per-layer ones).  ``fused=True`` with
+    ``arith="bf16x3"`` raises ValueError: the operator has no such arithmetic."""
     _arith_code(arith)
+    if fused and arith != "f32":
+        raise ValueError('install_native_geo: fused=True runs the fp32 kernels only; arith="bf16x3" needs the per-layer path (fused=False)')
 
     def make_forward(_prev):
         def forward(self, x):
+            plan = self.__dict__.get("_kpnerf_geo_fused")
+            if plan is not None:
+                refs, depth, eps = plan
+                f = 4 << depth
+                if (not _native_input(x, *self.parameters()) or x.shape[2] % f or x.shape[3] % f
+                        or (x.requires_grad and torch.is_grad_enabled())):
+                    return _prev(x)
+                NativeTraining.fused_geo_calls += 1
+                return torch.ops.kpnerf.hg_filter(x, [getattr(a, n) for a, n in refs], depth, eps)
             if not _native_input(x, *self.parameters()) or (((x.shape[2] - 1) // 2 + 1) % 2 or ((x.shape[3] - 1) // 2 + 1) % 2):
                 return _prev(x)
             NativeTraining.geo_calls += 1
@@ -788,7 +871,16 @@ def install_native_geo(module, fused_blocks=False, arith="f32"):
     served, left = _rebind_forward(module, "_kpnerf_geo_saved", lambda m: type(m).__name__ == "HGFilterV2", _geo_ineligible, make_forward)
     report = {k: ([], {}) for k in _GEO_PARTS}
     subs = dict(module.named_modules())
+    if fused:
+        report["fused"] = ([], {})
     for name in served:
+        if fused:
+            plan = _fused_geo_plan(subs[name])
+            if not isinstance(plan, str):
+                subs[name]._kpnerf_geo_fused = plan
+                report["fused"][0].append(name)
+                continue
+            report["fused"][1][name] = plan
         for part, fn in zip(_GEO_PARTS, (install_native_strided, lambda m: install_native_convs(m, arith=arith), install_native_norms,
                                          lambda m: install_native_blocks(m, fused=fused_blocks, arith=arith), install_native_hourglass)):
             s_, l_ = fn(subs[name])
@@ -813,6 +905,7 @@ def uninstall_native_geo(module):
     subtree: no attribute it added is left."""
     for m in module.modules():
         if "_kpnerf_geo_saved" in m.__dict__:
+            m.__dict__.pop("_kpnerf_geo_fused", None)
             for undo in (uninstall_native_strided, uninstall_native_convs, uninstall_native_norms, uninstall_native_blocks,
                          uninstall_native_hourglass):
                 undo(m)

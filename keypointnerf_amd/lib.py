@@ -131,6 +131,21 @@ class ResEncoderDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("N", "H", "W", "in_ch", "ngf", "n_down", "n_blocks", "n_up", "out_ch")] + [("eps", c_f)]
 
 
+class HgFilterDesc(ctypes.Structure):
+    """struct kpn_hg_filter_desc"""
+    _fields_ = [(n, c_i32) for n in ("N", "H", "W", "in_ch", "c_stem", "c2", "c3", "c4", "depth", "c_hd", "out_ch_hd", "out_ch")] + [("eps", c_f)]
+
+
+class HgFilterParams(ctypes.Structure):
+    """struct kpn_hg_filter_params"""
+    _fields_ = [("tensors", ctypes.POINTER(c_p)), ("packed", c_p)]
+
+
+class HgFilterGrads(ctypes.Structure):
+    """struct kpn_hg_filter_grads"""
+    _fields_ = [("tensors", ctypes.POINTER(c_p))]
+
+
 class ResampleDesc(ctypes.Structure):
     """struct kpn_resample2_desc"""
     _fields_ = [(n, c_i32) for n in ("N", "h", "w", "C")]
@@ -280,6 +295,14 @@ _SIGNATURES = {
     "kpn_res_encoder_forward": (ctypes.c_int, [ctypes.POINTER(ResEncoderDesc), c_p, c_p, ctypes.POINTER(c_p), c_p, c_p, c_p, c_sz, c_p]),
     "kpn_res_encoder_backward": (ctypes.c_int, [ctypes.POINTER(ResEncoderDesc), c_p, c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
                                                 c_p, c_sz, c_p]),
+    "kpn_hg_filter_tensors": (c_i32, [ctypes.POINTER(HgFilterDesc)]),
+    "kpn_hg_filter_workspace_bytes": (c_sz, [ctypes.POINTER(HgFilterDesc)]),
+    "kpn_hg_filter_state_floats": (c_sz, [ctypes.POINTER(HgFilterDesc)]),
+    "kpn_hg_filter_packed_floats": (c_sz, [ctypes.POINTER(HgFilterDesc)]),
+    "kpn_hg_filter_pack_device": (ctypes.c_int, [ctypes.POINTER(HgFilterDesc), ctypes.POINTER(c_p), c_p, c_p]),
+    "kpn_hg_filter_forward": (ctypes.c_int, [ctypes.POINTER(HgFilterDesc), c_p, ctypes.POINTER(HgFilterParams), c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "kpn_hg_filter_backward": (ctypes.c_int, [ctypes.POINTER(HgFilterDesc), c_p, c_p, c_p, ctypes.POINTER(HgFilterParams), c_p,
+                                              ctypes.POINTER(HgFilterGrads), c_p, c_sz, c_p]),
     "kpn_avg_pool2_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_avg_pool2_backward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p]),
     "kpn_upsample2x_add_forward": (ctypes.c_int, [ctypes.POINTER(ResampleDesc), c_p, c_p, c_p, c_p]),

@@ -1532,6 +1532,166 @@ def res_encoder_backward(x, dy, packed, state, cfg, eps, want=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# A whole HGFilterV2 (n_stack = 1, hd = False, norm = "group") and its parameter gradients as one call each (kpn_hg_filter_*; reference
+# src/utils.py:322-414).  x is the contiguous NCHW image, read as it is; out and x_hd are channels_last tensors of logical shape
+# (N, out_ch, H / 4, W / 4) and (N, out_ch_hd, H, W).  ``cfg`` is (in_ch, c_stem, c2, c3, c4, depth, c_hd, out_ch_hd, out_ch).  ``tensors``
+# in the order of include/kpnerf.h: conv1 w, b; bn1 w, b; per ConvBlock in dataflow order (conv2, conv3, conv4, the HourGlass's b1_d, b2_d,
+# b1_{d-1}, ..., b2_plus_1, b3_1, ..., b3_d - its module order - and top_m_0) the 9 or 12 tensors of conv_block; unpack1.conv w;
+# unpack1.norm w, b; conv_out w, b; conv_last0 w, b; bn_end0 w, b; l0 w, b.
+_HG_FILTER_WORKSPACE = ("kpn_hg_filter_workspace_bytes", "kpn_hg_filter_forward", "hg_filter: unsupported network")
+_HG_FILTER_FIELDS = ("in_ch", "c_stem", "c2", "c3", "c4", "depth", "c_hd", "out_ch_hd", "out_ch")
+
+
+def _hg_filter_desc(N, H, W, cfg, eps):
+    d = kl.HgFilterDesc()
+    d.N, d.H, d.W, d.eps = int(N), int(H), int(W), float(eps)
+    for n, v in zip(_HG_FILTER_FIELDS, cfg):
+        setattr(d, n, int(v))
+    return d
+
+
+def hg_filter_refusal(cfg, N=1, H=None, W=None):
+    """None if kpn_hg_filter_* serves the network (and, when given, the input size), else the library's reason"""
+    L = kl.get_library()
+    f = 4 << max(1, min(int(cfg[5]), 8))
+    d = _hg_filter_desc(N, f if H is None else H, f if W is None else W, cfg, 1e-5)
+    if L.kpn_hg_filter_workspace_bytes(ctypes.byref(d)) > 0:
+        return None
+    L.kpn_hg_filter_forward(ctypes.byref(d), None, None, None, None, None, None, 0, None)
+    return L.kpn_last_error().decode()
+
+
+def hg_filter_supported(cfg, N=1, H=None, W=None):
+    """whether kpn_hg_filter_* serves an HGFilterV2 of these widths and this depth (and, when given, of this input size)"""
+    return hg_filter_refusal(cfg, N, H, W) is None
+
+
+def hg_filter_block_widths(cfg):
+    """[(cin, cout)] of the ConvBlocks in tensor order"""
+    _, c_stem, c2, c3, c4, depth = (int(v) for v in cfg[:6])
+    return [(c_stem, c2), (c2, c3), (c3, c4)] + [(c4, c4)] * (3 * depth + 2)
+
+
+def hg_filter_shapes(cfg):
+    """the shapes of ``tensors`` in order"""
+    in_ch, c_stem, c2, c3, c4, depth, c_hd, out_ch_hd, out_ch = (int(v) for v in cfg)
+    out = [(c_stem, in_ch, 7, 7), (c_stem,), (c_stem,), (c_stem,)]
+    for cin, cout in hg_filter_block_widths(cfg):
+        legs, win, wout = _block_widths(cin, cout)
+        for i in range(legs):
+            k = 3 if i < 3 else 1
+            out += [(win[i],), (win[i],), (wout[i], win[i], k, k)]
+    out += [(c2, c_hd, 3, 3), (c_hd,), (c_hd,), (out_ch_hd, c_hd, 5, 5), (out_ch_hd,), (c4, c4, 1, 1), (c4,), (c4,), (c4,), (out_ch, c4, 1, 1), (out_ch,)]
+    return out
+
+
+def hg_filter_state_floats(N, H, W, cfg):
+    """kpn_hg_filter_state_floats, restated from the layout include/kpnerf.h documents (the fake kernels and the tests use it)"""
+    _, c_stem, c2, c3, c4, depth, c_hd, _, _ = (int(v) for v in cfg)
+    stats = lambda C: 2 * N * C + 2 * N * min(32, C)  # noqa: E731
+
+    def block(cin, cout, P):
+        legs, win, _ = _block_widths(cin, cout)
+        return P * (3 * cout // 4) + sum(stats(win[i]) for i in range(legs))
+
+    P1, P2 = N * (H // 2) * (W // 2), N * (H // 4) * (W // 4)
+    total = 2 * P1 * c_stem + stats(c_stem) + block(c_stem, c2, P1) + P1 * c2 + N * H * W * c_hd + stats(c_hd)
+    total += P2 * c2 + block(c2, c3, P2) + P2 * c3 + block(c3, c4, P2) + P2 * c4
+    for k in range(depth):
+        P, Pl = P2 >> (2 * k), P2 >> (2 * k + 2)
+        total += block(c4, c4, P) + P * c4 + Pl * c4 + block(c4, c4, Pl) + Pl * c4 + block(c4, c4, Pl)      # b1, hg, low, b2, low1, b3
+    Pl = P2 >> (2 * depth)
+    total += block(c4, c4, Pl) + Pl * c4                                                                     # b2_plus and its output
+    return total + block(c4, c4, P2) + 2 * P2 * c4 + stats(c4)
+
+
+def _hg_filter_tensors(tensors, cfg, device):
+    shapes = hg_filter_shapes(cfg)
+    if len(tensors) != len(shapes):
+        raise ValueError(f"hg_filter: {len(shapes)} tensors, got {len(tensors)}")
+    out = []
+    for i, (t, shape) in enumerate(zip(tensors, shapes)):
+        t = _dev(t.detach(), f"tensors[{i}]")
+        if tuple(t.shape) != shape or t.device != device:
+            raise ValueError(f"hg_filter: tensors[{i}] must be {shape} on {device}, got {tuple(t.shape)} on {t.device}")
+        out.append(t)
+    return out
+
+
+def hg_filter_pack(tensors, cfg):
+    """The packed copies of every convolution weight in one buffer (kpn_hg_filter_pack_device): per weight, in tensor order, what its
+    layer's own packer gives (conv2d_s2_pack for conv1 and unpack1.conv, conv2d_pack for the others)."""
+    L = kl.get_library()
+    ts = _hg_filter_tensors(tensors, cfg, tensors[0].device)
+    f = 4 << int(cfg[5])
+    d = _hg_filter_desc(1, f, f, cfg, 1e-5)
+    n = _desc_size(L, d, "kpn_hg_filter_packed_floats", "kpn_hg_filter_pack_device", "hg_filter: unsupported network")
+    packed = torch.empty(n, dtype=_f32, device=ts[0].device)
+    L.check(L.kpn_hg_filter_pack_device(ctypes.byref(d), _pointer_array(ts), _p(packed), _stream()))
+    return packed
+
+
+def _hg_filter_check(L, d, packed, state, device):
+    if packed.numel() != L.kpn_hg_filter_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != device:
+        raise ValueError("packed does not belong to this network (hg_filter_pack)")
+    if state is not None and (state.numel() != L.kpn_hg_filter_state_floats(ctypes.byref(d)) or state.dtype != _f32 or state.device != device):
+        raise ValueError("state does not belong to this network (hg_filter_forward)")
+
+
+def hg_filter_forward(x, tensors, packed, cfg, eps):
+    """HGFilterV2(x) for packed = hg_filter_pack(tensors, cfg) (kpn_hg_filter_forward).  x: contiguous NCHW (N, in_ch, H, W).  Returns
+    (out (N, out_ch, H / 4, W / 4) channels_last, x_hd (N, out_ch_hd, H, W) channels_last, state): state holds what hg_filter_backward
+    reads - the layout of include/kpnerf.h."""
+    L = kl.get_library()
+    x = _res_encoder_x(x)
+    N, in_ch, H, W = x.shape
+    if in_ch != int(cfg[0]):
+        raise ValueError(f"x must have {int(cfg[0])} channels, got {in_ch}")
+    d = _hg_filter_desc(N, H, W, cfg, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_HG_FILTER_WORKSPACE)
+    ts = _hg_filter_tensors(tensors, cfg, x.device)
+    _hg_filter_check(L, d, packed, None, x.device)
+    out = torch.empty(N, H // 4, W // 4, int(cfg[8]), dtype=_f32, device=x.device)
+    x_hd = torch.empty(N, H, W, int(cfg[7]), dtype=_f32, device=x.device)
+    state = torch.empty(L.kpn_hg_filter_state_floats(ctypes.byref(d)), dtype=_f32, device=x.device)
+    pr = kl.HgFilterParams()
+    ptrs = _pointer_array(ts)
+    pr.tensors, pr.packed = ptrs, packed.data_ptr()
+    L.check(L.kpn_hg_filter_forward(ctypes.byref(d), _p(x), ctypes.byref(pr), _p(out), _p(x_hd), _p(state), _p(ws), nb, _stream()))
+    return out.permute(0, 3, 1, 2), x_hd.permute(0, 3, 1, 2), state
+
+
+def hg_filter_backward(x, d_out, d_x_hd, tensors, packed, state, cfg, eps, want=None):
+    """[gradient or None] per tensor of hg_filter_forward for the output gradients d_out (N, out_ch, H / 4, W / 4) and d_x_hd
+    (N, out_ch_hd, H, W), channels_last; either may be None (that branch contributes nothing), not both (kpn_hg_filter_backward).
+    ``want`` has one flag per tensor (default: all); what is not wanted is None, and only the legs a wanted gradient needs are launched."""
+    L = kl.get_library()
+    x = _res_encoder_x(x)
+    N, _, H, W = x.shape
+    shapes = hg_filter_shapes(cfg)
+    want = [True] * len(shapes) if want is None else [bool(w) for w in want]
+    if len(want) != len(shapes):
+        raise ValueError(f"hg_filter: {len(shapes)} tensors, got {len(want)} entries of want")
+    if d_out is None and d_x_hd is None:
+        raise ValueError("hg_filter: d_out and d_x_hd are both None")
+    for g, name, shape in ((d_out, "d_out", (N, int(cfg[8]), H // 4, W // 4)), (d_x_hd, "d_x_hd", (N, int(cfg[7]), H, W))):
+        if g is not None and tuple(_channels_last(g, name).shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
+    d = _hg_filter_desc(N, H, W, cfg, eps)
+    ws, nb = _desc_workspace(L, d, x.device, *_HG_FILTER_WORKSPACE)
+    ts = _hg_filter_tensors(tensors, cfg, x.device)
+    _hg_filter_check(L, d, packed, state, x.device)
+    out = [torch.empty(shape, dtype=_f32, device=x.device) if w else None for shape, w in zip(shapes, want)]
+    if any(want):
+        pr, gr = kl.HgFilterParams(), kl.HgFilterGrads()
+        ptrs, gptrs = _pointer_array(ts), _pointer_array(out)
+        pr.tensors, pr.packed, gr.tensors = ptrs, packed.data_ptr(), gptrs
+        L.check(L.kpn_hg_filter_backward(ctypes.byref(d), _p(x), _p(d_out), _p(d_x_hd), ctypes.byref(pr), _p(state.contiguous()), ctypes.byref(gr),
+                                         _p(ws), nb, _stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # The two resampling steps of an HourGlass and their gradients (kpn_avg_pool2_* / kpn_upsample2x_add_*; avg_pool2d(x, 2, stride=2)
 # and skip + interpolate(low, scale_factor=2, mode="bicubic", align_corners=True) with their autograd, reference
 # src/utils.py:287-306).  Activations are channels_last tensors of logical shape (N, C, H, W).

@@ -54,6 +54,11 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
                                  node: tensors = [weight, bias] per convolution in module order; x is the NCHW image; channels-last
                                  result, DIFFERENTIABLE w.r.t. every tensor, not x (kpn_res_encoder_forward / _backward); keeps x, the
                                  convolution outputs and the ResBlk sums for the backward, never a normalised or padded tensor
+    torch.ops.kpnerf.hg_filter(x, tensors, depth, eps) -> [out, x_hd]   a whole HGFilterV2(n_stack=1, hd=False, norm="group") as ONE
+                                 autograd node: tensors in the order of include/kpnerf.h; x is the NCHW image; channels-last results,
+                                 DIFFERENTIABLE w.r.t. every tensor, not x (kpn_hg_filter_forward / _backward); keeps x, the block
+                                 inputs and states, the pooled tensors and two convolution outputs, never a normalised tensor but
+                                 relu(bn1(conv1 x)); the fan-in sums of the backward run in its kernels
     torch.ops.kpnerf.avg_pool2(x) -> y   avg_pool2d(x, 2, stride=2) (C a multiple of 4, even H and W), channels-last result,
                                  DIFFERENTIABLE w.r.t. x (kpn_avg_pool2_forward / _backward)
     torch.ops.kpnerf.upsample2x_add(low, skip?) -> y   skip + bicubic x2 of low (align_corners=True; C a multiple of 4), channels-last
@@ -1222,6 +1227,123 @@ def _res_encoder(x, tensors, n_down, n_blocks, n_up, eps):
 
 _fragment.define("res_encoder(Tensor x, Tensor[] tensors, int n_down, int n_blocks, int n_up, float eps) -> Tensor")
 _fragment.impl("res_encoder", _res_encoder, "CompositeImplicitAutograd")
+
+
+# ---- torch.ops.kpnerf.hg_filter: a whole HGFilterV2, DIFFERENTIABLE w.r.t. every parameter, one autograd node ----
+# tensors, in the order of include/kpnerf.h: conv1 w, b; bn1 w, b; per ConvBlock in dataflow order (conv2, conv3, conv4, the HourGlass in its
+# module order b1_d, b2_d, ..., b2_plus_1, b3_1, ..., b3_d, top_m_0) the 9 or 12 tensors of conv_block; unpack1.conv w; unpack1.norm w, b;
+# conv_out w, b; conv_last0 w, b; bn_end0 w, b; l0 w, b.  The packed copies of all convolution weights are one buffer, packed once per
+# parameter version in the cache of kpnerf::res_encoder (the key is _tensor_key of every weight).  The backward reads x, `state` and the
+# parameters; it never reads an output.  There is no input gradient: an x that requires one raises.
+def _hg_cfg(x, tensors, depth):
+    """(in_ch, c_stem, c2, c3, c4, depth, c_hd, out_ch_hd, out_ch) from the tensors' shapes; ops.hg_filter_shapes checks the rest"""
+    nblocks = 3 * depth + 5
+    if depth < 1 or len(tensors) < 4 + 9 * nblocks + 11:
+        raise ValueError(f"hg_filter takes the tensors of an HGFilterV2 with an HourGlass of depth {depth}, got {len(tensors)} tensors")
+    widths, t = [tensors[0].shape[0]], 4
+    for _ in range(3):                                  # conv2, conv3, conv4: 9 tensors, 12 where the width changes
+        cin, cout = tensors[t].shape[0], 2 * tensors[t + 2].shape[0]
+        widths.append(cout)
+        t += 12 if cin != cout else 9
+    cfg = (x.shape[1], widths[0], widths[1], widths[2], widths[3], depth, tensors[-10].shape[0], tensors[-8].shape[0], tensors[-2].shape[0])
+    shapes = ops.hg_filter_shapes(cfg)
+    if len(shapes) != len(tensors) or any(tuple(a.shape) != b for a, b in zip(tensors, shapes)):
+        raise ValueError(f"hg_filter: the tensors do not have the shapes of an HGFilterV2 with the widths {cfg[1:5]} and depth {depth}")
+    return cfg
+
+
+def _hg_weights(tensors):
+    return [t for t in tensors if t.dim() == 4]
+
+
+def _hg_packed(tensors, cfg):
+    weights = _hg_weights(tensors)
+    if any(w.is_inference() for w in weights):
+        return ops.hg_filter_pack(tensors, cfg)
+    key = tuple(_tensor_key(w) for w in weights) + (("hg_filter",) + tuple(cfg),)
+    C = _ResPackCache
+    with C.lock:
+        e = C.entries.get(key[0][0])
+        if e is not None and e[0] == key:
+            C.entries.move_to_end(key[0][0])
+            C.hits += 1
+            return e[2]
+    packed = ops.hg_filter_pack(tensors, cfg)
+    with C.lock:
+        C.misses += 1
+        C.entries[key[0][0]] = (key, weights, packed)
+        C.entries.move_to_end(key[0][0])
+        while len(C.entries) > C.limit:
+            C.entries.popitem(last=False)
+    return packed
+
+
+@_lib.custom_op("kpnerf::hg_filter_cl", mutates_args=(), device_types="cuda")
+def hg_filter_cl(x: torch.Tensor, tensors: List[torch.Tensor], depth: int, eps: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(out, x_hd, state) of an HGFilterV2 for a contiguous NCHW x (kpn_hg_filter_forward): what torch.ops.kpnerf.hg_filter runs after its
+    memory-format conversion.  out is (N, out_ch, H / 4, W / 4) and x_hd (N, out_ch_hd, H, W), channels_last; state is the side buffer of
+    the backward."""
+    cfg = _hg_cfg(x, tensors, depth)
+    return ops.hg_filter_forward(x, tensors, _hg_packed(tensors, cfg), cfg, eps)
+
+
+@hg_filter_cl.register_fake
+def _(x, tensors, depth, eps):
+    cfg = _hg_cfg(x, tensors, depth)
+    N, _, H, W = x.shape
+    return (x.new_empty(N, H // 4, W // 4, cfg[8]).permute(0, 3, 1, 2), x.new_empty(N, H, W, cfg[7]).permute(0, 3, 1, 2),
+            x.new_empty(ops.hg_filter_state_floats(N, H, W, cfg)))
+
+
+@_lib.custom_op("kpnerf::hg_filter_backward", mutates_args=(), device_types="cuda")
+def hg_filter_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: torch.Tensor, d_out: Optional[torch.Tensor],
+                       d_x_hd: Optional[torch.Tensor], depth: int, eps: float, mask: List[bool]) -> List[torch.Tensor]:
+    """one gradient per tensor of kpnerf::hg_filter_cl for the output gradients d_out and d_x_hd, either of which may be None
+    (kpn_hg_filter_backward); mask has one flag per tensor: what is not wanted is not computed and its result is an empty tensor."""
+    cfg = _hg_cfg(x, tensors, depth)
+    cl = torch.channels_last
+    d_out = None if d_out is None else d_out.contiguous(memory_format=cl)
+    d_x_hd = None if d_x_hd is None else d_x_hd.contiguous(memory_format=cl)
+    grads = ops.hg_filter_backward(x, d_out, d_x_hd, tensors, _hg_packed(tensors, cfg), state, cfg, eps, want=mask)
+    return list(_empty_for_none(x, *grads))
+
+
+@hg_filter_backward.register_fake
+def _(x, tensors, state, d_out, d_x_hd, depth, eps, mask):
+    return [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask)]
+
+
+def _hg_filter_setup(ctx, inputs, output):
+    x, tensors, depth, eps = inputs
+    if ctx.needs_input_grad[0]:
+        raise RuntimeError("kpnerf::hg_filter: the 7x7 stem has no input gradient (x.requires_grad is set)")
+    ctx.save_for_backward(x, output[2], *tensors)                                # never an output, never a normalised tensor
+    ctx.cfg = (depth, eps)
+    ctx.set_materialize_grads(False)
+
+
+def _hg_filter_bwd(ctx, d_out, d_x_hd, _d_state):
+    x, state, *tensors = ctx.saved_tensors
+    none = (None, [None] * len(tensors), None, None)
+    mask = [bool(b) for b in ctx.needs_input_grad[1]]
+    if (d_out is None and d_x_hd is None) or not any(mask):
+        return none
+    out = torch.ops.kpnerf.hg_filter_backward(x, list(tensors), state, d_out, d_x_hd, *ctx.cfg, mask)
+    return None, list(_none_unless(mask, *out)), None, None
+
+
+hg_filter_cl.register_autograd(_hg_filter_bwd, setup_context=_hg_filter_setup)
+
+
+# torch.ops.kpnerf.hg_filter(x, tensors, depth, eps) -> [out, x_hd]: x in any memory format, converted once to the contiguous NCHW layout
+# the stem reads as it is; the results are channels_last.
+def _hg_filter(x, tensors, depth, eps):
+    out, x_hd, _ = torch.ops.kpnerf.hg_filter_cl(x.contiguous(), tensors, depth, eps)
+    return [out, x_hd]
+
+
+_fragment.define("hg_filter(Tensor x, Tensor[] tensors, int depth, float eps) -> Tensor[]")
+_fragment.impl("hg_filter", _hg_filter, "CompositeImplicitAutograd")
 
 
 # ---- torch.ops.kpnerf.avg_pool2 / upsample2x_add: the two resampling steps of an HourGlass, DIFFERENTIABLE ----
