@@ -63,8 +63,11 @@ extern "C" {
 /* still 10: a whole HGFilterV2 as one differentiable operator (kpn_hg_filter_desc, kpn_hg_filter_params, kpn_hg_filter_grads,
  * kpn_hg_filter_tensors, kpn_hg_filter_workspace_bytes, kpn_hg_filter_state_floats, kpn_hg_filter_packed_floats,
  * kpn_hg_filter_pack_device, kpn_hg_filter_forward, kpn_hg_filter_backward) is additive within 10 in the same way */
+/* still 10: keypoint sets - models with 1..24 keypoints and 0..3 encoding octaves served as the 24 / 3 model (kpn_field_shape,
+ * kpn_plain_weight_floats_shape, kpn_widen_plain, kpn_narrow_plain_grad, kpn_scene_prepare_kpt, kpn_fold_params_shape,
+ * kpn_fold_params_backward_shape) are additive within 10 in the same way */
 #define KPN_ABI_VERSION 10
-#define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt */
+#define KPN_N_KPT 24      /* configs/zju.json:44 sp_args.n_kpt: the CAPACITY of the field kernels (models with fewer keypoints: "Keypoint sets" below) */
 #define KPN_MAX_VIEWS 16
 
 enum { KPN_OK = 0, KPN_EINVAL = -1, KPN_ELAUNCH = -2, KPN_EWORKSPACE = -3 };
@@ -104,7 +107,7 @@ typedef struct kpn_scene_desc {
     float sigma;                     /* sp_args.sigma (0.1) */
     const float* KRT;                /* (V,4,4) */
     const float* extrin;             /* (V,4,4) */
-    const float* kpt3d;              /* (24,3) */
+    const float* kpt3d;              /* (24,3); (n_kpt,3) for kpn_scene_prepare_kpt */
     const float* img;                /* (V,3,H,W) */
     const uint8_t* fg_mask;          /* (V,H,W) bool bytes; ignored if disable_fg_mask */
     const float* geo0;
@@ -573,7 +576,8 @@ typedef struct kpn_param_table {
     float* ani_al;
 } kpn_param_table;
 /* floats of the side buffer kpn_fold_params leaves for its backward: per weight-normed row (504) the row norm in fp64 and the
- * fp32 scale g / norm; 8-byte aligned */
+ * fp32 scale g / norm; 8-byte aligned.  (kpn_fold_params_shape leaves the same buffer: the norm of a narrow row is the fp64 sum over
+ * the 232 canonical columns in the canonical lane order, i.e. the value kpn_fold_params gives for the widened row.) */
 size_t kpn_fold_norm_floats(void);
 /* kpn_fold_params: replaces torch._weight_norm(v, g, 0) per layer (what weight_norm's hook evaluates, src/utils.py:542-543), the
  * reshapes and the concatenation of weights.plain_tensor_from_module.  Per weight-normed row n = sqrt(sum v^2) and g / n in
@@ -610,6 +614,44 @@ typedef struct kpn_adam_args {
     double lr, beta1, beta2, eps, weight_decay;
 } kpn_adam_args;
 int kpn_adam_step(const kpn_adam_args* args, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Keypoint sets: models with n_kpt = 1..KPN_N_KPT keypoints and sp_level = 0..KPN_SP_LEVEL octaves of the rel_z_decay encoding.
+ * The reference sizes the first linear of mlp_geo from the encoder, D = SpatialEncoder.get_dim() = (1 + 2 sp_level) n_kpt
+ * (src/spatial.py:49-53, src/model.py:569-572): its weight is (128, D + 64), the encoding value of block t (0 = dz w, 1 + 2l =
+ * sin, 2 + 2l = cos of octave l) and keypoint k sits in column t n_kpt + k (src/spatial.py:110-118), the 64 geometry channels
+ * behind them.  The field kernels are built for the 24 / 3 model, whose column is 24 t + k (168 + j for geometry channel j).  A
+ * narrower model is served as that model: NARROW column t n_kpt + k <-> CANONICAL column 24 t + k, D + j <-> 168 + j; the
+ * canonical columns without a narrow one (PADDED: t > 2 sp_level or k >= n_kpt) carry weight 0, and the keypoint table repeats
+ * keypoint 0 in rows n_kpt..23, so a padded encoding value is finite, one a real keypoint produces too, and its product with the
+ * zero weight is an exact 0 in every accumulator.  Padded keypoints cost what real ones cost.
+ * The NARROW PLAIN vector is `plain` of kpn_pack_weights with layers1.0's W as (128, D + 64); nothing else differs.
+ * KPN_N_KPT is the capacity.  Every entry below returns KPN_EINVAL, with a message and before any launch, for n_kpt outside
+ * 1..KPN_N_KPT or sp_level outside 0..KPN_SP_LEVEL. */
+#define KPN_SP_LEVEL 3    /* configs/zju.json:41 sp_args.sp_level: the capacity */
+typedef struct kpn_field_shape { int32_t n_kpt, sp_level; } kpn_field_shape;
+/* floats of the narrow plain vector; 0 if the shape is out of range; kpn_plain_weight_floats() for {24, 3} */
+size_t kpn_plain_weight_floats_shape(const kpn_field_shape* shape);
+/* narrow plain -> plain (kpn_plain_weight_floats()): one launch that writes every element of plain_dev, +0 in the padded columns
+ * of layers1.0's W; everything else is a copy. */
+int kpn_widen_plain(const kpn_field_shape* shape, const float* narrow_dev, float* plain_dev, void* stream);
+/* Its adjoint, a gather: the gradient w.r.t. plain -> the gradient w.r.t. the narrow plain vector, one launch.  The padded
+ * columns of d_plain_dev are not read.  accumulate = 0 overwrites d_narrow_dev, != 0 adds to it (as kpn_fold_params_backward). */
+int kpn_narrow_plain_grad(const kpn_field_shape* shape, const float* d_plain_dev, float* d_narrow_dev, int32_t accumulate,
+                          void* stream);
+/* kpn_scene_prepare for desc->kpt3d of (n_kpt, 3) (the reference asserts kpt3d.shape[1] == n_kpt, src/spatial.py:80): rows
+ * n_kpt..23 of each view's keypoint table are the camera-frame coordinates of keypoint 0.  kpn_scene_prepare is its n_kpt = 24
+ * case, bit for bit. */
+int kpn_scene_prepare_kpt(const kpn_scene_desc* desc, int32_t n_kpt, void* scene_ws, void* stream);
+/* kpn_fold_params / kpn_fold_params_backward for a table whose v_or_w[0] (and, in grads_table, its gradient slot) is the narrow
+ * (128, D + 64) weight_v of layers1.0; plain_out and d_plain are canonical.  One launch each: the same kernels with a load map -
+ * the thread that owns canonical column c reads the narrow column mapped to it, or 0 - so plain_out, norms_out (the fp64 row
+ * sums run over the 232 canonical columns, the padded ones adding exact zeros), dg and dv (written through the same map; a
+ * padded column has no destination) are bit for bit those of kpn_fold_params / _backward on the widened weight_v, gathered. */
+int kpn_fold_params_shape(const kpn_field_shape* shape, const kpn_param_table* table, float* plain_out, float* norms_out,
+                          void* stream);
+int kpn_fold_params_backward_shape(const kpn_field_shape* shape, const kpn_param_table* table, const float* norms,
+                                   const float* d_plain, const kpn_param_table* grads_table, int32_t accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One convolution of the image encoders, forward and backward: replaces torch.nn.functional.conv2d and its autograd

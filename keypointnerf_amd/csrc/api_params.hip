@@ -24,6 +24,14 @@ void fold_bind_norms(kpn_fold_kargs& k, float* norms) {
 }  // namespace
 static_assert(KPN_PARAM_LAYERS == P_COUNT, "kpn_param_table has one entry per layer of the plain layout");
 
+static int check_field_shape(const kpn_field_shape* s) {
+    KPN_REQUIRE(s != nullptr, "null field shape");
+    KPN_REQUIRE(s->n_kpt >= 1 && s->n_kpt <= KPN_NKPT, "n_kpt out of range: the field kernels hold 1..24 keypoints (KPN_N_KPT)");
+    KPN_REQUIRE(s->sp_level >= 0 && s->sp_level <= KPN_SP_LEVEL, "sp_level out of range: the field kernels hold 0..3 octaves (KPN_SP_LEVEL)");
+    return KPN_OK;
+}
+static bool canonical_shape(const kpn_field_shape* s) { return s->n_kpt == KPN_NKPT && s->sp_level == KPN_SP_LEVEL; }
+
 static int check_param_table(const kpn_param_table* t) {
     KPN_REQUIRE(t && t->ani_al, "null parameter table / ani_al");
     for (int l = 0; l < P_COUNT; ++l) {
@@ -35,7 +43,18 @@ static int check_param_table(const kpn_param_table* t) {
 
 extern "C" size_t kpn_fold_norm_floats(void) { return 3 * (size_t)fold_norm_rows(); }
 
+static const kpn_field_shape canonical_field_shape = {KPN_NKPT, KPN_SP_LEVEL};
 extern "C" int kpn_fold_params(const kpn_param_table* table, float* plain_out, float* norms_out, void* stream) {
+    return kpn_fold_params_shape(&canonical_field_shape, table, plain_out, norms_out, stream);
+}
+extern "C" int kpn_fold_params_backward(const kpn_param_table* table, const float* norms, const float* d_plain,
+                                        const kpn_param_table* grads_table, int32_t accumulate, void* stream) {
+    return kpn_fold_params_backward_shape(&canonical_field_shape, table, norms, d_plain, grads_table, accumulate, stream);
+}
+
+extern "C" int kpn_fold_params_shape(const kpn_field_shape* shape, const kpn_param_table* table, float* plain_out, float* norms_out,
+                                     void* stream) {
+    if (int e = check_field_shape(shape)) return e;
     if (int e = check_param_table(table)) return e;
     KPN_REQUIRE(plain_out && norms_out, "null pointer");
     KPN_REQUIRE(reinterpret_cast<uintptr_t>(norms_out) % 8 == 0, "norms_out must be 8-byte aligned");
@@ -44,12 +63,16 @@ extern "C" int kpn_fold_params(const kpn_param_table* table, float* plain_out, f
     fold_layers(k);
     k.plain = plain_out;
     fold_bind_norms(k, norms_out);
-    KPN_LAUNCH(k_fold_params, dim3((unsigned)fold_rows()), dim3(64), stream, k);
+    k.n_kpt = shape->n_kpt; k.sp_level = shape->sp_level;
+    if (canonical_shape(shape)) KPN_LAUNCH(k_fold_params<false>, dim3((unsigned)fold_rows()), dim3(64), stream, k);
+    else KPN_LAUNCH(k_fold_params<true>, dim3((unsigned)fold_rows()), dim3(64), stream, k);
     return check_launch("kpn_fold_params");
 }
 
-extern "C" int kpn_fold_params_backward(const kpn_param_table* table, const float* norms, const float* d_plain,
-                                        const kpn_param_table* grads_table, int32_t accumulate, void* stream) {
+extern "C" int kpn_fold_params_backward_shape(const kpn_field_shape* shape, const kpn_param_table* table, const float* norms,
+                                              const float* d_plain, const kpn_param_table* grads_table, int32_t accumulate,
+                                              void* stream) {
+    if (int e = check_field_shape(shape)) return e;
     if (int e = check_param_table(table)) return e;
     KPN_REQUIRE(norms && d_plain && grads_table, "null pointer");
     KPN_REQUIRE(reinterpret_cast<uintptr_t>(norms) % 8 == 0, "norms must be 8-byte aligned");
@@ -62,8 +85,34 @@ extern "C" int kpn_fold_params_backward(const kpn_param_table* table, const floa
     k.d_plain = d_plain;
     k.accumulate = accumulate != 0;
     fold_bind_norms(k, const_cast<float*>(norms));
-    KPN_LAUNCH(k_fold_params_backward, dim3((unsigned)fold_rows()), dim3(64), stream, k);
+    k.n_kpt = shape->n_kpt; k.sp_level = shape->sp_level;
+    if (canonical_shape(shape)) KPN_LAUNCH(k_fold_params_backward<false>, dim3((unsigned)fold_rows()), dim3(64), stream, k);
+    else KPN_LAUNCH(k_fold_params_backward<true>, dim3((unsigned)fold_rows()), dim3(64), stream, k);
     return check_launch("kpn_fold_params_backward");
+}
+
+// keypoint sets: the narrow plain vector (layers1.0's W as (128, D + 64)) <-> plain
+extern "C" size_t kpn_plain_weight_floats_shape(const kpn_field_shape* shape) {
+    if (check_field_shape(shape) != KPN_OK) return 0;
+    const int cols = plain_dims[P_G1_0][1];
+    return kpn_plain_weight_floats() - (size_t)plain_dims[P_G1_0][0] * (size_t)(cols - kpn_narrow_col(cols, shape->n_kpt, shape->sp_level));
+}
+extern "C" int kpn_widen_plain(const kpn_field_shape* shape, const float* narrow_dev, float* plain_dev, void* stream) {
+    if (int e = check_field_shape(shape)) return e;
+    KPN_REQUIRE(narrow_dev && plain_dev, "null pointer");
+    const int n = (int)kpn_plain_weight_floats();
+    KPN_LAUNCH(k_widen_plain, grid1d((int64_t)n, 256), dim3(256), stream, narrow_dev, plain_dev, n, plain_dims[P_G1_0][0],
+               (int)shape->n_kpt, (int)shape->sp_level);
+    return check_launch("kpn_widen_plain");
+}
+extern "C" int kpn_narrow_plain_grad(const kpn_field_shape* shape, const float* d_plain_dev, float* d_narrow_dev, int32_t accumulate,
+                                     void* stream) {
+    if (int e = check_field_shape(shape)) return e;
+    KPN_REQUIRE(d_plain_dev && d_narrow_dev, "null pointer");
+    const int n = (int)kpn_plain_weight_floats_shape(shape);
+    KPN_LAUNCH(k_narrow_plain_grad, grid1d((int64_t)n, 256), dim3(256), stream, d_plain_dev, d_narrow_dev, n, plain_dims[P_G1_0][0],
+               (int)shape->n_kpt, (int)shape->sp_level, (int)(accumulate != 0));
+    return check_launch("kpn_narrow_plain_grad");
 }
 
 extern "C" int kpn_adam_step(const kpn_adam_args* a, void* stream) {

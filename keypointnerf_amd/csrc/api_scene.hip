@@ -56,13 +56,18 @@ extern "C" int kpn_scene_layout(const kpn_scene_desc* d, size_t offsets[6]) {
 }
 
 extern "C" int kpn_scene_prepare(const kpn_scene_desc* d, void* scene_ws, void* stream) {
+    return kpn_scene_prepare_kpt(d, KPN_NKPT, scene_ws, stream);
+}
+
+extern "C" int kpn_scene_prepare_kpt(const kpn_scene_desc* d, int32_t n_kpt, void* scene_ws, void* stream) {
     if (int e = check_desc(d)) return e;
+    KPN_REQUIRE(n_kpt >= 1 && n_kpt <= KPN_NKPT, "n_kpt out of range: the field kernels hold 1..24 keypoints (KPN_N_KPT)");
     KPN_REQUIRE(scene_ws != nullptr, "scene workspace is null");
     const SceneLayout L = scene_layout(d);
     float* base = static_cast<float*>(scene_ws);
     const int V = d->n_views;
     float* flags = base + L.flags;   // zeroed by k_scene_table (first on the stream), raised by the copies behind it
-    KPN_LAUNCH(k_scene_table, dim3(V), dim3(128), stream, V, d->KRT, d->extrin, d->kpt3d, base + L.table, flags);
+    KPN_LAUNCH(k_scene_table, dim3(V), dim3(128), stream, V, (int)n_kpt, d->KRT, d->extrin, d->kpt3d, base + L.table, flags);
     const int HW = d->src_h * d->src_w;
     const int ptiles = (HW + KPN_PACK_PIX - 1) / KPN_PACK_PIX;
     KPN_LAUNCH(k_pack_rgbm, dim3(V * ptiles), dim3(256), stream, HW, ptiles, d->img,

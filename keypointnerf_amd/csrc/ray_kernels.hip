@@ -35,7 +35,9 @@ __device__ __forceinline__ void kpn_note_absmax(float* __restrict__ flags, int u
 // per-view table: KRT rows, extrinsic rows, camera centre = inverse(KRT)[:3,3] (model.py:823-824), keypoints in the camera
 // frame (spatial.py:85).  One workgroup of two wavefronts per view: the first lane of the second wavefront runs the double
 // Gauss-Jordan while the lanes of the first copy the rows, transform the 24 keypoints and zero the tail of the table row.
-__global__ __launch_bounds__(128) void k_scene_table(int V, const float* __restrict__ KRT, const float* __restrict__ extrin,
+// kpt3d holds n_kpt <= 24 keypoints; table rows n_kpt..23 repeat keypoint 0 (kpn_scene_prepare_kpt: a model with fewer keypoints
+// is the 24-keypoint model with zero weights on the padded ones, whose encoding values must be finite).
+__global__ __launch_bounds__(128) void k_scene_table(int V, int n_kpt, const float* __restrict__ KRT, const float* __restrict__ extrin,
                                                      const float* __restrict__ kpt3d, float* __restrict__ table,
                                                      float* __restrict__ flags) {
     const int v = blockIdx.x, t = threadIdx.x;
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(128) void k_scene_table(int V, const float* __restr
     if (t >= 64) return;
     if (t < 12) { tb[KPN_TBL_KRT + t] = M[t]; tb[KPN_TBL_EXT + t] = E[t]; }
     for (int e = t; e < KPN_NKPT * 3; e += 64) {
-        const int k = e / 3, i = e - k * 3;
+        const int row = e / 3, i = e - row * 3, k = row < n_kpt ? row : 0;
         tb[KPN_TBL_KCAM + e] =
             KADD(kpn_dot3(kpt3d[k * 3 + 0], kpt3d[k * 3 + 1], kpt3d[k * 3 + 2], E[i * 4 + 0], E[i * 4 + 1], E[i * 4 + 2]),
                  E[i * 4 + 3]);

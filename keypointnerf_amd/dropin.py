@@ -22,17 +22,22 @@ Served by the library (batch size 1, as configs/zju.json:12 and src/model.py:938
   ``ani_al`` and the image encoders (through ``feat_geo`` / ``feat_tex``) by autograd
   (``torch.ops.kpnerf.render_rays_train``, keypointnerf_amd/torch_ops.py).
 
+Models with 1..24 keypoints and 0..3 encoding octaves (``sp_args.n_kpt`` / ``sp_level``) are served; the kernels run them as the
+24 / 3 model with zero weights on the missing encoding values, so a padded keypoint costs what a real one costs.
+
 Anything outside that envelope (larger batches, ``separate_cf``, a spatial encoder other than the shipped
-``rel_z_decay``) is refused at ``install`` time or forwarded to the reference's own method — that is the
+``rel_z_decay``, more than 24 keypoints or 3 octaves) is refused at ``install`` time or forwarded to the reference's own method — that is the
 reference itself, not a fallback of this library.
 """
+import operator
 import types
 
 import numpy as np
 import torch
 
 from . import ops
-from .weights import hot_tensors, plain_tensor_from_module
+from .lib import N_KPT_CAPACITY, SP_LEVEL_CAPACITY
+from .weights import CANONICAL_SHAPE, field_shape, hot_tensors, plain_tensor_from_module
 
 _OUT_KEYS = ("tex_fg", "depth", "alpha", "tex_fg_fine", "depth_fine", "alpha_fine", "sdf")
 _SEAMS = ("batch_render_pifu_nerf", "render_pifu_nerf", "query", "rgba2out", "importance_sample", "ray_bbox_intersection")
@@ -56,18 +61,28 @@ def _version_key(tensors):
 
 
 def check_supported(net):
-    """The kernels implement the shipped configuration (reference configs/zju.json:39-45): keypoint-relative depth
-    encoding with Gaussian decay, 3 octaves, 24 keypoints, scale 1.  A model built with another SpatialEncoder
-    branch of the same feature width would pass the weight-shape check and render silently wrong: refuse it."""
+    """The kernels implement the shipped encoder (reference configs/zju.json:39-45): keypoint-relative depth encoding with
+    Gaussian decay, scale 1, built for 24 keypoints and 3 octaves.  The keypoint count and the octaves are properties of the
+    user's data, not of the design: a model with 1..24 keypoints and 0..3 octaves is served as the 24 / 3 model with zero weights
+    on the missing encoding values (include/kpnerf.h, "Keypoint sets"); more than that does not fit the rows kernel's first
+    layer.  A model built with another SpatialEncoder branch of the same feature width would pass the weight-shape check and
+    render silently wrong: refuse it."""
     enc = getattr(net, "sp_encoder", None)
     if enc is None:
         return
-    want = {"sp_type": "rel_z_decay", "sp_level": 3, "n_kpt": 24}
-    for k, v in want.items():
-        got = getattr(enc, k, v)
-        if got != v:
-            raise NotImplementedError(f"keypointnerf_amd serves sp_encoder.{k} == {v!r} only (got {got!r}; "
-                                      f"reference src/spatial.py:88-133 has other branches, configs/zju.json selects this one)")
+    got = getattr(enc, "sp_type", "rel_z_decay")
+    if got != "rel_z_decay":
+        raise NotImplementedError(f"keypointnerf_amd serves sp_encoder.sp_type == 'rel_z_decay' only (got {got!r}; "
+                                  f"reference src/spatial.py:88-133 has other branches, configs/zju.json selects this one)")
+    for k, lo, cap in (("n_kpt", 1, N_KPT_CAPACITY), ("sp_level", 0, SP_LEVEL_CAPACITY)):
+        got = getattr(enc, k, cap)
+        try:
+            ok = not isinstance(got, bool) and lo <= operator.index(got) <= cap     # any integer type: a numpy integer from a config too
+        except TypeError:
+            ok = False
+        if not ok:
+            raise NotImplementedError(f"keypointnerf_amd serves sp_encoder.{k} in {lo}..{cap} (got {got!r}): the field kernels' capacity "
+                                      f"is {N_KPT_CAPACITY} keypoints and {SP_LEVEL_CAPACITY} octaves (configs/zju.json:41,44)")
     if float(getattr(enc, "scale", 1.0)) != 1.0:
         raise NotImplementedError("keypointnerf_amd serves sp_encoder.scale == 1.0 only (configs/zju.json:42)")
 
@@ -82,6 +97,7 @@ class _State:
     def __init__(self, net, native_params=False):
         self.net = net
         self.native_params = bool(native_params)
+        self.shape = field_shape(net)  # (n_kpt, sp_level): sizes the first layer's weight_v; the kernels' operands are 24 / 3 always
         self.hot = None              # native_params: the 44 live tensors in kpn_param_table order
         self.weights = None
         self.weights_key = None
@@ -94,10 +110,11 @@ class _State:
         self.attached = None         # (encoder key, feat_geo object)
         self.attached_tex = None     # feat_tex object computed by attach_tex_feat(im) for the SAME im, else None
 
-    @staticmethod
-    def fold(tensors):
+    def fold(self, tensors):
         from . import torch_ops  # noqa: F401  (registers torch.ops.kpnerf.*)
-        return torch.ops.kpnerf.fold_params(tensors)
+        if self.shape == CANONICAL_SHAPE:
+            return torch.ops.kpnerf.fold_params(tensors)
+        return torch.ops.kpnerf.fold_params_shape(tensors, self.shape[0], self.shape[1])
 
     def native_tensors(self):
         if self.hot is None:                                         # resolved once: install() again after replacing parameter objects
@@ -142,8 +159,17 @@ class _State:
         same shape would serve a stale workspace).  PreparedScene keeps every input tensor alive."""
         if "transf" in cam:
             raise NotImplementedError("cam['transf'] (src/model.py:716-718) is not produced by decode_batch and not served")
+        self.check_keypoints(sp_data)
         return ops.PreparedScene(img, cam, feat_geo, feat_tex, sp_data, fg_mask,
                                  disable_fg_mask=getattr(self.net, "disable_fg_mask", False), sigma=encoder_sigma(self.net))
+
+    def check_keypoints(self, sp_data):
+        """The reference asserts kpt3d.shape[1] == n_kpt inside the encoder (src/spatial.py:80); here the table would silently pad
+        or truncate, so the same condition is an error."""
+        kpt = sp_data["kpt3d"]
+        if kpt.numel() != 3 * self.shape[0]:
+            raise ValueError(f"sp_data['kpt3d'] is {tuple(kpt.shape)}, the model's sp_encoder.n_kpt is {self.shape[0]}: expected "
+                             f"(1, {self.shape[0]}, 3) (reference src/spatial.py:80)")
 
     def plan(self, scene, grid, Sc, Sf, fine):
         """Render plans (outputs + workspace) are reused across calls with the same geometry; the outputs handed to
@@ -307,6 +333,7 @@ def install(net, rows_mode=None, native_params=False):
         extrin = sp_data["extrin"] if "extrin" in sp_data else cam_in["extrin"]
         if "transf" in cam_in:
             raise NotImplementedError("cam['transf'] (src/model.py:716-718) is not served")
+        st.check_keypoints(sp_data)
         if st.native_params:
             # the operands of this parameter version go to the render_rays_train call below, which then does not pack them again
             plain, packed = st.native_plain()

@@ -70,6 +70,14 @@ class ParamTable(ctypes.Structure):
     _fields_ = [("g", c_p * 19), ("v_or_w", c_p * 19), ("b", c_p * 19), ("ani_al", c_p)]
 
 
+class FieldShape(ctypes.Structure):
+    """struct kpn_field_shape"""
+    _fields_ = [("n_kpt", c_i32), ("sp_level", c_i32)]
+
+
+N_KPT_CAPACITY, SP_LEVEL_CAPACITY = 24, 3     # KPN_N_KPT, KPN_SP_LEVEL
+
+
 class AdamSegment(ctypes.Structure):
     """struct kpn_adam_segment"""
     _fields_ = [(n, c_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("count", c_i64)]
@@ -247,6 +255,13 @@ _SIGNATURES = {
     "kpn_fold_params": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, c_p]),
     "kpn_fold_params_backward": (ctypes.c_int, [ctypes.POINTER(ParamTable), c_p, c_p, ctypes.POINTER(ParamTable), c_i32, c_p]),
     "kpn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamArgs), c_p]),
+    "kpn_plain_weight_floats_shape": (c_sz, [ctypes.POINTER(FieldShape)]),
+    "kpn_widen_plain": (ctypes.c_int, [ctypes.POINTER(FieldShape), c_p, c_p, c_p]),
+    "kpn_narrow_plain_grad": (ctypes.c_int, [ctypes.POINTER(FieldShape), c_p, c_p, c_i32, c_p]),
+    "kpn_scene_prepare_kpt": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_i32, c_p, c_p]),
+    "kpn_fold_params_shape": (ctypes.c_int, [ctypes.POINTER(FieldShape), ctypes.POINTER(ParamTable), c_p, c_p, c_p]),
+    "kpn_fold_params_backward_shape": (ctypes.c_int, [ctypes.POINTER(FieldShape), ctypes.POINTER(ParamTable), c_p, c_p,
+                                                      ctypes.POINTER(ParamTable), c_i32, c_p]),
     "kpn_conv2d_packed_floats": (c_sz, [ctypes.POINTER(Conv2dDesc)]),
     "kpn_conv2d_pack_device": (ctypes.c_int, [ctypes.POINTER(Conv2dDesc), c_p, c_p, c_p]),
     "kpn_conv2d_workspace_bytes": (c_sz, [ctypes.POINTER(Conv2dDesc)]),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as kl
-from .weights import effective_weights, flatten_plain
+from .weights import CANONICAL_SHAPE, effective_weights, flatten_plain, widen_plain_host
 
 _f32 = torch.float32
 _REDUCE_SCRATCH_BYTES = 16392   # include/kpnerf.h, kpn_mse_psnr / kpn_pix_l1_loss: 2048 fp64 block partials and the ticket
@@ -50,9 +50,14 @@ def _p(t):
 class PackedWeights:
     """Hot-path parameters packed for the kernels; built from the reference's state dict / module."""
 
-    def __init__(self, state_dict_or_module, device="cuda"):
+    def __init__(self, state_dict_or_module, device="cuda", shape=None):
+        """shape = (n_kpt, sp_level) of the model the state dict belongs to (None: the shipped 24 / 3): its narrow first layer is
+        widened to the kernels' layout on the host (weights.widen_plain_host)."""
         sd = state_dict_or_module.state_dict() if hasattr(state_dict_or_module, "state_dict") else state_dict_or_module
-        packed = self._pack_on_host(flatten_plain(effective_weights(sd)))
+        plain = flatten_plain(effective_weights(sd, shape))
+        if shape is not None and tuple(shape) != CANONICAL_SHAPE:
+            plain = widen_plain_host(plain, _field_shape(shape, "PackedWeights"))
+        packed = self._pack_on_host(plain)
         # the packers' count of weights beyond fp16's range (include/kpnerf.h kpn_packed_f16_range_check).  Nothing to do here:
         # the two-fp16-piece kernels read the same count on the device and leave the work to the fp32-range kernels (range guard)
         self.f16_beyond = int(packed[-4])
@@ -90,13 +95,54 @@ class PackedWeights:
         return cls.wrap(torch.from_numpy(cls._pack_on_host(flat)).to(device))
 
 
+def _field_shape(shape, what):
+    """(n_kpt, sp_level) checked against the kernels' capacity (KPN_N_KPT, KPN_SP_LEVEL)"""
+    n, lv = int(shape[0]), int(shape[1])
+    if not (1 <= n <= kl.N_KPT_CAPACITY and 0 <= lv <= kl.SP_LEVEL_CAPACITY):
+        raise ValueError(f"{what}: n_kpt must lie in 1..{kl.N_KPT_CAPACITY} and sp_level in 0..{kl.SP_LEVEL_CAPACITY}, got {n} / {lv}")
+    return n, lv
+
+
+def widen_plain(narrow, n_kpt, sp_level):
+    """The narrow plain vector of a (n_kpt, sp_level) model -> the kernels' plain vector, one launch (kpn_widen_plain)."""
+    L = kl.get_library()
+    fs = kl.FieldShape(*_field_shape((n_kpt, sp_level), "widen_plain"))
+    flat = _dev(narrow, "narrow").reshape(-1)
+    if flat.numel() != L.kpn_plain_weight_floats_shape(ctypes.byref(fs)):
+        raise ValueError(f"widen_plain: expected {L.kpn_plain_weight_floats_shape(ctypes.byref(fs))} floats for n_kpt = {n_kpt}, "
+                         f"sp_level = {sp_level}, got {flat.numel()}")
+    plain = torch.empty(L.kpn_plain_weight_floats(), dtype=_f32, device=flat.device)
+    L.check(L.kpn_widen_plain(ctypes.byref(fs), _p(flat), _p(plain), _stream()))
+    return plain
+
+
+def narrow_plain_grad(d_plain, n_kpt, sp_level, out=None, accumulate=False):
+    """The adjoint of widen_plain: the gradient of the plain vector -> the gradient of the narrow one (kpn_narrow_plain_grad).
+    out: a destination, overwritten or (accumulate=True) added to."""
+    L = kl.get_library()
+    fs = kl.FieldShape(*_field_shape((n_kpt, sp_level), "narrow_plain_grad"))
+    g = _dev(d_plain, "d_plain").reshape(-1)
+    if g.numel() != L.kpn_plain_weight_floats():
+        raise ValueError("narrow_plain_grad: d_plain has the wrong size")
+    n = L.kpn_plain_weight_floats_shape(ctypes.byref(fs))
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs a destination (out)")
+        out = torch.empty(n, dtype=_f32, device=g.device)
+    elif out.dtype != _f32 or not out.is_contiguous() or out.numel() != n or not _on_gpu(out):
+        raise ValueError("narrow_plain_grad: out must be a contiguous float32 GPU tensor of the narrow vector's size")
+    L.check(L.kpn_narrow_plain_grad(ctypes.byref(fs), _p(g), _p(out), int(bool(accumulate)), _stream()))
+    return out
+
+
 class PreparedScene:
     """kpn_scene_desc + the prepared (channels-last) device workspace for one set of source views.
 
     Arguments are the reference's own objects (reference src/model.py:336-355, 653-680):
     img (V,3,H,W); cam dict {KRT,(K),extrin|sp_data['extrin'],width,height,znear,zfar,nml_scale};
-    feat_geo [ (V,64,h0,w0), (V,8,h1,w1) ]; feat_tex (V,8,ht,wt); sp_data {kpt3d (1,24,3), extrin (V,4,4)};
-    src_foreground_mask (1,V,1,H,W) bool.
+    feat_geo [ (V,64,h0,w0), (V,8,h1,w1) ]; feat_tex (V,8,ht,wt); sp_data {kpt3d (1,n,3), extrin (V,4,4)};
+    src_foreground_mask (1,V,1,H,W) bool.  n <= 24 keypoints (the model's n_kpt, src/spatial.py:80): the kernels' table holds 24,
+    rows n..23 repeat keypoint 0 (kpn_scene_prepare_kpt) and the padded first-layer weights of such a model are zero.
     """
 
     def __init__(self, img, cam, feat_geo, feat_tex, sp_data, src_foreground_mask, disable_fg_mask=False, sigma=0.1):
@@ -114,9 +160,12 @@ class PreparedScene:
         extrin = sp_data["extrin"] if "extrin" in sp_data else cam["extrin"]
         self.extrin = _dev(extrin, "extrin").reshape(V, 4, 4)
         kpt = _dev(sp_data["kpt3d"], "kpt3d")
-        if kpt.numel() != 72:
-            raise ValueError("kpt3d must be (1,24,3): batch size 1 and 24 keypoints (reference src/model.py:938, configs/zju.json:44)")
-        self.kpt3d = kpt.reshape(24, 3)
+        n_kpt = kpt.numel() // 3
+        if kpt.numel() != 3 * n_kpt or not 1 <= n_kpt <= kl.N_KPT_CAPACITY:
+            raise ValueError(f"kpt3d must be (1,n,3) with n in 1..{kl.N_KPT_CAPACITY}: batch size 1 (reference src/model.py:938) and at most "
+                             f"the {kl.N_KPT_CAPACITY} keypoints the field kernels hold (configs/zju.json:44), got {tuple(kpt.shape)}")
+        self.n_kpt = n_kpt
+        self.kpt3d = kpt.reshape(n_kpt, 3)
         if int(cam["width"]) != W or int(cam["height"]) != H:
             raise ValueError("cam width/height must match the source images")
         if disable_fg_mask:
@@ -143,7 +192,7 @@ class PreparedScene:
         if nbytes == 0:
             raise kl.KpnError(L.kpn_last_error().decode())
         self.ws = torch.empty(nbytes // 4, dtype=_f32, device=self.img.device)
-        L.check(L.kpn_scene_prepare(ctypes.byref(d), _p(self.ws), _stream()))
+        L.check(L.kpn_scene_prepare_kpt(ctypes.byref(d), n_kpt, _p(self.ws), _stream()))
 
     def as_op_args(self):
         """(scene_ws, scene_dims, scene_scalars) for torch.ops.kpnerf.field_query (keypointnerf_amd/torch_ops.py)."""
@@ -648,20 +697,21 @@ def train_loss(tex, tex_fine, tar, alpha, alpha_fine, tar_alpha, weights, want_g
     return terms, d_x, d_xf, d_a, d_af
 
 
-def _hot_layout():
-    """per slot of the 44-tensor list (weights.hot_tensor_names): (kpn_param_table field, layer index or None, shape)"""
-    from .synthetic import HOTPATH_LAYERS
+def _hot_layout(shape=None):
+    """per slot of the 44-tensor list (weights.hot_tensor_names): (kpn_param_table field, layer index or None, shape); shape =
+    (n_kpt, sp_level) of the model (None: 24 / 3) sizes the first layer's weight_v"""
+    from .synthetic import HOTPATH_LAYERS, hotpath_layers
     slots = []
-    for l, (_, _, (o, i), wn) in enumerate(HOTPATH_LAYERS):
+    for l, (_, _, (o, i), wn) in enumerate(HOTPATH_LAYERS if shape is None else hotpath_layers(*shape)):
         if wn:
             slots.append(("g", l, (o, 1)))
         slots += [("v_or_w", l, (o, i)), ("b", l, (o,))]
     return slots + [("ani_al", None, ())]
 
 
-def _param_table(tensors, what):
+def _param_table(tensors, what, shape=None):
     """kpn_param_table over a 44-tensor list in weights.hot_tensor_names order; an entry of `tensors` may be None (a NULL slot)"""
-    slots = _hot_layout()
+    slots = _hot_layout(shape)
     if len(tensors) != len(slots):
         raise ValueError(f"{what}: expected {len(slots)} tensors (weights.hot_tensor_names), got {len(tensors)}")
     table = kl.ParamTable()
@@ -679,26 +729,35 @@ def _param_table(tensors, what):
     return table
 
 
-def fold_params(tensors):
+def fold_params(tensors, shape=None):
     """The live hot-path tensors (weights.hot_tensors) -> (plain, norms): the flat effective-parameter vector of
     weights.flatten_plain's layout — weight-norm folded (torch._weight_norm(v, g, 0), reference src/utils.py:542-543), everything
-    else copied — and the side buffer fold_params_backward needs, in one launch (kpn_fold_params)."""
+    else copied — and the side buffer fold_params_backward needs, in one launch (kpn_fold_params).  shape = (n_kpt, sp_level) of
+    the model (None: 24 / 3): the first layer's weight_v is then the narrow tensor, plain stays the kernels' 24 / 3 vector
+    (kpn_fold_params_shape, still one launch)."""
     L = kl.get_library()
     tensors = [t.detach() for t in tensors]
-    table = _param_table(tensors, "fold_params tensors")
+    if shape is not None:
+        shape = _field_shape(shape, "fold_params")
+    table = _param_table(tensors, "fold_params tensors", shape)
     dev = tensors[0].device
     plain = torch.empty(L.kpn_plain_weight_floats(), dtype=_f32, device=dev)
     norms = torch.empty(L.kpn_fold_norm_floats() // 2, dtype=torch.float64, device=dev).view(_f32)     # 8-byte aligned
-    L.check(L.kpn_fold_params(ctypes.byref(table), _p(plain), _p(norms), _stream()))
+    if shape is None:
+        L.check(L.kpn_fold_params(ctypes.byref(table), _p(plain), _p(norms), _stream()))
+    else:
+        L.check(L.kpn_fold_params_shape(ctypes.byref(kl.FieldShape(*shape)), ctypes.byref(table), _p(plain), _p(norms), _stream()))
     return plain, norms
 
 
-def fold_params_backward(tensors, norms, d_plain, out=None, accumulate=False):
+def fold_params_backward(tensors, norms, d_plain, out=None, accumulate=False, shape=None):
     """d_plain -> the gradients of the 44 tensors in one launch (kpn_fold_params_backward).  out=None: returns new tensors.  out = a 44-list of destinations (None entries are skipped): written in place — overwritten, or added to with
     accumulate=True (.grad's semantics) — and returned."""
     L = kl.get_library()
     tensors = [t.detach() for t in tensors]
-    table = _param_table(tensors, "fold_params tensors")
+    if shape is not None:
+        shape = _field_shape(shape, "fold_params_backward")
+    table = _param_table(tensors, "fold_params tensors", shape)
     g = _dev(d_plain, "d_plain").reshape(-1)
     if g.numel() != L.kpn_plain_weight_floats() or norms.numel() != L.kpn_fold_norm_floats():
         raise ValueError("d_plain / norms have the wrong size")
@@ -706,8 +765,12 @@ def fold_params_backward(tensors, norms, d_plain, out=None, accumulate=False):
         if accumulate:
             raise ValueError("accumulate=True needs destinations (out)")
         out = [torch.empty_like(t) for t in tensors]      # separate allocations: the outputs of a custom operator may not alias
-    grads = _param_table([None if t is None else t.detach() for t in out], "fold_params gradients")
-    L.check(L.kpn_fold_params_backward(ctypes.byref(table), _p(norms), _p(g), ctypes.byref(grads), int(bool(accumulate)), _stream()))
+    grads = _param_table([None if t is None else t.detach() for t in out], "fold_params gradients", shape)
+    if shape is None:
+        L.check(L.kpn_fold_params_backward(ctypes.byref(table), _p(norms), _p(g), ctypes.byref(grads), int(bool(accumulate)), _stream()))
+    else:
+        L.check(L.kpn_fold_params_backward_shape(ctypes.byref(kl.FieldShape(*shape)), ctypes.byref(table), _p(norms), _p(g),
+                                                 ctypes.byref(grads), int(bool(accumulate)), _stream()))
     return out
 
 

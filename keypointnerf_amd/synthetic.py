@@ -16,7 +16,8 @@ import math
 import numpy as np
 import torch
 
-N_KPT = 24
+N_KPT = 24          # the capacity of the field kernels (KPN_N_KPT) and the shipped skeleton (configs/zju.json:44)
+SP_LEVEL = 3        # likewise for the octaves of the keypoint encoding (KPN_SP_LEVEL, configs/zju.json:41)
 
 
 def _look_at(pos, target=(0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)):
@@ -50,7 +51,7 @@ def _intrinsics(H, W, focal_at_512=600.0):
 
 
 def make_scene(n_views=3, src_hw=(512, 512), tar_hw=(512, 512), mask="ellipsoid", seed=1,
-               tar_near_far=(2.0, 8.0), tar_angle=None, device="cpu", dtype=torch.float32, tar_focal_at_512=600.0):
+               tar_near_far=(2.0, 8.0), tar_angle=None, device="cpu", dtype=torch.float32, tar_focal_at_512=600.0, n_kpt=N_KPT):
     """Returns a dict with the tensors/dicts the reference's hot path consumes.
 
     keys: img (V,3,H,W) in [0,1]; feat_geo [list of 2]; feat_tex; cam (source cameras dict);
@@ -61,7 +62,12 @@ def make_scene(n_views=3, src_hw=(512, 512), tar_hw=(512, 512), mask="ellipsoid"
     1.8 m subject 70 % of the frame height; 800 frames it like the reference's orbit does (render_video_zju: 1337.6 px at
     5 m = 94 % of the height, src/model.py:178-187), which is what brings the fraction of valid sample points to the
     30-40 % SURVEY.md §8(d) specifies for the ellipsoid scene.
+
+    n_kpt: the skeleton's size (1..24): the first n_kpt rows of the 24-keypoint scene of the same seed, everything else — the
+    bounds included — unchanged, so that models of different keypoint counts see the same frame.
     """
+    if not 1 <= int(n_kpt) <= N_KPT:
+        raise ValueError(f"n_kpt must lie in 1..{N_KPT}")
     H, W = src_hw
     Ht, Wt = tar_hw
     g = torch.Generator().manual_seed(seed)
@@ -125,7 +131,7 @@ def make_scene(n_views=3, src_hw=(512, 512), tar_hw=(512, 512), mask="ellipsoid"
         raise ValueError(f"unknown mask kind {mask!r}")
 
     scene = {"img": img, "feat_geo": feat_geo, "feat_tex": feat_tex, "cam": cam, "cam_tar": cam_tar,
-             "sp_data": {"kpt3d": kpt3d, "extrin": extrin}, "bounds": bounds,
+             "sp_data": {"kpt3d": kpt3d if n_kpt == N_KPT else kpt3d[:, :n_kpt].contiguous(), "extrin": extrin}, "bounds": bounds,
              "src_foreground_mask": fg, "n_views": V}
     return to_device(scene, device)
 
@@ -167,7 +173,16 @@ HOTPATH_LAYERS = [
 ]
 
 
-def random_hotpath_state_dict(seed=0, bias_std=0.05, density_gain=25.0, density_bias=0.0):
+def hotpath_layers(n_kpt=N_KPT, sp_level=SP_LEVEL):
+    """HOTPATH_LAYERS of a model with n_kpt keypoints and sp_level octaves: the reference sizes the first linear of mlp_geo from the
+    encoder, (1 + 2 sp_level) n_kpt + 64 inputs (src/spatial.py:49-53, src/model.py:569-572); nothing else depends on them."""
+    if not (1 <= int(n_kpt) <= N_KPT and 0 <= int(sp_level) <= SP_LEVEL):
+        raise ValueError(f"n_kpt must lie in 1..{N_KPT} and sp_level in 0..{SP_LEVEL}")
+    name, prefix, (o, _), wn = HOTPATH_LAYERS[0]
+    return [(name, prefix, (o, (1 + 2 * int(sp_level)) * int(n_kpt) + 64), wn)] + HOTPATH_LAYERS[1:]
+
+
+def random_hotpath_state_dict(seed=0, bias_std=0.05, density_gain=25.0, density_bias=0.0, n_kpt=N_KPT, sp_level=SP_LEVEL):
     """A random state dict with the reference's parameter names/shapes for the hot-path modules.
 
     Used where the reference itself is not importable (GPU box): kaiming-like weights, non-zero
@@ -175,10 +190,11 @@ def random_hotpath_state_dict(seed=0, bias_std=0.05, density_gain=25.0, density_
     density head scaled so that alpha along a ray is neither ~0 nor saturated.  density_bias is added to the bias of the
     density output `rad` (mlp_geo.layers2.layers.2, row 1): a negative value makes relu(rad) exactly 0 in part of the visual
     hull, as a trained density is in the free space between the silhouettes' hull and the surface.
+    n_kpt / sp_level: the model's keypoint count and octaves (hotpath_layers); the defaults are the shipped model.
     """
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for name, prefix, (o, i), wn in HOTPATH_LAYERS:
+    for name, prefix, (o, i), wn in hotpath_layers(n_kpt, sp_level):
         w = torch.randn(o, i, generator=g) * math.sqrt(2.0 / i)
         b = torch.randn(o, generator=g) * bias_std
         if wn:

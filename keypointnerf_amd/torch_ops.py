@@ -20,6 +20,12 @@ calling them on CPU tensors raises NotImplementedError from the dispatcher.
     torch.ops.kpnerf.fold_params(tensors) -> plain   the 44 live hot-path tensors (weights.hot_tensors) -> the flat effective
                                  parameters in one launch, DIFFERENTIABLE w.r.t. every tensor (one more launch in the backward)
 
+    torch.ops.kpnerf.fold_params_shape(tensors, n_kpt, sp_level) -> plain   the same for a model with n_kpt <= 24 keypoints and
+                                 sp_level <= 3 octaves, whose first weight_v is (128, (1 + 2 sp_level) n_kpt + 64): plain is the
+                                 kernels' 24 / 3 vector, zeros in the padded columns; one launch each way
+    torch.ops.kpnerf.widen_plain(narrow, n_kpt, sp_level) -> plain   the narrow plain vector of such a model (torch's own weight-norm
+                                 fold + cat) -> the kernels' vector, DIFFERENTIABLE (the backward gathers: kpn_narrow_plain_grad)
+
 ``scene_ws / scene_dims / scene_scalars`` come from ``ops.PreparedScene.as_op_args()``.
 
     torch.ops.kpnerf.pix_l1_loss(src, tar, lam) -> (loss, d loss / d src)   the L1 terms of the training loss, DIFFERENTIABLE
@@ -71,6 +77,7 @@ the flat effective-parameter vector ``plain`` (and from there ``weight_g`` / ``w
 ``weights.plain_tensor_from_module``) and the three encoder feature maps.  This is the op the training drop-in calls.
 """
 import collections
+import ctypes
 from typing import List, Optional, Tuple
 
 import torch
@@ -494,6 +501,84 @@ fold_params_norms.register_autograd(_fold_bwd, setup_context=_fold_setup)
 _fragment = torch.library.Library("kpnerf", "FRAGMENT")
 _fragment.define("fold_params(Tensor[] tensors) -> Tensor")
 _fragment.impl("fold_params", lambda tensors: torch.ops.kpnerf.fold_params_norms(tensors)[0], "CompositeImplicitAutograd")
+
+
+# ---- keypoint sets: models with fewer keypoints / octaves than the kernels' 24 / 3 (include/kpnerf.h, "Keypoint sets") ----
+@_lib.custom_op("kpnerf::widen_plain", mutates_args=(), device_types="cuda")
+def widen_plain(narrow: torch.Tensor, n_kpt: int, sp_level: int) -> torch.Tensor:
+    """The narrow plain vector of a (n_kpt, sp_level) model -> the kernels' plain vector (kpn_widen_plain, one launch): the first
+    layer's columns scattered to their 24 / 3 places, zeros in the padded ones, everything else copied."""
+    return ops.widen_plain(narrow, n_kpt, sp_level)
+
+
+@widen_plain.register_fake
+def _(narrow, n_kpt, sp_level):
+    return narrow.new_empty(kl.get_library().kpn_plain_weight_floats())
+
+
+@_lib.custom_op("kpnerf::narrow_plain_grad", mutates_args=(), device_types="cuda")
+def narrow_plain_grad(d_plain: torch.Tensor, n_kpt: int, sp_level: int) -> torch.Tensor:
+    """widen_plain's adjoint: the gradient of the plain vector gathered into the narrow one's (kpn_narrow_plain_grad)."""
+    return ops.narrow_plain_grad(d_plain, n_kpt, sp_level)
+
+
+@narrow_plain_grad.register_fake
+def _(d_plain, n_kpt, sp_level):
+    return d_plain.new_empty(kl.get_library().kpn_plain_weight_floats_shape(ctypes.byref(kl.FieldShape(n_kpt, sp_level))))
+
+
+def _widen_setup(ctx, inputs, output):
+    ctx.shape = (inputs[1], inputs[2])
+
+
+def _widen_bwd(ctx, d_plain):
+    return torch.ops.kpnerf.narrow_plain_grad(d_plain.contiguous(), *ctx.shape), None, None
+
+
+widen_plain.register_autograd(_widen_bwd, setup_context=_widen_setup)
+
+
+@_lib.custom_op("kpnerf::fold_params_norms_shape", mutates_args=(), device_types="cuda")
+def fold_params_norms_shape(tensors: List[torch.Tensor], n_kpt: int, sp_level: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fold_params_norms for a (n_kpt, sp_level) model: tensors[1] is its narrow first weight_v (kpn_fold_params_shape)."""
+    return ops.fold_params(tensors, shape=(n_kpt, sp_level))
+
+
+@fold_params_norms_shape.register_fake
+def _(tensors, n_kpt, sp_level):
+    L = kl.get_library()
+    return tensors[0].new_empty(L.kpn_plain_weight_floats()), tensors[0].new_empty(L.kpn_fold_norm_floats())
+
+
+@_lib.custom_op("kpnerf::fold_params_backward_shape", mutates_args=(), device_types="cuda")
+def fold_params_backward_shape(tensors: List[torch.Tensor], norms: torch.Tensor, d_plain: torch.Tensor, n_kpt: int,
+                               sp_level: int) -> List[torch.Tensor]:
+    """fold_params_backward for a (n_kpt, sp_level) model (kpn_fold_params_backward_shape, overwrite mode)."""
+    return ops.fold_params_backward(tensors, norms, d_plain, shape=(n_kpt, sp_level))
+
+
+@fold_params_backward_shape.register_fake
+def _(tensors, norms, d_plain, n_kpt, sp_level):
+    return [torch.empty_like(t) for t in tensors]
+
+
+def _fold_shape_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[0], output[1])
+    ctx.shape = (inputs[1], inputs[2])
+    ctx.set_materialize_grads(False)
+
+
+def _fold_shape_bwd(ctx, d_plain, _d_norms):
+    *tensors, norms = ctx.saved_tensors
+    if d_plain is None:
+        return None, None, None
+    return torch.ops.kpnerf.fold_params_backward_shape(list(tensors), norms, d_plain.contiguous(), *ctx.shape), None, None
+
+
+fold_params_norms_shape.register_autograd(_fold_shape_bwd, setup_context=_fold_shape_setup)
+_fragment.define("fold_params_shape(Tensor[] tensors, int n_kpt, int sp_level) -> Tensor")
+_fragment.impl("fold_params_shape", lambda tensors, n_kpt, sp_level: torch.ops.kpnerf.fold_params_norms_shape(tensors, n_kpt, sp_level)[0],
+               "CompositeImplicitAutograd")
 
 
 def _encoder_no_autograd(ctx, inputs, output):
