@@ -202,6 +202,28 @@ int kpn_query_backward(const kpn_scene_desc* desc, const void* scene_ws, const f
                        float noise_std, const float* d_out, float* d_plain, float* d_geo0, float* d_geo1, float* d_tex,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same backward calls with one more output, the gradient with respect to the 3D KEYPOINTS (sp_data["kpt3d"]): what autograd
+ * does for SpatialEncoder.forward's rel_z_decay branch (src/spatial.py:76-118), where the keypoints enter the encoding through
+ * kptxyz = kpt3d R^T + t, dz and the decay weight w.  Everything else (arguments, outputs, accumulation) is the call without the
+ * suffix.
+ *   d_kpt3d (n_kpt, 3): += d loss / d kpt3d, summed over the kept (point, view) rows; only the first n_kpt rows are written
+ *        (n_kpt = the keypoints the scene was prepared with, 1..KPN_N_KPT: kpn_scene_prepare_kpt; 24 after kpn_scene_prepare).
+ *        Accumulating like the other outputs: the caller zeroes it.  fp64 sums in a fixed order, no float atomics: reproducible
+ *        for a given order of the valid list.
+ *   workspace: the matching *_workspace_bytes_kpt (the plain size plus the transposed encoding operand of layers1.0 and the
+ *        fp64 partial sums).
+ * Rows of views dropped by keep_mask and rows of masked points contribute exactly nothing and are never read.  No gradient reaches
+ * the query points, the cameras or sigma through these entries. */
+size_t kpn_geo_rows_backward_workspace_bytes_kpt(int64_t n_points, int32_t n_views);
+int kpn_geo_rows_backward_kpt(const kpn_scene_desc* desc, const void* scene_ws, const float* packed_weights, int64_t n_points,
+                              const float* pts, uint32_t keep_mask, const float* d_x, float* d_plain, float* d_geo0,
+                              float* d_geo1, float* d_kpt3d, int32_t n_kpt, void* workspace, size_t workspace_bytes, void* stream);
+size_t kpn_query_backward_workspace_bytes_kpt(int64_t n_points, int32_t n_views);
+int kpn_query_backward_kpt(const kpn_scene_desc* desc, const void* scene_ws, const float* packed_weights, int64_t n_points,
+                           const float* pts, const float* view, int32_t mode, uint32_t keep_mask, const float* noise,
+                           float noise_std, const float* d_out, float* d_plain, float* d_geo0, float* d_geo1, float* d_tex,
+                           float* d_kpt3d, int32_t n_kpt, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Rows kernel of the dominant stage (MLPUNet.layers1 per (point, view) row, reference src/utils.py:691-720), all with
  * fp32 accumulation and the same parity bar against the reference goldens:
  *   3 = v_mfma_f32_32x32x16_f16 with every fp32 operand carried as two fp16 pieces (x - fp16(x) is formed exactly by one
@@ -477,6 +499,20 @@ int kpn_render_rays_train_backward_kept(const kpn_scene_desc* desc, const void* 
                                         const kpn_render_args* args, const kpn_train_args* train, const kpn_render_grads* grads,
                                         float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, void* state,
                                         size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Both train-branch backward calls with the keypoint gradient (kpn_query_backward_kpt above; src/spatial.py:76-118): d_kpt3d
+ * (n_kpt, 3) receives the sum of the coarse and the fine pass of every chunk of rays, +=.  `workspace` is the one of
+ * kpn_render_rays_train_backward_workspace_bytes_kpt for both; the state is the plain call's. */
+size_t kpn_render_rays_train_backward_workspace_bytes_kpt(const kpn_scene_desc* desc, const kpn_render_args* args);
+int kpn_render_rays_train_backward_kpt(const kpn_scene_desc* desc, const void* scene_ws, const float* packed_weights,
+                                       const kpn_render_args* args, const kpn_train_args* train, const kpn_render_grads* grads,
+                                       float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, float* d_kpt3d, int32_t n_kpt,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+int kpn_render_rays_train_backward_kept_kpt(const kpn_scene_desc* desc, const void* scene_ws, const float* packed_weights,
+                                            const kpn_render_args* args, const kpn_train_args* train, const kpn_render_grads* grads,
+                                            float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, float* d_kpt3d,
+                                            int32_t n_kpt, void* state, size_t state_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The perceptual term of the training loss, VGGLoss (src/utils.py:750-805), called by compute_error on every training and

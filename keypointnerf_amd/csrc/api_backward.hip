@@ -102,6 +102,21 @@ BwdLayout bwd_layout(int64_t N, int V, int full) {
     return L;
 }
 size_t bwd_workspace_bytes(int64_t N, int V, int full) { return (N <= 0 || V <= 0) ? 0 : bwd_layout(N, V, full).total; }
+// The keypoint gradient's scratch (kpt_grad_kernels.hip), BEHIND a pass's layout so that no existing offset or size moves: the
+// transposed encoding operand of layers1.0, then the workgroups' fp64 partials [workers][V][KPN_KG_Q].
+const int kKptWorkers = kEmu ? 3 : 256;   // one workgroup per CU and view
+struct KptLayout { size_t wt, partial, partial_bytes, total; };
+KptLayout kpt_layout(size_t base, int V) {
+    KptLayout K{};
+    Carver c;
+    c.o = align_up(base, 256);
+    K.wt = c.take((size_t)KPN_KG_WT_FLOATS * 4);
+    K.partial_bytes = (size_t)kKptWorkers * V * KPN_KG_Q * sizeof(double);
+    K.partial = c.take(K.partial_bytes);
+    K.total = c.o;
+    return K;
+}
+size_t bwd_workspace_bytes_kpt(int64_t N, int V, int full) { return (N <= 0 || V <= 0) ? 0 : kpt_layout(bwd_layout(N, V, full).total, V).total; }
 }  // namespace
 
 // rows[0] = (point, view) rows of the current pass, rows[1] = points, both padded to whole tiles
@@ -121,12 +136,18 @@ struct BackwardPass {
     const float *pts = nullptr, *view = nullptr, *noise = nullptr; float noise_std = 0.0f; const kpn_points* marched = nullptr;
     const float *d_x = nullptr, *d_out = nullptr; float *d_plain = nullptr, *d_geo0 = nullptr, *d_geo1 = nullptr, *d_tex = nullptr;
     void* ws = nullptr; size_t ws_bytes = 0; void* fwd_query_ws = nullptr;
+    float* d_kpt = nullptr; int n_kpt = 0;   // optional: d loss / d kpt3d (n_kpt, 3), added to; ws then holds kpt_layout() as well
 };
 int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp, const BackwardPass& p, void* stream) {
     const int V = d->n_views;
     const int full = p.d_x != nullptr ? 0 : (p.d_tex ? 2 : 1);
     const BwdLayout L = bwd_layout(p.N, V, full);
     if (p.ws_bytes < L.total) return fail(KPN_EWORKSPACE, "backward workspace too small");
+    const KptLayout K = kpt_layout(L.total, V);
+    if (p.d_kpt) {
+        KPN_REQUIRE(p.n_kpt >= 1 && p.n_kpt <= KPN_NKPT, "n_kpt in 1..24");
+        if (p.ws_bytes < K.total) return fail(KPN_EWORKSPACE, "backward workspace too small for the keypoint gradient");
+    }
     if (p.marched && p.N > L.chunk) return fail(KPN_EINVAL, "ray-marched backward pass too large");
     kpn_scene_dev sc = scene_dev(d, scene_ws);
     sc.keep = p.keep_mask;
@@ -186,6 +207,10 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
         if (all.n) KPN_LAUNCH(k_weight_grad_reduce, dim3((mv_all * 2048 + mv_all * 32 + 31) / 32, gz_all, all.n), dim3(256), stream, all,
                               (int)kGradWorkers);
     };
+    if (p.d_kpt) {
+        hipMemsetAsync(base + K.partial, 0, K.partial_bytes, (hipStream_t)stream);
+        KPN_LAUNCH(k_kpt_grad_pack, grid1d(KPN_KG_WT_FLOATS, 256), dim3(256), stream, wp, fp(K.wt));
+    }
     for (int64_t c0 = 0; c0 < p.N; c0 += L.chunk) {
         const int64_t n = (p.N - c0 < L.chunk) ? (p.N - c0) : L.chunk;
         const kpn_points ps = p.marched ? *p.marched
@@ -237,6 +262,10 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
             KPN_LAUNCH(k_geo_rows_bwd, dim3(blocks), dim3(256), stream, sc, ps, wp, (const int*)list, vcount, count + 3,
                        full ? (const float*)u.F.dxrows : p.d_x + c0 * V * 64, full ? 1 : 0, u.B);
         }
+        if (p.d_kpt) {   // reads the D0 and X0 dumps of the launch above
+            const kpn_kpt_grad_args ka{u.B.D0, u.B.X0, fp(K.wt), reinterpret_cast<double*>(base + K.partial), p.n_kpt, wgrad_keep};
+            KPN_LAUNCH(k_kpt_grad, dim3(kKptWorkers, V), dim3(256), stream, sc, ps, (const int*)list, vcount, ka);
+        }
         queue_jobs(ST_LAYERS1);
         if (overflow) return fail(KPN_EWORKSPACE, "weight-gradient scratch too small (internal)");
         {
@@ -244,6 +273,9 @@ int run_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
             run_jobs();
         }
     }
+    if (p.d_kpt)
+        KPN_LAUNCH(k_kpt_grad_finish, dim3(p.n_kpt), dim3(256), stream, sc, (const double*)reinterpret_cast<double*>(base + K.partial),
+                   (int)kKptWorkers, p.d_kpt);
     return check_launch("field backward");
 }
 }  // namespace
@@ -260,6 +292,23 @@ extern "C" int kpn_geo_rows_backward(const kpn_scene_desc* d, const void* scene_
     BackwardPass p;
     p.N = N; p.pts = pts; p.keep_mask = keep_mask; p.d_x = d_x;
     p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.ws = ws; p.ws_bytes = ws_bytes;
+    return run_backward(d, scene_ws, wp, p, stream);
+}
+
+extern "C" size_t kpn_geo_rows_backward_workspace_bytes_kpt(int64_t N, int32_t V) { return bwd_workspace_bytes_kpt(N, V, 0); }
+
+extern "C" int kpn_geo_rows_backward_kpt(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N,
+                                         const float* pts, uint32_t keep_mask, const float* d_x, float* d_plain, float* d_geo0,
+                                         float* d_geo1, float* d_kpt3d, int32_t n_kpt, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = check_desc(d)) return e;
+    KPN_REQUIRE(N >= 0 && N < (1ll << 31), "point count out of range");
+    KPN_REQUIRE(n_kpt >= 1 && n_kpt <= KPN_NKPT, "n_kpt in 1..24");
+    if (N == 0) return KPN_OK;
+    KPN_REQUIRE(scene_ws && wp && pts && d_x && d_plain && d_geo0 && d_geo1 && d_kpt3d && ws, "null pointer");
+    BackwardPass p;
+    p.N = N; p.pts = pts; p.keep_mask = keep_mask; p.d_x = d_x;
+    p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.ws = ws; p.ws_bytes = ws_bytes;
+    p.d_kpt = d_kpt3d; p.n_kpt = n_kpt;
     return run_backward(d, scene_ws, wp, p, stream);
 }
 
@@ -294,5 +343,24 @@ extern "C" int kpn_query_backward(const kpn_scene_desc* d, const void* scene_ws,
     BackwardPass p;
     p.N = N; p.pts = pts; p.view = view; p.mode = mode; p.keep_mask = keep_mask; p.noise = noise; p.noise_std = noise_std; p.d_out = d_out;
     p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.d_tex = d_tex; p.ws = ws; p.ws_bytes = ws_bytes;
+    return run_backward(d, scene_ws, wp, p, stream);
+}
+
+extern "C" size_t kpn_query_backward_workspace_bytes_kpt(int64_t N, int32_t V) { return bwd_workspace_bytes_kpt(N, V, 2); }
+
+extern "C" int kpn_query_backward_kpt(const kpn_scene_desc* d, const void* scene_ws, const float* wp, int64_t N, const float* pts,
+                                      const float* view, int32_t mode, uint32_t keep_mask, const float* noise, float noise_std,
+                                      const float* d_out, float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, float* d_kpt3d,
+                                      int32_t n_kpt, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = check_desc(d)) return e;
+    KPN_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (raw query) or 1 (eval_func)");
+    KPN_REQUIRE(N >= 0 && N < (1ll << 31), "point count out of range");
+    KPN_REQUIRE(n_kpt >= 1 && n_kpt <= KPN_NKPT, "n_kpt in 1..24");
+    if (N == 0) return KPN_OK;
+    KPN_REQUIRE(scene_ws && wp && pts && view && d_out && d_plain && d_geo0 && d_geo1 && d_tex && d_kpt3d && ws, "null pointer");
+    BackwardPass p;
+    p.N = N; p.pts = pts; p.view = view; p.mode = mode; p.keep_mask = keep_mask; p.noise = noise; p.noise_std = noise_std; p.d_out = d_out;
+    p.d_plain = d_plain; p.d_geo0 = d_geo0; p.d_geo1 = d_geo1; p.d_tex = d_tex; p.ws = ws; p.ws_bytes = ws_bytes;
+    p.d_kpt = d_kpt3d; p.n_kpt = n_kpt;
     return run_backward(d, scene_ws, wp, p, stream);
 }

@@ -284,6 +284,8 @@ struct TrainCall {
     void *state, *ws, *stream;
     TrainBwdLayout L; TrainStateLayout S;
     kpn_scene_dev sc; int64_t R; int Sc, Sf, Sfull; RayView rays;
+    float* d_kpt = nullptr; int n_kpt = 0;   // optional keypoint gradient (the _kpt entries): `ws` then ends with kpt_layout()'s scratch
+    size_t bwd_bytes() const { return d_kpt ? kpt_layout(L.total - L.bwd, d->n_views).total : L.total - L.bwd; }
     // the checks of every entry point, in their order, then the layouts.  forward_only: fills `state` and writes the outputs of `a`;
     // otherwise a backward: from `state`, or (state == nullptr) the classic one that repeats the forward inside `ws`
     int begin(size_t state_bytes, size_t ws_bytes, bool forward_only) {
@@ -299,7 +301,8 @@ struct TrainCall {
         if (forward_only) KPN_REQUIRE(state != nullptr, "state null");
         L = train_bwd_layout(d, a);
         S = train_state_layout(d, a);
-        if (!forward_only && ws_bytes < L.total) return fail(KPN_EWORKSPACE, "train backward workspace too small");
+        if (d_kpt) KPN_REQUIRE(n_kpt >= 1 && n_kpt <= KPN_NKPT, "n_kpt in 1..24");
+        if (!forward_only && ws_bytes < L.bwd + bwd_bytes()) return fail(KPN_EWORKSPACE, "train backward workspace too small");
         if (state && state_bytes < S.total) return fail(KPN_EWORKSPACE, "train state too small");
         sc = scene_dev(d, scene_ws);
         R = (int64_t)a->nx * a->ny; Sc = a->n_coarse; Sf = a->n_fine; Sfull = Sc + Sf;
@@ -362,7 +365,8 @@ struct TrainCall {
         BackwardPass b;
         b.N = c.n * p.ps.S; b.marched = &p.ps; b.mode = 1; b.keep_mask = p.keep; b.d_out = drgba;
         b.d_plain = d_plain; b.d_geo0 = d_geo0; b.d_geo1 = d_geo1; b.d_tex = d_tex;
-        b.ws = at<char>(ws, L.bwd); b.ws_bytes = L.total - L.bwd; b.fwd_query_ws = p.query;
+        b.ws = at<char>(ws, L.bwd); b.ws_bytes = bwd_bytes(); b.fwd_query_ws = p.query;
+        b.d_kpt = d_kpt; b.n_kpt = n_kpt;
         return run_backward(d, scene_ws, wp, b, stream);
     }
 };
@@ -373,16 +377,45 @@ extern "C" size_t kpn_render_rays_train_backward_workspace_bytes(const kpn_scene
     return train_bwd_layout(d, a).total;
 }
 
-extern "C" int kpn_render_rays_train_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
-                                              const kpn_render_args* a, const kpn_train_args* t, const kpn_render_grads* g,
-                                              float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, void* ws,
-                                              size_t ws_bytes, void* stream) {
-    TrainCall tc{d, scene_ws, wp, a, t, g, d_plain, d_geo0, d_geo1, d_tex, nullptr, ws, stream};
+namespace {
+int train_backward_classic(TrainCall& tc, size_t ws_bytes) {
+    void* const ws = tc.ws;
     return tc.run(0, ws_bytes, false, [&](const TrainChunk& c) {   // the classic backward: the forward repeated inside `ws`
         int e;   // (the coarse composite's per-ray results are not used: L.scratch)
         return ((e = tc.forward(c, c.coarse)) || (e = tc.composite(c, c.coarse, at(ws, tc.L.scratch))) || (e = tc.reverse(c, c.coarse)) ||
                 (e = tc.forward(c, c.fine)) || (e = tc.reverse(c, c.fine))) ? e : KPN_OK;
     });
+}
+int train_backward_kept(TrainCall& tc, size_t state_bytes, size_t ws_bytes) {
+    return tc.run(state_bytes, ws_bytes, false, [&](const TrainChunk& c) {
+        const int e = tc.reverse(c, c.coarse);
+        return e ? e : tc.reverse(c, c.fine);
+    });
+}
+}  // namespace
+
+extern "C" int kpn_render_rays_train_backward(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
+                                              const kpn_render_args* a, const kpn_train_args* t, const kpn_render_grads* g,
+                                              float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, void* ws,
+                                              size_t ws_bytes, void* stream) {
+    TrainCall tc{d, scene_ws, wp, a, t, g, d_plain, d_geo0, d_geo1, d_tex, nullptr, ws, stream};
+    return train_backward_classic(tc, ws_bytes);
+}
+
+extern "C" size_t kpn_render_rays_train_backward_workspace_bytes_kpt(const kpn_scene_desc* d, const kpn_render_args* a) {
+    if (check_desc(d) != KPN_OK || check_render(a) != KPN_OK || !a->fine) return 0;
+    const TrainBwdLayout L = train_bwd_layout(d, a);
+    return L.bwd + kpt_layout(L.total - L.bwd, d->n_views).total;
+}
+
+extern "C" int kpn_render_rays_train_backward_kpt(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
+                                                  const kpn_render_args* a, const kpn_train_args* t, const kpn_render_grads* g,
+                                                  float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, float* d_kpt3d,
+                                                  int32_t n_kpt, void* ws, size_t ws_bytes, void* stream) {
+    KPN_REQUIRE(d_kpt3d != nullptr, "d_kpt3d null");
+    TrainCall tc{d, scene_ws, wp, a, t, g, d_plain, d_geo0, d_geo1, d_tex, nullptr, ws, stream};
+    tc.d_kpt = d_kpt3d; tc.n_kpt = n_kpt;
+    return train_backward_classic(tc, ws_bytes);
 }
 
 extern "C" size_t kpn_render_rays_train_state_bytes(const kpn_scene_desc* d, const kpn_render_args* a) {
@@ -404,8 +437,16 @@ extern "C" int kpn_render_rays_train_backward_kept(const kpn_scene_desc* d, cons
                                                    size_t state_bytes, void* ws, size_t ws_bytes, void* stream) {
     KPN_REQUIRE(state != nullptr, "state null");
     TrainCall tc{d, scene_ws, wp, a, t, g, d_plain, d_geo0, d_geo1, d_tex, state, ws, stream};
-    return tc.run(state_bytes, ws_bytes, false, [&](const TrainChunk& c) {
-        const int e = tc.reverse(c, c.coarse);
-        return e ? e : tc.reverse(c, c.fine);
-    });
+    return train_backward_kept(tc, state_bytes, ws_bytes);
+}
+extern "C" int kpn_render_rays_train_backward_kept_kpt(const kpn_scene_desc* d, const void* scene_ws, const float* wp,
+                                                       const kpn_render_args* a, const kpn_train_args* t, const kpn_render_grads* g,
+                                                       float* d_plain, float* d_geo0, float* d_geo1, float* d_tex, float* d_kpt3d,
+                                                       int32_t n_kpt, void* state, size_t state_bytes, void* ws, size_t ws_bytes,
+                                                       void* stream) {
+    KPN_REQUIRE(state != nullptr, "state null");
+    KPN_REQUIRE(d_kpt3d != nullptr, "d_kpt3d null");
+    TrainCall tc{d, scene_ws, wp, a, t, g, d_plain, d_geo0, d_geo1, d_tex, state, ws, stream};
+    tc.d_kpt = d_kpt3d; tc.n_kpt = n_kpt;
+    return train_backward_kept(tc, state_bytes, ws_bytes);
 }

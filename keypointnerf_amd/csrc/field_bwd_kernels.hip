@@ -15,8 +15,9 @@
 //   k_weight_grad  : dW[o][f] += sum_rows dY[row][o] X[row][f], db[o] += sum_rows dY[row][o] — the
 //                reduction over rows is the K dimension of v_mfma_f32_32x32x2_f32; row-major dumps are
 //                exactly its A/B operand layout (lane = feature, k = row parity), no transposes.
-// The keypoint encoding has no upstream parameters (points and keypoints are inputs), so dX0's first
-// 168 entries are never formed.
+// The keypoint encoding has no upstream parameters, so dX0's first 168 entries are not formed here.  When the caller asks for the
+// gradient with respect to the keypoints (the *_kpt entries), k_kpt_grad (kpt_grad_kernels.hip) forms them per tile from the D0
+// and X0 dumps and reduces them to (n_kpt, 3) at once; the query points stay plain inputs.
 #include "kpn_device.h"
 
 struct kpn_bwd_bufs {

@@ -30,6 +30,7 @@ extern "C" void kpn_internal_launch_geo_rows_pair(int mode, int blocks, void* st
 #endif
 #include "field_bwd_kernels.hip"
 #include "fuse_bwd_kernels.hip"
+#include "kpt_grad_kernels.hip"       // the keypoint gradient, from the dumps of field_bwd_kernels.hip
 #include "vgg_kernels.hip"
 #include "encoder_kernels.hip"
 #include "encoder_split_kernels.hip"   // the stride-1 family on three bf16 pieces (KPN_CONV_BF16X3)

@@ -160,6 +160,12 @@ class _State:
         if "transf" in cam:
             raise NotImplementedError("cam['transf'] (src/model.py:716-718) is not produced by decode_batch and not served")
         self.check_keypoints(sp_data)
+        if torch.is_grad_enabled() and sp_data["kpt3d"].requires_grad:
+            # the reference's eval branch is differentiable in kpt3d (src/spatial.py:76-118); these kernels have no reverse, and a
+            # leaf that asks for a gradient must not silently get none
+            raise NotImplementedError("sp_data['kpt3d'] requires a gradient, which the eval-branch kernels (kpn_render_rays, kpn_query) "
+                                      "cannot provide: the keypoint gradient is served by the stochastic (uniform=False) branch; "
+                                      "detach kpt3d or call under torch.no_grad()")
         return ops.PreparedScene(img, cam, feat_geo, feat_tex, sp_data, fg_mask,
                                  disable_fg_mask=getattr(self.net, "disable_fg_mask", False), sigma=encoder_sigma(self.net))
 
@@ -353,7 +359,7 @@ def install(net, rows_mode=None, native_params=False):
             # the forward — within the training budget only: a whole validation frame rendered with gradients enabled
             # (net.eval() without no_grad) stays differentiable, its backward repeats the forward instead of pinning tens of GB
             bool(torch.is_grad_enabled() and R <= _KEEP_STATE_MAX_RAYS
-                 and (plain.requires_grad or feat_geo[0].requires_grad or feat_tex.requires_grad)))
+                 and (plain.requires_grad or feat_geo[0].requires_grad or feat_tex.requires_grad or sp_data["kpt3d"].requires_grad)))
         out = {}
         for k, v in zip(_OUT_KEYS, res):                            # (1,3,R) / (1,R) in pixel-list order
             out[k] = v.view(1, 3, out_h, out_w) if k.startswith("tex") else v.view(1, out_h, out_w)

@@ -189,6 +189,20 @@ _SIGNATURES = {
     "kpn_render_rays_train_backward": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p, ctypes.POINTER(RenderArgs),
                                                       ctypes.POINTER(TrainArgs), ctypes.POINTER(RenderGrads), c_p, c_p, c_p, c_p,
                                                       c_p, c_sz, c_p]),
+    # the same calls with d_kpt3d (n_kpt, 3) and n_kpt after the last map gradient (include/kpnerf.h)
+    "kpn_geo_rows_backward_workspace_bytes_kpt": (c_sz, [c_i64, c_i32]),
+    "kpn_geo_rows_backward_kpt": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p, c_i64, c_p, ctypes.c_uint32, c_p, c_p, c_p,
+                                                 c_p, c_p, c_i32, c_p, c_sz, c_p]),
+    "kpn_query_backward_workspace_bytes_kpt": (c_sz, [c_i64, c_i32]),
+    "kpn_query_backward_kpt": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p, c_i64, c_p, c_p, c_i32, ctypes.c_uint32, c_p,
+                                              ctypes.c_float, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_sz, c_p]),
+    "kpn_render_rays_train_backward_workspace_bytes_kpt": (c_sz, [ctypes.POINTER(SceneDesc), ctypes.POINTER(RenderArgs)]),
+    "kpn_render_rays_train_backward_kpt": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p, ctypes.POINTER(RenderArgs),
+                                                          ctypes.POINTER(TrainArgs), ctypes.POINTER(RenderGrads), c_p, c_p, c_p, c_p,
+                                                          c_p, c_i32, c_p, c_sz, c_p]),
+    "kpn_render_rays_train_backward_kept_kpt": (ctypes.c_int, [ctypes.POINTER(SceneDesc), c_p, c_p, ctypes.POINTER(RenderArgs),
+                                                               ctypes.POINTER(TrainArgs), ctypes.POINTER(RenderGrads), c_p, c_p, c_p,
+                                                               c_p, c_p, c_i32, c_p, c_sz, c_p, c_sz, c_p]),
     "kpn_set_geo_rows_mode": (ctypes.c_int, [c_i32]),
     "kpn_get_geo_rows_mode": (ctypes.c_int, []),
     "kpn_packed_f16_range_check": (ctypes.c_int, [c_p, c_p, c_p]),

@@ -306,17 +306,24 @@ def _grad_buffers(scene, device, with_tex):
             *(torch.zeros(scene.n_views, h, w, c, dtype=_f32, device=device) for h, w, c in maps))
 
 
+def _kpt_grad_buffer(scene, device):
+    """the zeroed (n_kpt, 3) accumulator of the keypoint gradient (the *_kpt entries of include/kpnerf.h)"""
+    return torch.zeros(scene.n_kpt, 3, dtype=_f32, device=device)
+
+
 def _nchw(d_plain, *d_maps):
     """what the backward wrappers return: the map gradients as NCHW views of the channels-last accumulators"""
     return (d_plain, *(m.permute(0, 3, 1, 2) for m in d_maps))
 
 
-def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF):
+def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF, want_kpt=False):
     """Reverse pass of the per-(point,view) geometry rows (kpn_geo_rows_backward): MLPUNet.layers1 and the
     feat_geo gathers (reference src/utils.py:691-716, src/model.py:763-765).
     pts (1,N,3) or (N,3); d_x (N,V,64) = d loss / d layers1-output.  Returns (d_plain, d_geo0, d_geo1):
     d_plain flat like weights.flatten_plain (feed it to weights.plain_grads_to_state_dict), d_geo* shaped
-    like feat_geo[*] (NCHW views of the channels-last accumulators)."""
+    like feat_geo[*] (NCHW views of the channels-last accumulators).
+    want_kpt: also the gradient with respect to sp_data["kpt3d"] (kpn_geo_rows_backward_kpt; reference src/spatial.py:76-118), as
+    (1, n_kpt, 3) after the other results."""
     L = kl.get_library()
     p = _dev(pts, "pts").reshape(-1, 3)
     N, V = p.shape[0], scene.n_views
@@ -325,12 +332,18 @@ def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF):
         raise ValueError(f"d_x must be (N, V, 64) = {(N, V, 64)}, got {tuple(g.shape)}")
     d = scene.desc
     d_plain, d_g0, d_g1 = _grad_buffers(scene, p.device, with_tex=False)
-    if N > 0:
+    d_kpt = _kpt_grad_buffer(scene, p.device) if want_kpt else None
+    if N > 0 and want_kpt:
+        nb = L.kpn_geo_rows_backward_workspace_bytes_kpt(N, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
+        L.check(L.kpn_geo_rows_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
+                                            _p(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_kpt), scene.n_kpt, _p(ws), nb, _stream()))
+    elif N > 0:
         nb = L.kpn_geo_rows_backward_workspace_bytes(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
         L.check(L.kpn_geo_rows_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
                                         _p(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(ws), nb, _stream()))
-    return _nchw(d_plain, d_g0, d_g1)
+    return _nchw(d_plain, d_g0, d_g1) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
 
 
 def query_backward_geometry(scene, weights, pts, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0):
@@ -358,12 +371,13 @@ def query_backward_geometry(scene, weights, pts, d_out, mode=1, keep_mask=0xFFFF
     return _nchw(d_plain, d_g0, d_g1)
 
 
-def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0):
+def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0, want_kpt=False):
     """Reverse pass of the whole field evaluation incl. the colour head (kpn_query_backward):
     what loss.backward() does for KeypointNeRF.query + eval_func in training_step (reference src/model.py:128-155).
     pts, view (N,3)/(1,N,3); d_out (N,5) = d loss / d [sigma, sdf, r, g, b] (mode 1) or d [sdf_raw, rad, r, g, b] (mode 0).
     Returns (d_plain, d_geo0, d_geo1, d_tex): flat effective-parameter gradient (weights.plain_grads_to_state_dict maps it
-    to weight_g / weight_v / bias / ani_al) and the feature-map gradients shaped like feat_geo[0], feat_geo[1], feat_tex."""
+    to weight_g / weight_v / bias / ani_al) and the feature-map gradients shaped like feat_geo[0], feat_geo[1], feat_tex.
+    want_kpt: also d loss / d sp_data["kpt3d"] as (1, n_kpt, 3), last (kpn_query_backward_kpt)."""
     L = kl.get_library()
     p, vw = _dev(pts, "pts").reshape(-1, 3), _dev(view, "view").reshape(-1, 3)
     N, V = p.shape[0], scene.n_views
@@ -375,13 +389,20 @@ def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFF
         raise ValueError("noise must have one value per point")
     d = scene.desc
     d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, p.device, with_tex=True)
-    if N > 0:
+    d_kpt = _kpt_grad_buffer(scene, p.device) if want_kpt else None
+    if N > 0 and want_kpt:
+        nb = L.kpn_query_backward_workspace_bytes_kpt(N, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
+        L.check(L.kpn_query_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
+                                         int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g),
+                                         _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt), scene.n_kpt, _p(ws), nb, _stream()))
+    elif N > 0:
         nb = L.kpn_query_backward_workspace_bytes(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
         L.check(L.kpn_query_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
                                      int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g), _p(d_plain),
                                      _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
-    return _nchw(d_plain, d_g0, d_g1, d_tx)
+    return _nchw(d_plain, d_g0, d_g1, d_tx) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
 
 
 class RenderPlan:
@@ -516,12 +537,14 @@ def render_rays_train(scene, weights, cam_tar, bounds, pix, u_coarse, u_fine, ke
 
 def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u_fine, keep_coarse, keep_fine, grads,
                                noise_coarse=None, noise_fine=None, rand_noise_std=0.0, n_coarse=64, n_fine=64, chunk_rays=0,
-                               state=None):
+                               state=None, want_kpt=False):
     """loss.backward() through render_rays_train (kpn_render_rays_train_backward): `grads` maps output names
     ('tex_fg', 'depth', 'alpha', 'tex_fg_fine', 'depth_fine', 'alpha_fine', 'sdf') to the gradients of those outputs,
     shaped like them ((1,3,R) / (1,R)); missing keys are zero.  Same other arguments as the forward call.
     `state`: the tensor render_rays_train(..., keep_state=True) returned for the SAME arguments (kpn_render_rays_train_
-    backward_kept: the forward is not repeated).  Returns (d_plain, d_geo0, d_geo1, d_tex) as ops.query_backward."""
+    backward_kept: the forward is not repeated).  Returns (d_plain, d_geo0, d_geo1, d_tex) as ops.query_backward.
+    want_kpt: also d loss / d sp_data["kpt3d"] as (1, n_kpt, 3), last (kpn_render_rays_train_backward[_kept]_kpt): the coarse and the
+    fine pass both add to it."""
     L = kl.get_library()
     R = pix.shape[0]
     t, draws = _train_args(R, pix, u_coarse, u_fine, keep_coarse, keep_fine, noise_coarse, noise_fine, rand_noise_std, n_coarse, n_fine)
@@ -540,11 +563,22 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
     d = scene.desc
     dv = pix.device
     d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, dv, with_tex=True)
-    nb = L.kpn_render_rays_train_backward_workspace_bytes(ctypes.byref(d), ctypes.byref(a))
+    d_kpt = _kpt_grad_buffer(scene, dv) if want_kpt else None
+    nb = (L.kpn_render_rays_train_backward_workspace_bytes_kpt if want_kpt else L.kpn_render_rays_train_backward_workspace_bytes)(
+        ctypes.byref(d), ctypes.byref(a))
     if nb == 0:
         raise kl.KpnError("bad render arguments: " + L.kpn_last_error().decode())
     ws = torch.empty(nb, dtype=torch.uint8, device=dv)
-    if state is not None and state.numel() > 0:
+    kept = state is not None and state.numel() > 0
+    if want_kpt and kept:
+        L.check(L.kpn_render_rays_train_backward_kept_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
+                                                          ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt),
+                                                          scene.n_kpt, _p(state), state.numel(), _p(ws), nb, _stream()))
+    elif want_kpt:
+        L.check(L.kpn_render_rays_train_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
+                                                     ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt), scene.n_kpt,
+                                                     _p(ws), nb, _stream()))
+    elif kept:
         L.check(L.kpn_render_rays_train_backward_kept(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
                                                       ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(state),
                                                       state.numel(), _p(ws), nb, _stream()))
@@ -552,7 +586,7 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
         L.check(L.kpn_render_rays_train_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
                                                  ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
     # no host sync (stream-ordered reuse of freed blocks, see render_rays_train)
-    return _nchw(d_plain, d_g0, d_g1, d_tx)
+    return _nchw(d_plain, d_g0, d_g1, d_tx) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
 
 
 def set_geo_rows_mode(mode):

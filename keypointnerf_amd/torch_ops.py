@@ -333,6 +333,35 @@ def _(plain, geo0, geo1, tex, *rest):
     return torch.empty_like(plain), torch.empty_like(geo0), torch.empty_like(geo1), torch.empty_like(tex)
 
 
+@_lib.custom_op("kpnerf::render_rays_train_backward_kpt", mutates_args=(), device_types="cuda")
+def render_rays_train_backward_kpt(plain: torch.Tensor, geo0: torch.Tensor, geo1: torch.Tensor, tex: torch.Tensor, img: torch.Tensor,
+                                   KRT: torch.Tensor, extrin: torch.Tensor, kpt3d: torch.Tensor, fg_mask: Optional[torch.Tensor],
+                                   scene_scalars: List[float], K: torch.Tensor, RT: torch.Tensor, bounds: torch.Tensor,
+                                   znear: float, zfar: float, pix: torch.Tensor, u_c: torch.Tensor, u_f: torch.Tensor,
+                                   noise_c: Optional[torch.Tensor], noise_f: Optional[torch.Tensor], keep_c: int, keep_f: int,
+                                   noise_std: float, n_coarse: int, n_fine: int, d_tex_fg: Optional[torch.Tensor],
+                                   d_depth: Optional[torch.Tensor], d_alpha: Optional[torch.Tensor],
+                                   d_tex_fg_fine: Optional[torch.Tensor], d_depth_fine: Optional[torch.Tensor],
+                                   d_alpha_fine: Optional[torch.Tensor], d_sdf: Optional[torch.Tensor],
+                                   state: Optional[torch.Tensor] = None
+                                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """render_rays_train_backward with a fifth result, d loss / d kpt3d shaped like kpt3d (kpn_render_rays_train_backward[_kept]_kpt;
+    what autograd derives through SpatialEncoder.forward, reference src/spatial.py:76-118)."""
+    scene, w = _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, list(scene_scalars))
+    grads = dict(zip(_OUT_KEYS, (d_tex_fg, d_depth, d_alpha, d_tex_fg_fine, d_depth_fine, d_alpha_fine, d_sdf)))
+    d_plain, d_g0, d_g1, d_tx, d_kpt = ops.render_rays_train_backward(
+        scene, w, {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, pix, u_c, u_f, keep_c, keep_f, grads,
+        noise_coarse=noise_c, noise_fine=noise_f, rand_noise_std=noise_std, n_coarse=n_coarse, n_fine=n_fine, state=state,
+        want_kpt=True)
+    _iter_cache_clear()
+    return d_plain, d_g0.contiguous(), d_g1.contiguous(), d_tx.contiguous(), d_kpt.reshape(kpt3d.shape).to(kpt3d.dtype)
+
+
+@render_rays_train_backward_kpt.register_fake
+def _(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, *rest):
+    return torch.empty_like(plain), torch.empty_like(geo0), torch.empty_like(geo1), torch.empty_like(tex), torch.empty_like(kpt3d)
+
+
 def _train_setup(ctx, inputs, output):
     # tensors go through save_for_backward, so that autograd's version-counter check raises if one of them (feature maps, the
     # flat parameters, the draws) or the kept pass state is modified in place between forward and backward — the state is only
@@ -351,6 +380,10 @@ def _train_bwd(ctx, *grads):
     for i, t in zip(ctx.tensor_slots, saved[:-1]):
         args[i] = t
     state = saved[-1] if saved[-1].numel() > 0 else None
+    if ctx.needs_input_grad[7]:                                      # kpt3d (reference: autograd through src/spatial.py:76-118)
+        d_plain, d_g0, d_g1, d_tx, d_kpt = torch.ops.kpnerf.render_rays_train_backward_kpt(
+            *args, *[None if g is None else g.contiguous() for g in grads[:7]], state)
+        return (d_plain, d_g0, d_g1, d_tx, None, None, None, d_kpt) + (None,) * (ctx.n_inputs - 8)
     d_plain, d_g0, d_g1, d_tx = torch.ops.kpnerf.render_rays_train_backward(
         *args, *[None if g is None else g.contiguous() for g in grads[:7]], state)
     return (d_plain, d_g0, d_g1, d_tx) + (None,) * (ctx.n_inputs - 4)
