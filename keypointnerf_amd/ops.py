@@ -306,9 +306,14 @@ def _grad_buffers(scene, device, with_tex):
             *(torch.zeros(scene.n_views, h, w, c, dtype=_f32, device=device) for h, w, c in maps))
 
 
-def _kpt_grad_buffer(scene, device):
-    """the zeroed (n_kpt, 3) accumulator of the keypoint gradient (the *_kpt entries of include/kpnerf.h)"""
-    return torch.zeros(scene.n_kpt, 3, dtype=_f32, device=device)
+def _kpt_variant(scene, device, want_kpt):
+    """what want_kpt changes in a backward call (the *_kpt entries of include/kpnerf.h): the suffix of the entry points' names, the result
+    that follows the others - the zeroed (n_kpt, 3) accumulator of the keypoint gradient as (1, n_kpt, 3) - and the (d_kpt, n_kpt)
+    arguments that follow the map gradients"""
+    if not want_kpt:
+        return "", (), ()
+    d_kpt = torch.zeros(scene.n_kpt, 3, dtype=_f32, device=device)
+    return "_kpt", (d_kpt.view(1, -1, 3),), (_p(d_kpt), scene.n_kpt)
 
 
 def _nchw(d_plain, *d_maps):
@@ -332,18 +337,13 @@ def geo_rows_backward(scene, weights, pts, d_x, keep_mask=0xFFFFFFFF, want_kpt=F
         raise ValueError(f"d_x must be (N, V, 64) = {(N, V, 64)}, got {tuple(g.shape)}")
     d = scene.desc
     d_plain, d_g0, d_g1 = _grad_buffers(scene, p.device, with_tex=False)
-    d_kpt = _kpt_grad_buffer(scene, p.device) if want_kpt else None
-    if N > 0 and want_kpt:
-        nb = L.kpn_geo_rows_backward_workspace_bytes_kpt(N, V)
+    sfx, d_kpt, kpt_args = _kpt_variant(scene, p.device, want_kpt)
+    if N > 0:                   # kpn_geo_rows_backward or kpn_geo_rows_backward_kpt, each with its _workspace_bytes
+        nb = getattr(L, "kpn_geo_rows_backward_workspace_bytes" + sfx)(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
-        L.check(L.kpn_geo_rows_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
-                                            _p(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_kpt), scene.n_kpt, _p(ws), nb, _stream()))
-    elif N > 0:
-        nb = L.kpn_geo_rows_backward_workspace_bytes(N, V)
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
-        L.check(L.kpn_geo_rows_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
-                                        _p(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(ws), nb, _stream()))
-    return _nchw(d_plain, d_g0, d_g1) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
+        L.check(getattr(L, "kpn_geo_rows_backward" + sfx)(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), int(keep_mask) & 0xFFFFFFFF,
+                                                          _p(g), _p(d_plain), _p(d_g0), _p(d_g1), *kpt_args, _p(ws), nb, _stream()))
+    return _nchw(d_plain, d_g0, d_g1) + d_kpt
 
 
 def query_backward_geometry(scene, weights, pts, d_out, mode=1, keep_mask=0xFFFFFFFF, noise=None, noise_std=0.0):
@@ -389,20 +389,14 @@ def query_backward(scene, weights, pts, view, d_out, mode=1, keep_mask=0xFFFFFFF
         raise ValueError("noise must have one value per point")
     d = scene.desc
     d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, p.device, with_tex=True)
-    d_kpt = _kpt_grad_buffer(scene, p.device) if want_kpt else None
-    if N > 0 and want_kpt:
-        nb = L.kpn_query_backward_workspace_bytes_kpt(N, V)
+    sfx, d_kpt, kpt_args = _kpt_variant(scene, p.device, want_kpt)
+    if N > 0:                   # kpn_query_backward or kpn_query_backward_kpt, each with its _workspace_bytes
+        nb = getattr(L, "kpn_query_backward_workspace_bytes" + sfx)(N, V)
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
-        L.check(L.kpn_query_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
-                                         int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g),
-                                         _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt), scene.n_kpt, _p(ws), nb, _stream()))
-    elif N > 0:
-        nb = L.kpn_query_backward_workspace_bytes(N, V)
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=p.device)
-        L.check(L.kpn_query_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
-                                     int(keep_mask) & 0xFFFFFFFF, None if nz is None else _p(nz), float(noise_std), _p(g), _p(d_plain),
-                                     _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
-    return _nchw(d_plain, d_g0, d_g1, d_tx) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
+        L.check(getattr(L, "kpn_query_backward" + sfx)(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), N, _p(p), _p(vw), int(mode),
+                                                       int(keep_mask) & 0xFFFFFFFF, _p(nz), float(noise_std), _p(g), _p(d_plain),
+                                                       _p(d_g0), _p(d_g1), _p(d_tx), *kpt_args, _p(ws), nb, _stream()))
+    return _nchw(d_plain, d_g0, d_g1, d_tx) + d_kpt
 
 
 class RenderPlan:
@@ -563,30 +557,19 @@ def render_rays_train_backward(scene, weights, cam_tar, bounds, pix, u_coarse, u
     d = scene.desc
     dv = pix.device
     d_plain, d_g0, d_g1, d_tx = _grad_buffers(scene, dv, with_tex=True)
-    d_kpt = _kpt_grad_buffer(scene, dv) if want_kpt else None
-    nb = (L.kpn_render_rays_train_backward_workspace_bytes_kpt if want_kpt else L.kpn_render_rays_train_backward_workspace_bytes)(
-        ctypes.byref(d), ctypes.byref(a))
+    sfx, d_kpt, kpt_args = _kpt_variant(scene, dv, want_kpt)
+    nb = getattr(L, "kpn_render_rays_train_backward_workspace_bytes" + sfx)(ctypes.byref(d), ctypes.byref(a))
     if nb == 0:
         raise kl.KpnError("bad render arguments: " + L.kpn_last_error().decode())
     ws = torch.empty(nb, dtype=torch.uint8, device=dv)
+    # one of kpn_render_rays_train_backward, kpn_render_rays_train_backward_kpt, kpn_render_rays_train_backward_kept and
+    # kpn_render_rays_train_backward_kept_kpt; the _kept entries take (state, state_bytes) in front of the workspace
     kept = state is not None and state.numel() > 0
-    if want_kpt and kept:
-        L.check(L.kpn_render_rays_train_backward_kept_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
-                                                          ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt),
-                                                          scene.n_kpt, _p(state), state.numel(), _p(ws), nb, _stream()))
-    elif want_kpt:
-        L.check(L.kpn_render_rays_train_backward_kpt(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
-                                                     ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(d_kpt), scene.n_kpt,
-                                                     _p(ws), nb, _stream()))
-    elif kept:
-        L.check(L.kpn_render_rays_train_backward_kept(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
-                                                      ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(state),
-                                                      state.numel(), _p(ws), nb, _stream()))
-    else:
-        L.check(L.kpn_render_rays_train_backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t),
-                                                 ctypes.byref(g), _p(d_plain), _p(d_g0), _p(d_g1), _p(d_tx), _p(ws), nb, _stream()))
+    backward = getattr(L, "kpn_render_rays_train_backward" + ("_kept" if kept else "") + sfx)
+    L.check(backward(ctypes.byref(d), _p(scene.ws), _p(weights.tensor), ctypes.byref(a), ctypes.byref(t), ctypes.byref(g), _p(d_plain),
+                     _p(d_g0), _p(d_g1), _p(d_tx), *kpt_args, *((_p(state), state.numel()) if kept else ()), _p(ws), nb, _stream()))
     # no host sync (stream-ordered reuse of freed blocks, see render_rays_train)
-    return _nchw(d_plain, d_g0, d_g1, d_tx) + ((d_kpt.view(1, -1, 3),) if want_kpt else ())
+    return _nchw(d_plain, d_g0, d_g1, d_tx) + d_kpt
 
 
 def set_geo_rows_mode(mode):
@@ -1683,23 +1666,9 @@ def hg_filter_shapes(cfg):
 
 
 def hg_filter_state_floats(N, H, W, cfg):
-    """kpn_hg_filter_state_floats, restated from the layout include/kpnerf.h documents (the fake kernels and the tests use it)"""
-    _, c_stem, c2, c3, c4, depth, c_hd, _, _ = (int(v) for v in cfg)
-    stats = lambda C: 2 * N * C + 2 * N * min(32, C)  # noqa: E731
-
-    def block(cin, cout, P):
-        legs, win, _ = _block_widths(cin, cout)
-        return P * (3 * cout // 4) + sum(stats(win[i]) for i in range(legs))
-
-    P1, P2 = N * (H // 2) * (W // 2), N * (H // 4) * (W // 4)
-    total = 2 * P1 * c_stem + stats(c_stem) + block(c_stem, c2, P1) + P1 * c2 + N * H * W * c_hd + stats(c_hd)
-    total += P2 * c2 + block(c2, c3, P2) + P2 * c3 + block(c3, c4, P2) + P2 * c4
-    for k in range(depth):
-        P, Pl = P2 >> (2 * k), P2 >> (2 * k + 2)
-        total += block(c4, c4, P) + P * c4 + Pl * c4 + block(c4, c4, Pl) + Pl * c4 + block(c4, c4, Pl)      # b1, hg, low, b2, low1, b3
-    Pl = P2 >> (2 * depth)
-    total += block(c4, c4, Pl) + Pl * c4                                                                     # b2_plus and its output
-    return total + block(c4, c4, P2) + 2 * P2 * c4 + stats(c4)
+    """the floats of hg_filter_forward's state for this input size: the library's own answer (kpn_hg_filter_state_floats, a host-only
+    query; 0 for a network it does not serve).  The layout is documented in include/kpnerf.h."""
+    return kl.get_library().kpn_hg_filter_state_floats(ctypes.byref(_hg_filter_desc(N, H, W, cfg, 1e-5)))
 
 
 def _hg_filter_tensors(tensors, cfg, device):

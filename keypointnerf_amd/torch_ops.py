@@ -305,6 +305,25 @@ def _(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scene_scalars, K
     return f(1, 3, R), f(1, R), f(1, R), f(1, 3, R), f(1, R), f(1, R), f(1, R), geo0.new_empty(0, dtype=torch.uint8)
 
 
+def _train_backward(want_kpt, *args):
+    """the body of the two backward operators below over their 33 arguments: the 25 of the forward, the seven output gradients, the pass state"""
+    (plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scene_scalars, K, RT, bounds, znear, zfar, pix, u_c, u_f, noise_c, noise_f,
+     keep_c, keep_f, noise_std, n_coarse, n_fine), d_outs, state = args[:25], args[25:32], args[32]
+    scene, w = _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, list(scene_scalars))
+    d_plain, d_g0, d_g1, d_tx, *d_kpt = ops.render_rays_train_backward(
+        scene, w, {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, pix, u_c, u_f, keep_c, keep_f, dict(zip(_OUT_KEYS, d_outs)),
+        noise_coarse=noise_c, noise_fine=noise_f, rand_noise_std=noise_std, n_coarse=n_coarse, n_fine=n_fine, state=state,
+        want_kpt=want_kpt)
+    _iter_cache_clear()   # stream-ordered: the launches above hold nothing but device pointers the allocator keeps valid for them
+    return (d_plain, d_g0.contiguous(), d_g1.contiguous(), d_tx.contiguous()) + tuple(g.reshape(kpt3d.shape).to(kpt3d.dtype) for g in d_kpt)
+
+
+def _train_backward_fake(n_results):
+    def fake(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, *rest, **named):
+        return tuple(torch.empty_like(t) for t in (plain, geo0, geo1, tex, kpt3d)[:n_results])
+    return fake
+
+
 @_lib.custom_op("kpnerf::render_rays_train_backward", mutates_args=(), device_types="cuda")
 def render_rays_train_backward(plain: torch.Tensor, geo0: torch.Tensor, geo1: torch.Tensor, tex: torch.Tensor, img: torch.Tensor,
                                KRT: torch.Tensor, extrin: torch.Tensor, kpt3d: torch.Tensor, fg_mask: Optional[torch.Tensor],
@@ -319,18 +338,12 @@ def render_rays_train_backward(plain: torch.Tensor, geo0: torch.Tensor, geo1: to
                                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """loss.backward() through render_rays_train (kpn_render_rays_train_backward) -> (d_plain, d_geo0, d_geo1, d_tex),
     the map gradients NCHW like the maps."""
-    scene, w = _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, list(scene_scalars))
-    grads = dict(zip(_OUT_KEYS, (d_tex_fg, d_depth, d_alpha, d_tex_fg_fine, d_depth_fine, d_alpha_fine, d_sdf)))
-    d_plain, d_g0, d_g1, d_tx = ops.render_rays_train_backward(
-        scene, w, {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, pix, u_c, u_f, keep_c, keep_f, grads,
-        noise_coarse=noise_c, noise_fine=noise_f, rand_noise_std=noise_std, n_coarse=n_coarse, n_fine=n_fine, state=state)
-    _iter_cache_clear()   # stream-ordered: the launches above hold nothing but device pointers the allocator keeps valid for them
-    return d_plain, d_g0.contiguous(), d_g1.contiguous(), d_tx.contiguous()
+    return _train_backward(False, plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scene_scalars, K, RT, bounds, znear, zfar, pix,
+                           u_c, u_f, noise_c, noise_f, keep_c, keep_f, noise_std, n_coarse, n_fine, d_tex_fg, d_depth, d_alpha,
+                           d_tex_fg_fine, d_depth_fine, d_alpha_fine, d_sdf, state)
 
 
-@render_rays_train_backward.register_fake
-def _(plain, geo0, geo1, tex, *rest):
-    return torch.empty_like(plain), torch.empty_like(geo0), torch.empty_like(geo1), torch.empty_like(tex)
+render_rays_train_backward.register_fake(_train_backward_fake(4))
 
 
 @_lib.custom_op("kpnerf::render_rays_train_backward_kpt", mutates_args=(), device_types="cuda")
@@ -347,19 +360,12 @@ def render_rays_train_backward_kpt(plain: torch.Tensor, geo0: torch.Tensor, geo1
                                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """render_rays_train_backward with a fifth result, d loss / d kpt3d shaped like kpt3d (kpn_render_rays_train_backward[_kept]_kpt;
     what autograd derives through SpatialEncoder.forward, reference src/spatial.py:76-118)."""
-    scene, w = _scene_and_weights(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, list(scene_scalars))
-    grads = dict(zip(_OUT_KEYS, (d_tex_fg, d_depth, d_alpha, d_tex_fg_fine, d_depth_fine, d_alpha_fine, d_sdf)))
-    d_plain, d_g0, d_g1, d_tx, d_kpt = ops.render_rays_train_backward(
-        scene, w, {"K": K, "RT": RT, "znear": znear, "zfar": zfar}, bounds, pix, u_c, u_f, keep_c, keep_f, grads,
-        noise_coarse=noise_c, noise_fine=noise_f, rand_noise_std=noise_std, n_coarse=n_coarse, n_fine=n_fine, state=state,
-        want_kpt=True)
-    _iter_cache_clear()
-    return d_plain, d_g0.contiguous(), d_g1.contiguous(), d_tx.contiguous(), d_kpt.reshape(kpt3d.shape).to(kpt3d.dtype)
+    return _train_backward(True, plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, fg_mask, scene_scalars, K, RT, bounds, znear, zfar, pix,
+                           u_c, u_f, noise_c, noise_f, keep_c, keep_f, noise_std, n_coarse, n_fine, d_tex_fg, d_depth, d_alpha,
+                           d_tex_fg_fine, d_depth_fine, d_alpha_fine, d_sdf, state)
 
 
-@render_rays_train_backward_kpt.register_fake
-def _(plain, geo0, geo1, tex, img, KRT, extrin, kpt3d, *rest):
-    return torch.empty_like(plain), torch.empty_like(geo0), torch.empty_like(geo1), torch.empty_like(tex), torch.empty_like(kpt3d)
+render_rays_train_backward_kpt.register_fake(_train_backward_fake(5))
 
 
 def _train_setup(ctx, inputs, output):
@@ -380,13 +386,10 @@ def _train_bwd(ctx, *grads):
     for i, t in zip(ctx.tensor_slots, saved[:-1]):
         args[i] = t
     state = saved[-1] if saved[-1].numel() > 0 else None
-    if ctx.needs_input_grad[7]:                                      # kpt3d (reference: autograd through src/spatial.py:76-118)
-        d_plain, d_g0, d_g1, d_tx, d_kpt = torch.ops.kpnerf.render_rays_train_backward_kpt(
-            *args, *[None if g is None else g.contiguous() for g in grads[:7]], state)
-        return (d_plain, d_g0, d_g1, d_tx, None, None, None, d_kpt) + (None,) * (ctx.n_inputs - 8)
-    d_plain, d_g0, d_g1, d_tx = torch.ops.kpnerf.render_rays_train_backward(
-        *args, *[None if g is None else g.contiguous() for g in grads[:7]], state)
-    return (d_plain, d_g0, d_g1, d_tx) + (None,) * (ctx.n_inputs - 4)
+    # kpt3d needs a gradient (reference: autograd through src/spatial.py:76-118): the operator with the fifth result
+    op = torch.ops.kpnerf.render_rays_train_backward_kpt if ctx.needs_input_grad[7] else torch.ops.kpnerf.render_rays_train_backward
+    d_plain, d_g0, d_g1, d_tx, *d_kpt = op(*args, *[None if g is None else g.contiguous() for g in grads[:7]], state)
+    return (d_plain, d_g0, d_g1, d_tx, None, None, None, *d_kpt) + (None,) * (ctx.n_inputs - 7 - len(d_kpt))
 
 
 render_rays_train.register_autograd(_train_bwd, setup_context=_train_setup)
@@ -498,10 +501,14 @@ def fold_params_norms(tensors: List[torch.Tensor]) -> Tuple[torch.Tensor, torch.
     return ops.fold_params(tensors)
 
 
-@fold_params_norms.register_fake
-def _(tensors):
+# The fake kernels, the setup context and the autograd backward serve the (n_kpt, sp_level) twins further down as well: ``shape`` is
+# their two trailing arguments, or nothing.
+def _fold_norms_fake(tensors, n_kpt=None, sp_level=None):
     L = kl.get_library()
     return tensors[0].new_empty(L.kpn_plain_weight_floats()), tensors[0].new_empty(L.kpn_fold_norm_floats())
+
+
+fold_params_norms.register_fake(_fold_norms_fake)
 
 
 @_lib.custom_op("kpnerf::fold_params_backward", mutates_args=(), device_types="cuda")
@@ -510,24 +517,30 @@ def fold_params_backward(tensors: List[torch.Tensor], norms: torch.Tensor, d_pla
     return ops.fold_params_backward(tensors, norms, d_plain)
 
 
-@fold_params_backward.register_fake
-def _(tensors, norms, d_plain):
+def _fold_backward_fake(tensors, norms, d_plain, n_kpt=None, sp_level=None):
     return [torch.empty_like(t) for t in tensors]
 
 
+fold_params_backward.register_fake(_fold_backward_fake)
+
+
 def _fold_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[0], output[1])
+    tensors, *ctx.shape = inputs
+    ctx.save_for_backward(*tensors, output[1])
     ctx.set_materialize_grads(False)
 
 
-def _fold_bwd(ctx, d_plain, _d_norms):
-    *tensors, norms = ctx.saved_tensors
-    if d_plain is None:
-        return (None,)
-    return (torch.ops.kpnerf.fold_params_backward(list(tensors), norms, d_plain.contiguous()),)
+def _fold_autograd(backward_op):
+    def bwd(ctx, d_plain, _d_norms):
+        *tensors, norms = ctx.saved_tensors
+        nothing = (None,) * len(ctx.shape)
+        if d_plain is None:
+            return (None,) + nothing
+        return (backward_op(list(tensors), norms, d_plain.contiguous(), *ctx.shape),) + nothing
+    return bwd
 
 
-fold_params_norms.register_autograd(_fold_bwd, setup_context=_fold_setup)
+fold_params_norms.register_autograd(_fold_autograd(torch.ops.kpnerf.fold_params_backward), setup_context=_fold_setup)
 
 # torch.ops.kpnerf.fold_params(tensors) -> plain: fold_params_norms without the side buffer; it decomposes into that operator,
 # whose autograd formula serves it
@@ -577,10 +590,7 @@ def fold_params_norms_shape(tensors: List[torch.Tensor], n_kpt: int, sp_level: i
     return ops.fold_params(tensors, shape=(n_kpt, sp_level))
 
 
-@fold_params_norms_shape.register_fake
-def _(tensors, n_kpt, sp_level):
-    L = kl.get_library()
-    return tensors[0].new_empty(L.kpn_plain_weight_floats()), tensors[0].new_empty(L.kpn_fold_norm_floats())
+fold_params_norms_shape.register_fake(_fold_norms_fake)
 
 
 @_lib.custom_op("kpnerf::fold_params_backward_shape", mutates_args=(), device_types="cuda")
@@ -590,25 +600,8 @@ def fold_params_backward_shape(tensors: List[torch.Tensor], norms: torch.Tensor,
     return ops.fold_params_backward(tensors, norms, d_plain, shape=(n_kpt, sp_level))
 
 
-@fold_params_backward_shape.register_fake
-def _(tensors, norms, d_plain, n_kpt, sp_level):
-    return [torch.empty_like(t) for t in tensors]
-
-
-def _fold_shape_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[0], output[1])
-    ctx.shape = (inputs[1], inputs[2])
-    ctx.set_materialize_grads(False)
-
-
-def _fold_shape_bwd(ctx, d_plain, _d_norms):
-    *tensors, norms = ctx.saved_tensors
-    if d_plain is None:
-        return None, None, None
-    return torch.ops.kpnerf.fold_params_backward_shape(list(tensors), norms, d_plain.contiguous(), *ctx.shape), None, None
-
-
-fold_params_norms_shape.register_autograd(_fold_shape_bwd, setup_context=_fold_shape_setup)
+fold_params_backward_shape.register_fake(_fold_backward_fake)
+fold_params_norms_shape.register_autograd(_fold_autograd(torch.ops.kpnerf.fold_params_backward_shape), setup_context=_fold_setup)
 _fragment.define("fold_params_shape(Tensor[] tensors, int n_kpt, int sp_level) -> Tensor")
 _fragment.impl("fold_params_shape", lambda tensors, n_kpt, sp_level: torch.ops.kpnerf.fold_params_norms_shape(tensors, n_kpt, sp_level)[0],
                "CompositeImplicitAutograd")
@@ -668,7 +661,7 @@ tex_encode.register_autograd(_encoder_bwd, setup_context=_encoder_no_autograd)
 # weights stay resident (least recently used first out); conv2d_cache_clear() drops them all.
 class _ConvPackCache:
     lock = threading.Lock()
-    entries = collections.OrderedDict()     # data_ptr -> (key, weight, packed)
+    entries = collections.OrderedDict()     # data_ptr -> (key, weights, packed)
     limit = 512
     hits = misses = 0                       # observable by the tests
 
@@ -678,23 +671,27 @@ def conv2d_cache_clear():
         _ConvPackCache.entries.clear()
 
 
-def _conv_packed(weight, pack, tag):
-    """the packed copies of a weight, made by ``pack(weight)``; ``tag`` (hashable) tells the families and their kinds apart in the key"""
-    if weight.is_inference():
-        return pack(weight)
-    key = _tensor_key(weight) + (tag,)
-    C = _ConvPackCache
+def _packed(C, weights, tag, pack):
+    """``pack()``, the packed copies of ``weights``, kept in the cache ``C`` (this one and the one of kpnerf::res_encoder below) in the
+    slot of the first weight's storage address.  _tensor_key of every weight and ``tag`` (hashable: the family, its kind or arithmetic,
+    a network's configuration) decide hit or miss; the entry holds the weights it was packed from."""
+    key = [tag]                         # a plain loop: for one weight it costs what the per-weight lookup it replaced did
+    for w in weights:
+        if w.is_inference():
+            return pack()
+        key.append(_tensor_key(w))
+    slot = key[1][0]
     with C.lock:
-        e = C.entries.get(key[0])
+        e = C.entries.get(slot)
         if e is not None and e[0] == key:
-            C.entries.move_to_end(key[0])
+            C.entries.move_to_end(slot)
             C.hits += 1
             return e[2]
-    packed = pack(weight)
+    packed = pack()
     with C.lock:
         C.misses += 1
-        C.entries[key[0]] = (key, weight, packed)
-        C.entries.move_to_end(key[0])
+        C.entries[slot] = (key, weights, packed)
+        C.entries.move_to_end(slot)
         while len(C.entries) > C.limit:
             C.entries.popitem(last=False)
     return packed
@@ -703,26 +700,24 @@ def _conv_packed(weight, pack, tag):
 def _packed_conv(weight, arith=0):
     """the packed copies of a stride-1 weight for ``arith``: the arithmetic is part of the cache key, so a weight used under both has two
     entries' worth of packs, one resident at a time per weight"""
-    if arith == 0:
-        return _conv_packed(weight, ops.conv2d_pack, "conv")
-    return _conv_packed(weight, lambda w: ops.conv2d_pack(w, arith), ("conv", arith))
+    return _packed(_ConvPackCache, (weight,), ("conv", arith), lambda: ops.conv2d_pack(weight, arith))
 
 
 def _packed_s2(weight, kind):
-    return _conv_packed(weight, lambda w: ops.conv2d_s2_pack(w, kind), ("s2", kind))
+    return _packed(_ConvPackCache, (weight,), ("s2", kind), lambda: ops.conv2d_s2_pack(weight, kind))
 
 
 def _packed_rp(weight, kind):
-    return _conv_packed(weight, lambda w: ops.conv2d_rp_pack(w, kind), ("rp", kind))
+    return _packed(_ConvPackCache, (weight,), ("rp", kind), lambda: ops.conv2d_rp_pack(weight, kind))
 
 
 # What the three families' backward operators (kpnerf::conv2d_backward, conv2d_s2_backward, conv2d_rp_backward) and the autograd
 # backward of the four forward operators share.
-def _layer_backward(backward, x, dy, packed, args, has_bias, mask):
+def _layer_backward(backward, x, dy, packed, args, has_bias, mask, **arith):
     """the body of a backward operator: ``backward`` is the family's ops.*_backward, ``packed`` the packed copies (None without dx) and
     ``args`` what that function takes between them and has_bias"""
     dy = dy.contiguous(memory_format=torch.channels_last)
-    dx, dw, db = backward(x, dy, packed, *args, has_bias, want_dx=mask[0], want_dw=mask[1], want_db=mask[2])
+    dx, dw, db = backward(x, dy, packed, *args, has_bias, want_dx=mask[0], want_dw=mask[1], want_db=mask[2], **arith)
     return _empty_for_none(dy, dx, dw, db)
 
 
@@ -732,9 +727,9 @@ def _layer_backward_fake(x, weight, has_bias, mask, cout, dx_format=torch.channe
             x.new_empty(cout) if mask[2] and has_bias else e)
 
 
-def _layer_autograd(backward_op, what_attr, n_inputs):
+def _layer_autograd(backward_op, n_inputs):
     """the autograd backward of a forward operator over (x, weight, bias, ...n_inputs in all): only the legs whose inputs need a gradient
-    run, through ``backward_op`` with ctx.<what_attr> as its fourth argument"""
+    run, through ``backward_op`` with the tuple ctx.what (the padding, the kind, the arithmetic) between dy and has_bias"""
     nothing = (None,) * n_inputs
 
     def bwd(ctx, dy):
@@ -745,9 +740,37 @@ def _layer_autograd(backward_op, what_attr, n_inputs):
         mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]
         if not any(mask):
             return nothing
-        dx, dw, db = backward_op(x, weight, dy, getattr(ctx, what_attr), ctx.has_bias, mask)
+        dx, dw, db = backward_op(x, weight, dy, *ctx.what, ctx.has_bias, mask)
         return _none_unless(mask, dx, dw, db) + nothing[3:]
     return bwd
+
+
+# One implementation each of the forward, the backward, the fake kernels and the setup context serves kpnerf::conv2d and, further down,
+# kpnerf::conv2d_arith: the plain operators are its arith = 0 registration.
+def _conv2d_forward(x, weight, bias, padding, arith=0):
+    return ops.conv2d_forward(x, _packed_conv(weight, arith), bias, weight.shape[0], weight.shape[2], padding, arith=arith)
+
+
+def _conv2d_fake(x, weight, bias, padding, arith=0):
+    N, _, H, W = x.shape
+    cout, _, k, _ = weight.shape
+    return x.new_empty(N, H + 2 * padding - k + 1, W + 2 * padding - k + 1, cout).permute(0, 3, 1, 2)
+
+
+def _conv2d_backward(x, weight, dy, padding, has_bias, mask, arith=0):
+    return _layer_backward(ops.conv2d_backward, x, dy, _packed_conv(weight, arith) if mask[0] else None,
+                           (weight.shape[1], weight.shape[2], padding), has_bias, mask, arith=arith)
+
+
+def _conv2d_backward_fake(x, weight, dy, padding, has_bias, mask, arith=0):
+    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0], torch.preserve_format)
+
+
+def _conv2d_setup(ctx, inputs, output):
+    x, weight, bias, *ctx.what = inputs                         # (padding,) or (padding, arith)
+    ctx.save_for_backward(x, weight)
+    ctx.has_bias = bias is not None
+    ctx.set_materialize_grads(False)
 
 
 @_lib.custom_op("kpnerf::conv2d_cl", mutates_args=(), device_types="cuda")
@@ -755,14 +778,10 @@ def conv2d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     """conv2d(x, weight, bias, stride=1, padding=padding) for a channels_last x (kpn_conv2d_forward): what torch.ops.kpnerf.conv2d
     runs after its memory-format conversion.  weight (cout, cin, k, k), k in {1, 3, 5}, 0 <= padding < k, cin and cout multiples of 4.
     Returns (N, cout, Ho, Wo) channels_last."""
-    return ops.conv2d_forward(x, _packed_conv(weight), bias, weight.shape[0], weight.shape[2], padding)
+    return _conv2d_forward(x, weight, bias, padding)
 
 
-@conv2d_cl.register_fake
-def _(x, weight, bias, padding):
-    N, _, H, W = x.shape
-    cout, _, k, _ = weight.shape
-    return x.new_empty(N, H + 2 * padding - k + 1, W + 2 * padding - k + 1, cout).permute(0, 3, 1, 2)
+conv2d_cl.register_fake(_conv2d_fake)
 
 
 @_lib.custom_op("kpnerf::conv2d_backward", mutates_args=(), device_types="cuda")
@@ -770,23 +789,11 @@ def conv2d_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, pad
                     mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dx, dweight, dbias) of kpnerf::conv2d_cl for the output gradient dy (kpn_conv2d_backward); mask = [dx, dweight, dbias]
     wanted: a leg that is not wanted is not launched and its result is an empty tensor."""
-    return _layer_backward(ops.conv2d_backward, x, dy, _packed_conv(weight) if mask[0] else None, (weight.shape[1], weight.shape[2], padding),
-                           has_bias, mask)
+    return _conv2d_backward(x, weight, dy, padding, has_bias, mask)
 
 
-@conv2d_backward.register_fake
-def _(x, weight, dy, padding, has_bias, mask):
-    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0], torch.preserve_format)
-
-
-def _conv2d_setup(ctx, inputs, output):
-    x, weight, bias, padding = inputs
-    ctx.save_for_backward(x, weight)
-    ctx.padding, ctx.has_bias = padding, bias is not None
-    ctx.set_materialize_grads(False)
-
-
-conv2d_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_backward, "padding", 4), setup_context=_conv2d_setup)
+conv2d_backward.register_fake(_conv2d_backward_fake)
+conv2d_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_backward, 4), setup_context=_conv2d_setup)
 
 
 # torch.ops.kpnerf.conv2d(x, weight, bias, padding): x in any memory format.  A contiguous NCHW input is converted to channels_last
@@ -860,15 +867,15 @@ def _(x, weight, dy, kind, has_bias, mask):
 def _s2_setup(kind_of):
     def setup(ctx, inputs, output):
         x, weight, bias = inputs
-        ctx.kind, ctx.has_bias = kind_of(weight), bias is not None
-        if ctx.kind == kl.S2_STEM7 and ctx.needs_input_grad[0]:
+        ctx.what, ctx.has_bias = (kind_of(weight),), bias is not None
+        if ctx.what[0] == kl.S2_STEM7 and ctx.needs_input_grad[0]:
             raise RuntimeError("kpnerf::conv2d_down2: the 7x7 stem has no input gradient (x.requires_grad is set)")
         ctx.save_for_backward(x, weight)
         ctx.set_materialize_grads(False)
     return setup
 
 
-_s2_bwd = _layer_autograd(torch.ops.kpnerf.conv2d_s2_backward, "kind", 3)
+_s2_bwd = _layer_autograd(torch.ops.kpnerf.conv2d_s2_backward, 3)
 conv2d_down2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(_down2_kind))
 conv_transpose2d_up2_cl.register_autograd(_s2_bwd, setup_context=_s2_setup(lambda w: kl.S2_DECONV3))
 
@@ -924,14 +931,14 @@ def _(x, weight, dy, kind, has_bias, mask):
 
 def _rp_setup(ctx, inputs, output):
     x, weight, bias = inputs
-    ctx.kind, ctx.has_bias = ops.conv2d_rp_kind(weight.shape), bias is not None
-    if ctx.kind == kl.RP_STEM7 and ctx.needs_input_grad[0]:
+    ctx.what, ctx.has_bias = (ops.conv2d_rp_kind(weight.shape),), bias is not None
+    if ctx.what[0] == kl.RP_STEM7 and ctx.needs_input_grad[0]:
         raise RuntimeError("kpnerf::conv2d_replicate: the 7x7 stem has no input gradient (x.requires_grad is set)")
     ctx.save_for_backward(x, weight)
     ctx.set_materialize_grads(False)
 
 
-conv2d_replicate_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_rp_backward, "kind", 3), setup_context=_rp_setup)
+conv2d_replicate_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_rp_backward, 3), setup_context=_rp_setup)
 
 
 # torch.ops.kpnerf.conv2d_replicate(x, weight, bias): x in any memory format, converted once (as kpnerf::conv2d does) - to channels_last,
@@ -1023,23 +1030,66 @@ def _block_legs(tensors):
     return [tensors[i:i + 3] for i in range(0, len(tensors), 3)]
 
 
+# One implementation each of the forward, the backward, the fake kernels, the setup context and the autograd backward serves
+# kpnerf::conv_block and, further down, kpnerf::conv_block_arith: the plain operators are its arith = 0 registration.
+def _conv_block_forward(x, tensors, eps, arith=0):
+    legs = _block_legs(tensors)
+    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], 2 * legs[0][2].shape[0], eps,
+                                  arith=arith)
+
+
+def _conv_block_fake(x, tensors, eps, arith=0):
+    # the state size is the library's answer for a descriptor of plain ints: a symbolic N, H or W is specialised here (as in the fake
+    # kernels of hg_filter_cl and fold_params_norms)
+    N, cin, H, W = x.shape
+    cout = 2 * tensors[2].shape[0]
+    d = ops._block_desc(N, H, W, cin, cout, eps)
+    return x.new_empty(N, H, W, cout).permute(0, 3, 1, 2), x.new_empty(ops._conv_library(arith).kpn_conv_block_state_floats(ctypes.byref(d)))
+
+
+def _conv_block_backward(x, tensors, state, dy, eps, mask, arith=0):
+    legs = _block_legs(tensors)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
+    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], state, eps,
+                                        want_dx=mask[0], want=want, arith=arith)
+    return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
+
+
+def _conv_block_backward_fake(x, tensors, state, dy, eps, mask, arith=0):
+    # one empty tensor per gradient that is not wanted, as the operator returns them: no two results share memory
+    return [torch.empty_like(x) if mask[0] else x.new_empty(0)] + [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask[1:])]
+
+
+def _conv_block_setup(ctx, inputs, output):
+    x, tensors, *ctx.what = inputs                                               # (eps,) or (eps, arith)
+    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
+    ctx.set_materialize_grads(False)
+
+
+def _conv_block_autograd(backward_op):
+    def bwd(ctx, dy, _d_state):
+        x, state, *tensors = ctx.saved_tensors
+        none = (None, [None] * len(tensors)) + (None,) * len(ctx.what)
+        if dy is None:
+            return none
+        mask = [bool(ctx.needs_input_grad[0])] + [bool(b) for b in ctx.needs_input_grad[1]]
+        if not any(mask):
+            return none
+        out = _none_unless(mask, *backward_op(x, list(tensors), state, dy, *ctx.what, mask))
+        return (out[0], list(out[1:])) + none[2:]
+    return bwd
+
+
 @_lib.custom_op("kpnerf::conv_block_cl", mutates_args=(), device_types="cuda")
 def conv_block_cl(x: torch.Tensor, tensors: List[torch.Tensor], eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """(y, state) of a ConvBlock for a channels_last x (kpn_conv_block_forward): what torch.ops.kpnerf.conv_block runs after its
     memory-format conversion.  y is (N, cout, H, W) channels_last with cout = 2 * conv1.weight.shape[0]; state is the side buffer of the
     backward."""
-    legs = _block_legs(tensors)
-    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_packed_conv(w) for _, _, w in legs], 2 * legs[0][2].shape[0], eps)
+    return _conv_block_forward(x, tensors, eps)
 
 
-@conv_block_cl.register_fake
-def _(x, tensors, eps):
-    N, cin, H, W = x.shape
-    cout = 2 * tensors[2].shape[0]
-    G = lambda C: min(32, C)  # noqa: E731
-    widths = (cin, cout // 2, cout // 4) + ((cin,) if len(tensors) == 12 else ())
-    return (x.new_empty(N, H, W, cout).permute(0, 3, 1, 2),
-            x.new_empty(N * H * W * (cout // 2 + cout // 4) + sum(2 * N * C + 2 * N * G(C) for C in widths)))
+conv_block_cl.register_fake(_conv_block_fake)
 
 
 @_lib.custom_op("kpnerf::conv_block_backward", mutates_args=(), device_types="cuda")
@@ -1047,41 +1097,11 @@ def conv_block_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: tor
                         mask: List[bool]) -> List[torch.Tensor]:
     """[dx] + one gradient per tensor of kpnerf::conv_block_cl for the output gradient dy (kpn_conv_block_backward); mask = [dx wanted]
     + one flag per tensor: what is not wanted is not computed and its result is an empty tensor."""
-    legs = _block_legs(tensors)
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
-    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_packed_conv(w) for _, _, w in legs], state, eps,
-                                        want_dx=mask[0], want=want)
-    return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
+    return _conv_block_backward(x, tensors, state, dy, eps, mask)
 
 
-@conv_block_backward.register_fake
-def _(x, tensors, state, dy, eps, mask):
-    # one empty tensor per gradient that is not wanted, as the operator returns them: no two results share memory
-    return [torch.empty_like(x) if mask[0] else x.new_empty(0)] + [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask[1:])]
-
-
-def _conv_block_setup(ctx, inputs, output):
-    x, tensors, eps = inputs
-    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
-    ctx.eps = eps
-    ctx.set_materialize_grads(False)
-
-
-def _conv_block_bwd(ctx, dy, _d_state):
-    x, state, *tensors = ctx.saved_tensors
-    none = (None, [None] * len(tensors), None)
-    if dy is None:
-        return none
-    mask = [bool(ctx.needs_input_grad[0])] + [bool(b) for b in ctx.needs_input_grad[1]]
-    if not any(mask):
-        return none
-    out = torch.ops.kpnerf.conv_block_backward(x, list(tensors), state, dy, ctx.eps, mask)
-    out = _none_unless(mask, *out)
-    return out[0], list(out[1:]), None
-
-
-conv_block_cl.register_autograd(_conv_block_bwd, setup_context=_conv_block_setup)
+conv_block_backward.register_fake(_conv_block_backward_fake)
+conv_block_cl.register_autograd(_conv_block_autograd(torch.ops.kpnerf.conv_block_backward), setup_context=_conv_block_setup)
 
 
 # torch.ops.kpnerf.conv_block(x, tensors, eps): x in any memory format, converted to channels_last once (as kpnerf::conv2d does); the
@@ -1097,56 +1117,29 @@ _fragment.impl("conv_block", _conv_block, "CompositeImplicitAutograd")
 # ---- torch.ops.kpnerf.conv2d_arith / conv_block_arith: the two operators above with the arithmetic of their GEMMs as an argument ----
 # arith = 0 (CONV_F32) computes what kpnerf::conv2d / kpnerf::conv_block compute, bit for bit; arith = 1 (CONV_BF16X3) runs the
 # convolutions on three bf16 pieces per operand (kpn_conv2d_ex_*, kpn_conv_block_ex_*).  The existing schemas stay as they are; these
-# are operators of their own, with the same autograd structure, the same fake kernels and the same pack cache (arith is in its key).
+# are operators of their own over the same bodies (_conv2d_* / _conv_block_* above) and the same pack cache (arith is in its key).
 @_lib.custom_op("kpnerf::conv2d_arith_cl", mutates_args=(), device_types="cuda")
 def conv2d_arith_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], padding: int, arith: int) -> torch.Tensor:
     """kpnerf::conv2d_cl in the arithmetic ``arith`` (kpn_conv2d_ex_forward)"""
-    return ops.conv2d_forward(x, _packed_conv(weight, arith), bias, weight.shape[0], weight.shape[2], padding, arith=arith)
+    return _conv2d_forward(x, weight, bias, padding, arith)
 
 
-@conv2d_arith_cl.register_fake
-def _(x, weight, bias, padding, arith):
-    N, _, H, W = x.shape
-    cout, _, k, _ = weight.shape
-    return x.new_empty(N, H + 2 * padding - k + 1, W + 2 * padding - k + 1, cout).permute(0, 3, 1, 2)
+conv2d_arith_cl.register_fake(_conv2d_fake)
 
 
 @_lib.custom_op("kpnerf::conv2d_arith_backward", mutates_args=(), device_types="cuda")
 def conv2d_arith_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, padding: int, arith: int, has_bias: bool,
                           mask: List[bool]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """kpnerf::conv2d_backward in the arithmetic ``arith`` (kpn_conv2d_ex_backward)"""
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dx, dw, db = ops.conv2d_backward(x, dy, _packed_conv(weight, arith) if mask[0] else None, weight.shape[1], weight.shape[2], padding,
-                                     has_bias, want_dx=mask[0], want_dw=mask[1], want_db=mask[2], arith=arith)
-    return _empty_for_none(dy, dx, dw, db)
+    return _conv2d_backward(x, weight, dy, padding, has_bias, mask, arith)
 
 
 @conv2d_arith_backward.register_fake
 def _(x, weight, dy, padding, arith, has_bias, mask):
-    return _layer_backward_fake(x, weight, has_bias, mask, weight.shape[0], torch.preserve_format)
+    return _conv2d_backward_fake(x, weight, dy, padding, has_bias, mask)
 
 
-def _conv2d_arith_setup(ctx, inputs, output):
-    x, weight, bias, padding, arith = inputs
-    ctx.save_for_backward(x, weight)
-    ctx.padding, ctx.arith, ctx.has_bias = padding, arith, bias is not None
-    ctx.set_materialize_grads(False)
-
-
-def _conv2d_arith_bwd(ctx, dy):
-    nothing = (None,) * 5
-    if dy is None:
-        return nothing
-    x, weight = ctx.saved_tensors
-    need = ctx.needs_input_grad
-    mask = [bool(need[0]), bool(need[1]), bool(ctx.has_bias and need[2])]
-    if not any(mask):
-        return nothing
-    dx, dw, db = torch.ops.kpnerf.conv2d_arith_backward(x, weight, dy, ctx.padding, ctx.arith, ctx.has_bias, mask)
-    return _none_unless(mask, dx, dw, db) + nothing[3:]
-
-
-conv2d_arith_cl.register_autograd(_conv2d_arith_bwd, setup_context=_conv2d_arith_setup)
+conv2d_arith_cl.register_autograd(_layer_autograd(torch.ops.kpnerf.conv2d_arith_backward, 5), setup_context=_conv2d_setup)
 
 
 def _conv2d_arith(x, weight, bias, padding, arith):
@@ -1160,54 +1153,25 @@ _fragment.impl("conv2d_arith", _conv2d_arith, "CompositeImplicitAutograd")
 @_lib.custom_op("kpnerf::conv_block_arith_cl", mutates_args=(), device_types="cuda")
 def conv_block_arith_cl(x: torch.Tensor, tensors: List[torch.Tensor], eps: float, arith: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """kpnerf::conv_block_cl with every convolution in the arithmetic ``arith`` (kpn_conv_block_ex_forward)"""
-    legs = _block_legs(tensors)
-    return ops.conv_block_forward(x, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], 2 * legs[0][2].shape[0], eps,
-                                  arith=arith)
+    return _conv_block_forward(x, tensors, eps, arith)
 
 
-@conv_block_arith_cl.register_fake
-def _(x, tensors, eps, arith):
-    return torch.ops.kpnerf.conv_block_cl(x, tensors, eps)          # the shapes do not depend on the arithmetic
+conv_block_arith_cl.register_fake(_conv_block_fake)
 
 
 @_lib.custom_op("kpnerf::conv_block_arith_backward", mutates_args=(), device_types="cuda")
 def conv_block_arith_backward(x: torch.Tensor, tensors: List[torch.Tensor], state: torch.Tensor, dy: torch.Tensor, eps: float, arith: int,
                               mask: List[bool]) -> List[torch.Tensor]:
     """kpnerf::conv_block_backward with every convolution in the arithmetic ``arith`` (kpn_conv_block_ex_backward)"""
-    legs = _block_legs(tensors)
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    want = [tuple(mask[1 + 3 * i:4 + 3 * i]) for i in range(len(legs))]
-    dx, grads = ops.conv_block_backward(x, dy, [(g, b) for g, b, _ in legs], [_packed_conv(w, arith) for _, _, w in legs], state, eps,
-                                        want_dx=mask[0], want=want, arith=arith)
-    return list(_empty_for_none(dy, dx, *[g for leg in grads for g in leg]))
+    return _conv_block_backward(x, tensors, state, dy, eps, mask, arith)
 
 
 @conv_block_arith_backward.register_fake
 def _(x, tensors, state, dy, eps, arith, mask):
-    return [torch.empty_like(x) if mask[0] else x.new_empty(0)] + [torch.empty_like(t) if m else x.new_empty(0) for t, m in zip(tensors, mask[1:])]
+    return _conv_block_backward_fake(x, tensors, state, dy, eps, mask)
 
 
-def _conv_block_arith_setup(ctx, inputs, output):
-    x, tensors, eps, arith = inputs
-    ctx.save_for_backward(x, output[1], *tensors)                                # never y, never a normalised tensor
-    ctx.eps, ctx.arith = eps, arith
-    ctx.set_materialize_grads(False)
-
-
-def _conv_block_arith_bwd(ctx, dy, _d_state):
-    x, state, *tensors = ctx.saved_tensors
-    none = (None, [None] * len(tensors), None, None)
-    if dy is None:
-        return none
-    mask = [bool(ctx.needs_input_grad[0])] + [bool(b) for b in ctx.needs_input_grad[1]]
-    if not any(mask):
-        return none
-    out = torch.ops.kpnerf.conv_block_arith_backward(x, list(tensors), state, dy, ctx.eps, ctx.arith, mask)
-    out = _none_unless(mask, *out)
-    return out[0], list(out[1:]), None, None
-
-
-conv_block_arith_cl.register_autograd(_conv_block_arith_bwd, setup_context=_conv_block_arith_setup)
+conv_block_arith_cl.register_autograd(_conv_block_autograd(torch.ops.kpnerf.conv_block_arith_backward), setup_context=_conv_block_setup)
 
 
 def _conv_block_arith(x, tensors, eps, arith):
@@ -1230,20 +1194,6 @@ def _res_cfg(tensors, n_down, n_blocks, n_up):
     return (tensors[0].shape[0], n_down, n_blocks, n_up, tensors[-2].shape[0])
 
 
-def _res_state_floats(N, H, W, in_ch, cfg):
-    """kpn_res_encoder_state_floats, restated for the fake kernels"""
-    shapes = ops.res_encoder_layer_shapes(in_ch, cfg)[:-1]
-    total, h, w = 0, H, W
-    for i, (_, C) in enumerate(shapes):
-        if 1 <= i <= cfg[1]:
-            h, w = h // 2, w // 2
-        elif i > cfg[1] + 2 * cfg[2]:
-            h, w = 2 * h, 2 * w
-        total += N * h * w * C + 4 * N * C
-    f = 1 << cfg[1]
-    return total + (cfg[2] + 1) * N * (H // f) * (W // f) * (cfg[0] * f)
-
-
 class _ResPackCache:
     lock = threading.Lock()
     entries = collections.OrderedDict()     # data_ptr of the stem's weight -> (key, weights, packed)
@@ -1257,24 +1207,7 @@ def res_encoder_cache_clear():
 
 
 def _res_packed(weights, in_ch, cfg):
-    if any(w.is_inference() for w in weights):
-        return ops.res_encoder_pack(weights, in_ch, cfg)
-    key = tuple(_tensor_key(w) for w in weights) + (tuple(cfg),)
-    C = _ResPackCache
-    with C.lock:
-        e = C.entries.get(key[0][0])
-        if e is not None and e[0] == key:
-            C.entries.move_to_end(key[0][0])
-            C.hits += 1
-            return e[2]
-    packed = ops.res_encoder_pack(weights, in_ch, cfg)
-    with C.lock:
-        C.misses += 1
-        C.entries[key[0][0]] = (key, list(weights), packed)
-        C.entries.move_to_end(key[0][0])
-        while len(C.entries) > C.limit:
-            C.entries.popitem(last=False)
-    return packed
+    return _packed(_ResPackCache, weights, tuple(cfg), lambda: ops.res_encoder_pack(weights, in_ch, cfg))
 
 
 @_lib.custom_op("kpnerf::res_encoder_cl", mutates_args=(), device_types="cuda")
@@ -1292,7 +1225,8 @@ def _(x, tensors, n_down, n_blocks, n_up, eps):
     cfg = _res_cfg(tensors, n_down, n_blocks, n_up)
     N, in_ch, H, W = x.shape
     f = n_down - n_up
-    return x.new_empty(N, H >> f, W >> f, cfg[4]).permute(0, 3, 1, 2), x.new_empty(_res_state_floats(N, H, W, in_ch, cfg))
+    d = ops._res_encoder_desc(N, H, W, in_ch, cfg, eps)       # plain ints: a symbolic N, H or W is specialised here
+    return x.new_empty(N, H >> f, W >> f, cfg[4]).permute(0, 3, 1, 2), x.new_empty(kl.get_library().kpn_res_encoder_state_floats(ctypes.byref(d)))
 
 
 @_lib.custom_op("kpnerf::res_encoder_backward", mutates_args=(), device_types="cuda")
@@ -1370,30 +1304,9 @@ def _hg_cfg(x, tensors, depth):
     return cfg
 
 
-def _hg_weights(tensors):
-    return [t for t in tensors if t.dim() == 4]
-
-
 def _hg_packed(tensors, cfg):
-    weights = _hg_weights(tensors)
-    if any(w.is_inference() for w in weights):
-        return ops.hg_filter_pack(tensors, cfg)
-    key = tuple(_tensor_key(w) for w in weights) + (("hg_filter",) + tuple(cfg),)
-    C = _ResPackCache
-    with C.lock:
-        e = C.entries.get(key[0][0])
-        if e is not None and e[0] == key:
-            C.entries.move_to_end(key[0][0])
-            C.hits += 1
-            return e[2]
-    packed = ops.hg_filter_pack(tensors, cfg)
-    with C.lock:
-        C.misses += 1
-        C.entries[key[0][0]] = (key, weights, packed)
-        C.entries.move_to_end(key[0][0])
-        while len(C.entries) > C.limit:
-            C.entries.popitem(last=False)
-    return packed
+    weights = [t for t in tensors if t.dim() == 4]
+    return _packed(_ResPackCache, weights, ("hg_filter",) + tuple(cfg), lambda: ops.hg_filter_pack(tensors, cfg))
 
 
 @_lib.custom_op("kpnerf::hg_filter_cl", mutates_args=(), device_types="cuda")

@@ -180,6 +180,47 @@ def test_op_keeps_its_input_its_state_and_the_parameters_only():
     assert len(saved) == 2 + len(tensors)
 
 
+def test_op_pack_cache_is_reused_rebuilt_after_an_in_place_update_and_shared_with_res_encoder():
+    """the counts of tests/test_gpu_conv.py for the one packed buffer of the network, which lives in the cache of kpnerf::res_encoder: an
+    entry of either operator stays resident beside the other's"""
+    from keypointnerf_amd import torch_ops
+    from tests import res_encoder_cases as ec
+    C = torch_ops._ResPackCache
+    torch_ops.res_encoder_cache_clear()
+    dev, x, gs = _on_device("narrow")
+    tensors = hc.tensors_of(dev)
+    run = lambda ts=tensors, xs=x: torch.ops.kpnerf.hg_filter(xs, ts, hc.CASES["narrow"]["depth"], hc.EPS)  # noqa: E731
+    h0, m0 = C.hits, C.misses
+    y1, y2 = run(), run()
+    assert (C.misses - m0, C.hits - h0) == (1, 1) and torch.equal(y1[0], y2[0]) and torch.equal(y1[1], y2[1]) and len(C.entries) == 1
+    torch.autograd.grad(y2, tensors, gs)
+    assert (C.misses - m0, C.hits - h0) == (1, 2)                       # the backward reads the forward's packed buffer
+    # an encoder of kpnerf::res_encoder beside it: its own slot, and both entries hit afterwards
+    c = ec.CASES["noblocks"]
+    enc, xe, _, _, _ = ec.reference("noblocks")
+    enc, xe = copy.deepcopy(enc).cuda(), xe.cuda()
+    te = [t for m in ec.convs_of(enc) for t in (m.weight, m.bias)]
+    res = lambda: torch.ops.kpnerf.res_encoder(xe, te, c["n_down"], c["n_blocks"], c["n_up"], ec.EPS)  # noqa: E731
+    e1 = res()
+    assert (C.misses - m0, C.hits - h0) == (2, 2) and len(C.entries) == 2
+    y3, e2 = run(), res()
+    assert (C.misses - m0, C.hits - h0) == (2, 4) and len(C.entries) == 2
+    assert torch.equal(y3[0], y1[0]) and torch.equal(e2, e1)
+    with torch.no_grad():
+        tensors[-2].mul_(2.0)                                           # what an optimizer step does, to l0's weight
+    y4 = run()
+    assert (C.misses - m0, C.hits - h0) == (3, 4) and len(C.entries) == 2
+    assert not torch.equal(y4[0], y1[0]) and torch.equal(y4[1], y1[1])  # out = l0(...): a stale pack would give y1; x_hd does not read l0
+    with torch.inference_mode():
+        ti = [t.detach().clone() for t in tensors]
+        yi = run(ti, x.clone())
+        run(ti, x.clone())
+    assert len(C.entries) == 2 and (C.misses - m0, C.hits - h0) == (3, 4)       # inference tensors get no cache
+    assert torch.equal(yi[0], y4[0])
+    torch_ops.res_encoder_cache_clear()
+    assert len(C.entries) == 0
+
+
 def test_op_raises_on_an_input_that_requires_a_gradient():
     import keypointnerf_amd.torch_ops  # noqa: F401
     dev, x, _ = _on_device("narrow")

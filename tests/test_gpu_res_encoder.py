@@ -120,6 +120,35 @@ def test_op_partial_gradients_and_memory_formats():
     assert not y.requires_grad and torch.equal(y, y0)
 
 
+def test_op_pack_cache_is_reused_and_rebuilt_after_an_in_place_update():
+    """the counts of tests/test_gpu_conv.py for the one packed buffer of an encoder: keyed on every weight, not on the first alone"""
+    from keypointnerf_amd import torch_ops
+    C = torch_ops._ResPackCache
+    torch_ops.res_encoder_cache_clear()
+    c = ec.CASES["noblocks"]
+    dev, x, g = _case_on_device("noblocks")
+    tensors = _tensors(dev)
+    h0, m0 = C.hits, C.misses
+    y1 = torch.ops.kpnerf.res_encoder(x, tensors, *_cfg(c))
+    y2 = torch.ops.kpnerf.res_encoder(x, tensors, *_cfg(c))
+    assert (C.misses - m0, C.hits - h0) == (1, 1) and torch.equal(y1, y2) and len(C.entries) == 1
+    torch.autograd.grad(y2, tensors, g)
+    assert (C.misses - m0, C.hits - h0) == (1, 2)                       # the backward reads the forward's packed buffer
+    with torch.no_grad():
+        tensors[-2].mul_(2.0)                                           # what an optimizer step does, to the output layer's weight
+    y3 = torch.ops.kpnerf.res_encoder(x, tensors, *_cfg(c))
+    assert (C.misses - m0, C.hits - h0) == (2, 2) and len(C.entries) == 1
+    assert not torch.equal(y3, y1)                                      # no norm behind the output layer: a stale pack would give y1
+    with torch.inference_mode():
+        ti = [t.detach().clone() for t in tensors]
+        yi = torch.ops.kpnerf.res_encoder(x.clone(), ti, *_cfg(c))
+        torch.ops.kpnerf.res_encoder(x.clone(), ti, *_cfg(c))
+    assert len(C.entries) == 1 and (C.misses - m0, C.hits - h0) == (2, 2)       # inference tensors get no cache
+    assert torch.equal(yi, y3)
+    torch_ops.res_encoder_cache_clear()
+    assert len(C.entries) == 0
+
+
 def test_op_raises_on_an_input_that_requires_a_gradient():
     import keypointnerf_amd.torch_ops  # noqa: F401
     c = ec.CASES["noblocks"]

@@ -32,6 +32,84 @@ def test_ops_are_registered_with_fake_kernels():
         torch.ops.kpnerf.rgba2out(torch.zeros(1, 2, 4, 5), torch.zeros(1, 2, 4))
 
 
+# Every operator of the namespace: its schema string, and "CUDA" for a torch.library.custom_op registration (device_types="cuda") or
+# "Comp" for a CompositeImplicitAutograd one.  Callers, saved graphs and tests name these; the operators' bodies may be shared or
+# rewritten, this table may not change with them.
+_SCHEMAS = [
+    ('kpnerf::avg_pool2(Tensor x) -> Tensor', 'Comp'),
+    ('kpnerf::avg_pool2_backward(Tensor dy) -> Tensor', 'CUDA'),
+    ('kpnerf::avg_pool2_cl(Tensor x) -> Tensor', 'CUDA'),
+    ('kpnerf::conv2d(Tensor x, Tensor weight, Tensor? bias, int padding) -> Tensor', 'Comp'),
+    ('kpnerf::conv2d_arith(Tensor x, Tensor weight, Tensor? bias, int padding, int arith) -> Tensor', 'Comp'),
+    ('kpnerf::conv2d_arith_backward(Tensor x, Tensor weight, Tensor dy, SymInt padding, SymInt arith, bool has_bias, bool[] mask) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv2d_arith_cl(Tensor x, Tensor weight, Tensor? bias, SymInt padding, SymInt arith) -> Tensor', 'CUDA'),
+    ('kpnerf::conv2d_backward(Tensor x, Tensor weight, Tensor dy, SymInt padding, bool has_bias, bool[] mask) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv2d_cl(Tensor x, Tensor weight, Tensor? bias, SymInt padding) -> Tensor', 'CUDA'),
+    ('kpnerf::conv2d_down2(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'Comp'),
+    ('kpnerf::conv2d_down2_cl(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'CUDA'),
+    ('kpnerf::conv2d_replicate(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'Comp'),
+    ('kpnerf::conv2d_replicate_cl(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'CUDA'),
+    ('kpnerf::conv2d_rp_backward(Tensor x, Tensor weight, Tensor dy, SymInt kind, bool has_bias, bool[] mask) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv2d_s2_backward(Tensor x, Tensor weight, Tensor dy, SymInt kind, bool has_bias, bool[] mask) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv_block(Tensor x, Tensor[] tensors, float eps) -> Tensor', 'Comp'),
+    ('kpnerf::conv_block_arith(Tensor x, Tensor[] tensors, float eps, int arith) -> Tensor', 'Comp'),
+    ('kpnerf::conv_block_arith_backward(Tensor x, Tensor[] tensors, Tensor state, Tensor dy, float eps, SymInt arith, bool[] mask) -> Tensor[]', 'CUDA'),
+    ('kpnerf::conv_block_arith_cl(Tensor x, Tensor[] tensors, float eps, SymInt arith) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv_block_backward(Tensor x, Tensor[] tensors, Tensor state, Tensor dy, float eps, bool[] mask) -> Tensor[]', 'CUDA'),
+    ('kpnerf::conv_block_cl(Tensor x, Tensor[] tensors, float eps) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::conv_transpose2d_up2(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'Comp'),
+    ('kpnerf::conv_transpose2d_up2_cl(Tensor x, Tensor weight, Tensor? bias) -> Tensor', 'CUDA'),
+    ('kpnerf::field_query(Tensor scene_ws, SymInt[] scene_dims, float[] scene_scalars, Tensor weights, Tensor pts, Tensor view, SymInt mode) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::fold_params(Tensor[] tensors) -> Tensor', 'Comp'),
+    ('kpnerf::fold_params_backward(Tensor[] tensors, Tensor norms, Tensor d_plain) -> Tensor[]', 'CUDA'),
+    ('kpnerf::fold_params_backward_shape(Tensor[] tensors, Tensor norms, Tensor d_plain, SymInt n_kpt, SymInt sp_level) -> Tensor[]', 'CUDA'),
+    ('kpnerf::fold_params_norms(Tensor[] tensors) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::fold_params_norms_shape(Tensor[] tensors, SymInt n_kpt, SymInt sp_level) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::fold_params_shape(Tensor[] tensors, int n_kpt, int sp_level) -> Tensor', 'Comp'),
+    ('kpnerf::geo_encode(Tensor img, Tensor packed, SymInt[] cfg, float eps) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::group_norm(Tensor x, Tensor? weight, Tensor? bias, int groups, float eps, bool relu) -> Tensor', 'Comp'),
+    ('kpnerf::group_norm_backward(Tensor x, Tensor? weight, Tensor stats, Tensor dy, SymInt groups, float eps, bool relu, bool[] mask) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::group_norm_cl(Tensor x, Tensor? weight, Tensor? bias, SymInt groups, float eps, bool relu) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::hg_filter(Tensor x, Tensor[] tensors, int depth, float eps) -> Tensor[]', 'Comp'),
+    ('kpnerf::hg_filter_backward(Tensor x, Tensor[] tensors, Tensor state, Tensor? d_out, Tensor? d_x_hd, SymInt depth, float eps, bool[] mask) -> Tensor[]', 'CUDA'),
+    ('kpnerf::hg_filter_cl(Tensor x, Tensor[] tensors, SymInt depth, float eps) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::importance_sample(Tensor contrib, Tensor z, SymInt n, Tensor? u=None) -> Tensor', 'CUDA'),
+    ('kpnerf::narrow_plain_grad(Tensor d_plain, SymInt n_kpt, SymInt sp_level) -> Tensor', 'CUDA'),
+    ('kpnerf::pix_l1_loss(Tensor src, Tensor tar, float lam) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::ray_bbox_intersection(Tensor bounds, Tensor orig, Tensor direct) -> (Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::render_rays(Tensor scene_ws, SymInt[] scene_dims, float[] scene_scalars, Tensor weights, Tensor K, Tensor RT, Tensor bounds, float znear, float zfar, SymInt[] grid, SymInt n_coarse, SymInt n_fine, bool fine) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::render_rays_train(Tensor plain, Tensor geo0, Tensor geo1, Tensor tex, Tensor img, Tensor KRT, Tensor extrin, Tensor kpt3d, Tensor? fg_mask, float[] scene_scalars, Tensor K, Tensor RT, Tensor bounds, float znear, float zfar, Tensor pix, Tensor u_c, Tensor u_f, Tensor? noise_c, Tensor? noise_f, SymInt keep_c, SymInt keep_f, float noise_std, SymInt n_coarse, SymInt n_fine, bool keep_state=False) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::render_rays_train_backward(Tensor plain, Tensor geo0, Tensor geo1, Tensor tex, Tensor img, Tensor KRT, Tensor extrin, Tensor kpt3d, Tensor? fg_mask, float[] scene_scalars, Tensor K, Tensor RT, Tensor bounds, float znear, float zfar, Tensor pix, Tensor u_c, Tensor u_f, Tensor? noise_c, Tensor? noise_f, SymInt keep_c, SymInt keep_f, float noise_std, SymInt n_coarse, SymInt n_fine, Tensor? d_tex_fg, Tensor? d_depth, Tensor? d_alpha, Tensor? d_tex_fg_fine, Tensor? d_depth_fine, Tensor? d_alpha_fine, Tensor? d_sdf, Tensor? state=None) -> (Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::render_rays_train_backward_kpt(Tensor plain, Tensor geo0, Tensor geo1, Tensor tex, Tensor img, Tensor KRT, Tensor extrin, Tensor kpt3d, Tensor? fg_mask, float[] scene_scalars, Tensor K, Tensor RT, Tensor bounds, float znear, float zfar, Tensor pix, Tensor u_c, Tensor u_f, Tensor? noise_c, Tensor? noise_f, SymInt keep_c, SymInt keep_f, float noise_std, SymInt n_coarse, SymInt n_fine, Tensor? d_tex_fg, Tensor? d_depth, Tensor? d_alpha, Tensor? d_tex_fg_fine, Tensor? d_depth_fine, Tensor? d_alpha_fine, Tensor? d_sdf, Tensor? state=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::res_encoder(Tensor x, Tensor[] tensors, int n_down, int n_blocks, int n_up, float eps) -> Tensor', 'Comp'),
+    ('kpnerf::res_encoder_backward(Tensor x, Tensor[] tensors, Tensor state, Tensor dy, SymInt n_down, SymInt n_blocks, SymInt n_up, float eps, bool[] mask) -> Tensor[]', 'CUDA'),
+    ('kpnerf::res_encoder_cl(Tensor x, Tensor[] tensors, SymInt n_down, SymInt n_blocks, SymInt n_up, float eps) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::rgba2out(Tensor rgba, Tensor z) -> (Tensor, Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::rgba2out_backward(Tensor rgba, Tensor z, Tensor? d_color, Tensor? d_depth, Tensor? d_alpha, Tensor? d_sdf) -> Tensor', 'CUDA'),
+    ('kpnerf::tex_encode(Tensor img, Tensor packed, SymInt[] cfg, float eps) -> Tensor', 'CUDA'),
+    ('kpnerf::train_loss(Tensor? tex, Tensor? tex_fine, Tensor tar, Tensor? alpha, Tensor? alpha_fine, Tensor? tar_alpha, float[] weights) -> (Tensor, Tensor, Tensor, Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::upsample2x_add(Tensor low, Tensor? skip) -> Tensor', 'Comp'),
+    ('kpnerf::upsample2x_add_backward(Tensor dy) -> Tensor', 'CUDA'),
+    ('kpnerf::upsample2x_add_cl(Tensor low, Tensor? skip) -> Tensor', 'CUDA'),
+    ('kpnerf::vgg_loss(Tensor x, Tensor y, Tensor packed, float[] consts, float lam) -> (Tensor, Tensor)', 'CUDA'),
+    ('kpnerf::widen_plain(Tensor narrow, SymInt n_kpt, SymInt sp_level) -> Tensor', 'CUDA'),
+]
+
+
+def test_every_operator_keeps_its_schema_and_dispatch_key():
+    import keypointnerf_amd.torch_ops  # noqa: F401
+    has = torch._C._dispatch_has_kernel_for_dispatch_key
+    got = []
+    for s in torch._C._jit_get_all_schemas():
+        if s.name.startswith("kpnerf::"):
+            keys = [k for k, full in (("CUDA", "CUDA"), ("Comp", "CompositeImplicitAutograd"), ("CPU", "CPU")) if has(s.name, full)]
+            got.append((str(s), "+".join(keys)))
+    got.sort()
+    want = sorted(_SCHEMAS)
+    assert [g[0] for g in got] == [w[0] for w in want], sorted(set(got) ^ set(want))
+    assert got == want, [(g, w) for g, w in zip(got, want) if g != w]
+
+
 @pytest.mark.gpu
 def test_custom_ops_match_direct_calls():
     import keypointnerf_amd.torch_ops  # noqa: F401
