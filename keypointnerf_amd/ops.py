@@ -13,6 +13,7 @@ torch is plumbing here (device memory, streams); the arithmetic is in csrc/*.hip
 its tensors are not on a HIP device or the library is missing — there is no CPU/eager fallback.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -1009,21 +1010,17 @@ def _desc_workspace(L, d, device, size_fn, probe_fn, label):
     return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
 
-_CONV_WORKSPACE = ("kpn_conv2d_workspace_bytes", "kpn_conv2d_forward", "conv2d: unsupported convolution")
 _NORM_WORKSPACE = ("kpn_group_norm_workspace_bytes", "kpn_group_norm_forward", "group_norm: unsupported normalisation")
 
 
 # ------------------------------------------------------------------------------------------------
-# One stride-1 convolution and its gradients (kpn_conv2d_*; torch.nn.functional.conv2d and its autograd, reference
-# src/utils.py:416-474, 261-309, 322-414).  Activations are channels_last tensors of logical shape (N, C, H, W).
-def _conv_desc(N, H, W, cin, cout, k, padding, has_bias):
-    d = kl.Conv2dDesc()
-    d.N, d.H, d.W, d.cin, d.cout, d.k, d.pad, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(k), int(padding), int(has_bias)
-    return d
+# The three families of single convolution layers and their gradients, one description behind them as in the library (enc::Layer,
+# csrc/api_layer.hip): a cached plan per layer shape (_layer_plan) and one body each for pack, forward and backward.  The public
+# functions of a family, further down, say which layer theirs is: the family ("conv2d", "conv2d_s2", "conv2d_rp": kpn_<family>_*) and
+# ``what``, (k, padding) of the stride-1 family or the kind of the other two.
 
-
-# The arithmetic of the convolution's GEMMs (include/kpnerf.h): ``arith`` = kl.CONV_F32 (0, the default: v_mfma_f32_32x32x2_f32) or
-# kl.CONV_BF16X3 (1: three bf16 pieces per operand on v_mfma_f32_32x32x16_bf16, csrc/encoder_split_kernels.hip).  A packed weight, a
+# The arithmetic of the stride-1 convolution's GEMMs (include/kpnerf.h): ``arith`` = kl.CONV_F32 (0, the default: v_mfma_f32_32x32x2_f32)
+# or kl.CONV_BF16X3 (1: three bf16 pieces per operand on v_mfma_f32_32x32x16_bf16, csrc/encoder_split_kernels.hip).  A packed weight, a
 # workspace and a block's packed legs belong to one arithmetic.
 class _ArithLibrary:
     """kpn_conv2d_<f> and kpn_conv_block_<f> of the library as their _ex forms with one arith; everything else is the library's"""
@@ -1068,9 +1065,121 @@ def _conv_weight(w):
     return w.contiguous()
 
 
+_LAYER_DESCS = {"conv2d": kl.Conv2dDesc, "conv2d_s2": kl.Conv2dS2Desc, "conv2d_rp": kl.Conv2dRpDesc}
+_NCHW_STEMS = (("conv2d_s2", kl.S2_STEM7), ("conv2d_rp", kl.RP_STEM7))      # read x as a contiguous NCHW tensor, have no input gradient
+
+
+@functools.lru_cache(maxsize=4096)      # a training loop has one per layer shape and arithmetic: the encoders together stay below 200
+def _layer_plan(L, fam, what, cin, cout, N=None, H=None, W=None, has_bias=False):
+    """Everything about a layer that its key decides, built once: ``L`` is the library the calls run on (_conv_library(arith): the
+    arithmetic is part of the key through it), N to has_bias the descriptor's fields.  Callers pass them by position.
+    -> (byref of the descriptor, forward, backward, pack_device, workspace bytes, packed floats, Ho, Wo, shape of dw in the layer's own
+    layout (IOHW for the transposed layer), x is read as contiguous NCHW, the layer has an input gradient, the descriptor).
+    Without N, H, W it is the packer's plan, which depends on the weight alone: it has no workspace and no output size.
+    Raises the library's reason for a descriptor it does not serve (nothing is kept then: the next call asks again)."""
+    weight_only = N is None
+    if weight_only:
+        N, H, W = 1, 2, 2
+    d = _LAYER_DESCS[fam]()
+    d.N, d.H, d.W, d.cin, d.cout, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(has_bias)
+    if fam == "conv2d":
+        k, pad = what
+        d.k, d.pad = int(k), int(pad)
+        Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
+    elif fam == "conv2d_s2":
+        d.kind, k = int(what), 7 if what == kl.S2_STEM7 else 3
+        Ho, Wo = (2 * H, 2 * W) if what == kl.S2_DECONV3 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    else:
+        d.kind, k = int(what), 3 if what == kl.RP_CONV3 else 7
+        Ho, Wo = H, W
+    dw_shape = (cin, cout, k, k) if (fam, what) == ("conv2d_s2", kl.S2_DECONV3) else (cout, cin, k, k)
+    pre = f"kpn_{fam}_"
+    if weight_only:
+        nb, pf = 0, _desc_size(L, d, pre + "packed_floats", pre + "pack_device", f"{fam}: unsupported weight {dw_shape}")
+    else:
+        nb = _desc_size(L, d, pre + "workspace_bytes", pre + "forward", f"{fam}: unsupported convolution")
+        pf = getattr(L, pre + "packed_floats")(ctypes.byref(d))
+    nchw = (fam, what) in _NCHW_STEMS
+    return (ctypes.byref(d), getattr(L, pre + "forward"), getattr(L, pre + "backward"), getattr(L, pre + "pack_device"), nb, pf, Ho, Wo,
+            dw_shape, nchw, not nchw, d)
+
+
+def _layer_supported(L, fam, what, cin, cout):
+    try:
+        _layer_plan(L, fam, what, cin, cout)
+    except ValueError:
+        return False
+    return True
+
+
+def _layer_input(t, name, nchw, channels=None):
+    """x as the layer reads it: dense in channels_last memory, or (the stems) a contiguous NCHW tensor"""
+    if not nchw:
+        return _channels_last(t, name, channels)
+    t = _dev(t, name)
+    if t.dim() != 4 or not t.is_contiguous() or (channels is not None and t.shape[1] != channels):
+        raise ValueError(f"{name} must be a contiguous NCHW (N, {channels if channels is not None else 'C'}, H, W) tensor, got {tuple(t.shape)}")
+    return t
+
+
+def _layer_pack(L, fam, what, w, cin, cout):
+    ref, _, _, pack, _, n, _, _, _, _, _, _ = _layer_plan(L, fam, what, cin, cout)
+    packed = torch.empty(n, dtype=_f32, device=w.device)
+    L.check(pack(ref, _p(w), _p(packed), _stream()))
+    return packed
+
+
+def _layer_forward(L, fam, what, x, packed, bias, cout):
+    try:
+        N, cin, H, W = x.shape
+    except (AttributeError, ValueError):    # no (N, C, H, W) to plan with: the refusal of the layout the layer reads
+        _layer_input(x, "x", (fam, what) in _NCHW_STEMS)
+        raise
+    ref, forward, _, _, nb, n, Ho, Wo, _, nchw, _, _ = _layer_plan(L, fam, what, cin, cout, N, H, W, bias is not None)
+    x = _layer_input(x, "x", nchw)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    if packed.numel() != n or packed.dtype != _f32 or packed.device != x.device:
+        raise ValueError(f"packed does not belong to this convolution ({fam}_pack)")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    if b is not None and tuple(b.shape) != (cout,):
+        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
+    y = torch.empty(N, Ho, Wo, cout, dtype=_f32, device=x.device)
+    L.check(forward(ref, _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
+    return y.permute(0, 3, 1, 2)
+
+
+def _layer_backward(L, fam, what, x, dy, packed, x_shape, has_bias, want_dx, want_dw, want_db):
+    """dy: checked by the caller (_channels_last)"""
+    N, cin, H, W = x_shape
+    cout = dy.shape[1]
+    ref, _, backward, _, nb, n, Ho, Wo, dw_shape, nchw, has_dx, _ = _layer_plan(L, fam, what, cin, cout, N, H, W, has_bias)
+    if want_dx and not has_dx:
+        raise ValueError(f"{fam}: the stem has no input gradient")
+    if tuple(dy.shape) != (N, cout, Ho, Wo):
+        raise ValueError(f"dy must be {(N, cout, Ho, Wo)}, got {tuple(dy.shape)}")
+    want_db = bool(want_db and has_bias)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dy.device)
+    if want_dw:
+        x = _layer_input(x, "x", nchw, cin)
+        if tuple(x.shape) != (N, cin, H, W):
+            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
+    if want_dx and (packed is None or packed.numel() != n or packed.device != dy.device):
+        raise ValueError(f"packed does not belong to this convolution ({fam}_pack)")
+    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
+    dw = torch.empty(dw_shape, dtype=_f32, device=dy.device) if want_dw else None
+    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
+    if want_dx or want_dw or want_db:
+        L.check(backward(ref, _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw), _p(db), _p(ws), nb,
+                         _stream()))
+    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+
+
+# ------------------------------------------------------------------------------------------------
+# One stride-1 convolution and its gradients (kpn_conv2d_*; torch.nn.functional.conv2d and its autograd, reference
+# src/utils.py:416-474, 261-309, 322-414).  Activations are channels_last tensors of logical shape (N, C, H, W).
 def conv2d_supported(cin, cout, k, arith=0):
     """whether kpn_conv2d_* serves a stride-1 convolution of these channel counts and this square kernel"""
-    return _conv_library(arith).kpn_conv2d_packed_floats(ctypes.byref(_conv_desc(1, 1, 1, cin, cout, k, 0, 0))) > 0
+    return _layer_supported(_conv_library(arith), "conv2d", (k, 0), cin, cout)
 
 
 def conv2d_pack(weight, arith=0):
@@ -1078,30 +1187,13 @@ def conv2d_pack(weight, arith=0):
     transposed and flipped) read (kpn_conv2d_pack_device), for the calls with the same ``arith``."""
     L = _conv_library(arith)
     w = _conv_weight(weight.detach())
-    d = _conv_desc(1, 1, 1, w.shape[1], w.shape[0], w.shape[2], 0, 0)
-    n = _desc_size(L, d, "kpn_conv2d_packed_floats", "kpn_conv2d_pack_device", f"conv2d: unsupported weight {tuple(w.shape)}")
-    packed = torch.empty(n, dtype=_f32, device=w.device)
-    L.check(L.kpn_conv2d_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
-    return packed
+    return _layer_pack(L, "conv2d", (w.shape[2], 0), w, w.shape[1], w.shape[0])
 
 
 def conv2d_forward(x, packed, bias, cout, k, padding, arith=0):
     """conv2d(x, w, bias, stride=1, padding=padding) for packed = conv2d_pack(w, arith) (kpn_conv2d_forward).  x: (N, cin, H, W)
     channels_last; returns (N, cout, Ho, Wo) channels_last."""
-    L = _conv_library(arith)
-    x = _channels_last(x, "x")
-    N, cin, H, W = x.shape
-    d = _conv_desc(N, H, W, cin, cout, k, padding, bias is not None)
-    ws, nb = _desc_workspace(L, d, x.device, *_CONV_WORKSPACE)
-    if packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
-        raise ValueError("packed does not belong to this convolution (conv2d_pack)")
-    b = None if bias is None else _dev(bias.detach(), "bias")
-    if b is not None and tuple(b.shape) != (cout,):
-        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
-    Ho, Wo = H + 2 * padding - k + 1, W + 2 * padding - k + 1
-    y = torch.empty(N, Ho, Wo, cout, dtype=_f32, device=x.device)
-    L.check(L.kpn_conv2d_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
-    return y.permute(0, 3, 1, 2)
+    return _layer_forward(_conv_library(arith), "conv2d", (k, padding), x, packed, bias, cout)
 
 
 def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want_dw=True, want_db=True, arith=0):
@@ -1110,24 +1202,9 @@ def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want
     only: either may be None when its leg is off.  dx is channels_last, dw OIHW."""
     L = _conv_library(arith)
     dy = _channels_last(dy, "dy")
-    N, cout, Ho, Wo = dy.shape
-    H, W = Ho - 2 * padding + k - 1, Wo - 2 * padding + k - 1
-    want_db = bool(want_db and has_bias)
-    d = _conv_desc(N, H, W, cin, cout, k, padding, has_bias)
-    ws, nb = _desc_workspace(L, d, dy.device, *_CONV_WORKSPACE)
-    if want_dw:
-        x = _channels_last(x, "x", cin)
-        if tuple(x.shape) != (N, cin, H, W):
-            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
-    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
-        raise ValueError("packed does not belong to this convolution (conv2d_pack)")
-    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
-    dw = torch.empty(cout, cin, k, k, dtype=_f32, device=dy.device) if want_dw else None
-    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
-    if want_dx or want_dw or want_db:
-        L.check(L.kpn_conv2d_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
-                                      _p(db), _p(ws), nb, _stream()))
-    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+    N, _, Ho, Wo = dy.shape
+    return _layer_backward(L, "conv2d", (k, padding), x, dy, packed, (N, cin, Ho - 2 * padding + k - 1, Wo - 2 * padding + k - 1), has_bias,
+                           want_dx, want_dw, want_db)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1135,36 +1212,9 @@ def conv2d_backward(x, dy, packed, cin, k, padding, has_bias, want_dx=True, want
 # pad 3) and ConvTranspose2d(k 3, stride 2, pad 1, output_padding 1), reference src/utils.py:199-247, 322-414.  ``kind`` is one of
 # lib.S2_CONV3 / S2_STEM7 / S2_DECONV3.  Activations are channels_last tensors of logical shape (N, C, H, W); the stem's input alone
 # is a contiguous NCHW tensor, read as it is.
-_S2_WORKSPACE = ("kpn_conv2d_s2_workspace_bytes", "kpn_conv2d_s2_forward", "conv2d_s2: unsupported convolution")
-
-
-def _s2_desc(kind, N, H, W, cin, cout, has_bias):
-    d = kl.Conv2dS2Desc()
-    d.N, d.H, d.W, d.cin, d.cout, d.kind, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(kind), int(has_bias)
-    return d
-
-
-def _s2_channels(kind, weight_shape):
-    """(cin, cout) of a weight in the layer's own layout: OIHW, or (cin, cout, 3, 3) for the transposed layer"""
-    return (weight_shape[0], weight_shape[1]) if kind == kl.S2_DECONV3 else (weight_shape[1], weight_shape[0])
-
-
-def _s2_out_hw(kind, H, W):
-    return (2 * H, 2 * W) if kind == kl.S2_DECONV3 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
-
-
-def _s2_input(kind, x, name, channels=None):
-    if kind != kl.S2_STEM7:
-        return _channels_last(x, name, channels)
-    x = _dev(x, name)
-    if x.dim() != 4 or not x.is_contiguous() or (channels is not None and x.shape[1] != channels):
-        raise ValueError(f"{name} must be a contiguous NCHW (N, {channels if channels is not None else 'C'}, H, W) tensor, got {tuple(x.shape)}")
-    return x
-
-
 def conv2d_s2_supported(kind, cin, cout):
     """whether kpn_conv2d_s2_* serves a layer of this kind and these channel counts"""
-    return kl.get_library().kpn_conv2d_s2_packed_floats(ctypes.byref(_s2_desc(kind, 1, 2, 2, cin, cout, 0))) > 0
+    return _layer_supported(kl.get_library(), "conv2d_s2", kind, cin, cout)
 
 
 def conv2d_s2_pack(weight, kind):
@@ -1174,31 +1224,15 @@ def conv2d_s2_pack(weight, kind):
     w = _conv_weight(weight.detach())
     if w.shape[2] != (7 if kind == kl.S2_STEM7 else 3):
         raise ValueError(f"conv2d_s2: a weight {tuple(w.shape)} does not belong to kind {kind}")
-    cin, cout = _s2_channels(kind, w.shape)
-    d = _s2_desc(kind, 1, 2, 2, cin, cout, 0)
-    n = _desc_size(L, d, "kpn_conv2d_s2_packed_floats", "kpn_conv2d_s2_pack_device", f"conv2d_s2: unsupported weight {tuple(w.shape)}")
-    packed = torch.empty(n, dtype=_f32, device=w.device)
-    L.check(L.kpn_conv2d_s2_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
-    return packed
+    # (cin, cout) of a weight in the layer's own layout: OIHW, or (cin, cout, 3, 3) for the transposed layer
+    cin, cout = (w.shape[0], w.shape[1]) if kind == kl.S2_DECONV3 else (w.shape[1], w.shape[0])
+    return _layer_pack(L, "conv2d_s2", kind, w, cin, cout)
 
 
 def conv2d_s2_forward(x, packed, bias, cout, kind):
     """The layer's forward for packed = conv2d_s2_pack(w, kind) (kpn_conv2d_s2_forward).  x: (N, cin, H, W) channels_last, or
     contiguous NCHW for the stem; returns (N, cout, Ho, Wo) channels_last."""
-    L = kl.get_library()
-    x = _s2_input(kind, x, "x")
-    N, cin, H, W = x.shape
-    d = _s2_desc(kind, N, H, W, cin, cout, bias is not None)
-    ws, nb = _desc_workspace(L, d, x.device, *_S2_WORKSPACE)
-    if packed.numel() != L.kpn_conv2d_s2_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
-        raise ValueError("packed does not belong to this convolution (conv2d_s2_pack)")
-    b = None if bias is None else _dev(bias.detach(), "bias")
-    if b is not None and tuple(b.shape) != (cout,):
-        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
-    Ho, Wo = _s2_out_hw(kind, H, W)
-    y = torch.empty(N, Ho, Wo, cout, dtype=_f32, device=x.device)
-    L.check(L.kpn_conv2d_s2_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
-    return y.permute(0, 3, 1, 2)
+    return _layer_forward(kl.get_library(), "conv2d_s2", kind, x, packed, bias, cout)
 
 
 def conv2d_s2_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, want_dw=True, want_db=True):
@@ -1206,31 +1240,8 @@ def conv2d_s2_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, wan
     gradient that is not wanted is None and its leg is not launched.  x (of shape x_shape, in the forward's layout) is read for dw
     only and packed for dx only: either may be None when its leg is off.  dx is channels_last, dw has the weight's own layout.  The
     stem has no input gradient."""
-    L = kl.get_library()
-    dy = _channels_last(dy, "dy")
-    N, cin, H, W = (int(v) for v in x_shape)
-    cout = dy.shape[1]
-    if want_dx and kind == kl.S2_STEM7:
-        raise ValueError("conv2d_s2: the stem has no input gradient")
-    if tuple(dy.shape) != (N, cout) + _s2_out_hw(kind, H, W):
-        raise ValueError(f"dy must be {(N, cout) + _s2_out_hw(kind, H, W)}, got {tuple(dy.shape)}")
-    want_db = bool(want_db and has_bias)
-    d = _s2_desc(kind, N, H, W, cin, cout, has_bias)
-    ws, nb = _desc_workspace(L, d, dy.device, *_S2_WORKSPACE)
-    if want_dw:
-        x = _s2_input(kind, x, "x", cin)
-        if tuple(x.shape) != (N, cin, H, W):
-            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
-    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_s2_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
-        raise ValueError("packed does not belong to this convolution (conv2d_s2_pack)")
-    k = 7 if kind == kl.S2_STEM7 else 3
-    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
-    dw = torch.empty((cin, cout, k, k) if kind == kl.S2_DECONV3 else (cout, cin, k, k), dtype=_f32, device=dy.device) if want_dw else None
-    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
-    if want_dx or want_dw or want_db:
-        L.check(L.kpn_conv2d_s2_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
-                                         _p(db), _p(ws), nb, _stream()))
-    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+    return _layer_backward(kl.get_library(), "conv2d_s2", kind, x, _channels_last(dy, "dy"), packed, x_shape, has_bias, want_dx, want_dw,
+                           want_db)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1238,19 +1249,6 @@ def conv2d_s2_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, wan
 # k = 7 and the 7x7 stem, reference src/utils.py:199-259.  ``kind`` is one of lib.RP_CONV3 / RP_CONV7 / RP_STEM7.  Activations are
 # channels_last tensors of logical shape (N, C, H, W); the stem's input alone is a contiguous NCHW tensor, read as it is.  The output
 # has the input's size.
-_RP_WORKSPACE = ("kpn_conv2d_rp_workspace_bytes", "kpn_conv2d_rp_forward", "conv2d_rp: unsupported convolution")
-
-
-def _rp_desc(kind, N, H, W, cin, cout, has_bias):
-    d = kl.Conv2dRpDesc()
-    d.N, d.H, d.W, d.cin, d.cout, d.kind, d.has_bias = int(N), int(H), int(W), int(cin), int(cout), int(kind), int(has_bias)
-    return d
-
-
-def _rp_input(kind, x, name, channels=None):
-    return _s2_input(kl.S2_STEM7 if kind == kl.RP_STEM7 else kl.S2_CONV3, x, name, channels)
-
-
 def conv2d_rp_kind(weight_shape):
     """the kind a (cout, cin, k, k) weight belongs to: k = 3, k = 7, or the stem (k = 7 with at most 4 input channels)"""
     k = weight_shape[-1]
@@ -1261,7 +1259,7 @@ def conv2d_rp_kind(weight_shape):
 
 def conv2d_rp_supported(kind, cin, cout):
     """whether kpn_conv2d_rp_* serves a layer of this kind and these channel counts"""
-    return kl.get_library().kpn_conv2d_rp_packed_floats(ctypes.byref(_rp_desc(kind, 1, 1, 1, cin, cout, 0))) > 0
+    return _layer_supported(kl.get_library(), "conv2d_rp", kind, cin, cout)
 
 
 def conv2d_rp_pack(weight, kind):
@@ -1271,60 +1269,21 @@ def conv2d_rp_pack(weight, kind):
     w = _conv_weight(weight.detach())
     if w.shape[2] != (3 if kind == kl.RP_CONV3 else 7):
         raise ValueError(f"conv2d_rp: a weight {tuple(w.shape)} does not belong to kind {kind}")
-    d = _rp_desc(kind, 1, 1, 1, w.shape[1], w.shape[0], 0)
-    n = _desc_size(L, d, "kpn_conv2d_rp_packed_floats", "kpn_conv2d_rp_pack_device", f"conv2d_rp: unsupported weight {tuple(w.shape)}")
-    packed = torch.empty(n, dtype=_f32, device=w.device)
-    L.check(L.kpn_conv2d_rp_pack_device(ctypes.byref(d), _p(w), _p(packed), _stream()))
-    return packed
+    return _layer_pack(L, "conv2d_rp", kind, w, w.shape[1], w.shape[0])
 
 
 def conv2d_rp_forward(x, packed, bias, cout, kind):
     """The layer's forward for packed = conv2d_rp_pack(w, kind) (kpn_conv2d_rp_forward).  x: (N, cin, H, W) channels_last, or
     contiguous NCHW for the stem; returns (N, cout, H, W) channels_last."""
-    L = kl.get_library()
-    x = _rp_input(kind, x, "x")
-    N, cin, H, W = x.shape
-    d = _rp_desc(kind, N, H, W, cin, cout, bias is not None)
-    ws, nb = _desc_workspace(L, d, x.device, *_RP_WORKSPACE)
-    if packed.numel() != L.kpn_conv2d_rp_packed_floats(ctypes.byref(d)) or packed.dtype != _f32 or packed.device != x.device:
-        raise ValueError("packed does not belong to this convolution (conv2d_rp_pack)")
-    b = None if bias is None else _dev(bias.detach(), "bias")
-    if b is not None and tuple(b.shape) != (cout,):
-        raise ValueError(f"bias must be ({cout},), got {tuple(b.shape)}")
-    y = torch.empty(N, H, W, cout, dtype=_f32, device=x.device)
-    L.check(L.kpn_conv2d_rp_forward(ctypes.byref(d), _p(x), _p(packed), _p(b), _p(y), _p(ws), nb, _stream()))
-    return y.permute(0, 3, 1, 2)
+    return _layer_forward(kl.get_library(), "conv2d_rp", kind, x, packed, bias, cout)
 
 
 def conv2d_rp_backward(x, dy, packed, x_shape, kind, has_bias, want_dx=True, want_dw=True, want_db=True):
     """(dx, dw, db) of conv2d_rp_forward for the output gradient dy (N, cout, H, W) channels_last (kpn_conv2d_rp_backward); a gradient
     that is not wanted is None and its leg is not launched.  x (of shape x_shape, in the forward's layout) is read for dw only and
     packed for dx only: either may be None when its leg is off.  dx is channels_last, dw OIHW.  The stem has no input gradient."""
-    L = kl.get_library()
-    dy = _channels_last(dy, "dy")
-    N, cin, H, W = (int(v) for v in x_shape)
-    cout = dy.shape[1]
-    if want_dx and kind == kl.RP_STEM7:
-        raise ValueError("conv2d_rp: the stem has no input gradient")
-    if tuple(dy.shape) != (N, cout, H, W):
-        raise ValueError(f"dy must be {(N, cout, H, W)}, got {tuple(dy.shape)}")
-    want_db = bool(want_db and has_bias)
-    d = _rp_desc(kind, N, H, W, cin, cout, has_bias)
-    ws, nb = _desc_workspace(L, d, dy.device, *_RP_WORKSPACE)
-    if want_dw:
-        x = _rp_input(kind, x, "x", cin)
-        if tuple(x.shape) != (N, cin, H, W):
-            raise ValueError(f"x must be {(N, cin, H, W)}, got {tuple(x.shape)}")
-    if want_dx and (packed is None or packed.numel() != L.kpn_conv2d_rp_packed_floats(ctypes.byref(d)) or packed.device != dy.device):
-        raise ValueError("packed does not belong to this convolution (conv2d_rp_pack)")
-    k = 3 if kind == kl.RP_CONV3 else 7
-    dx = torch.empty(N, H, W, cin, dtype=_f32, device=dy.device) if want_dx else None
-    dw = torch.empty(cout, cin, k, k, dtype=_f32, device=dy.device) if want_dw else None
-    db = torch.empty(cout, dtype=_f32, device=dy.device) if want_db else None
-    if want_dx or want_dw or want_db:
-        L.check(L.kpn_conv2d_rp_backward(ctypes.byref(d), _p(x) if want_dw else None, _p(dy), _p(packed) if want_dx else None, _p(dx), _p(dw),
-                                         _p(db), _p(ws), nb, _stream()))
-    return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db
+    return _layer_backward(kl.get_library(), "conv2d_rp", kind, x, _channels_last(dy, "dy"), packed, x_shape, has_bias, want_dx, want_dw,
+                           want_db)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1424,9 +1383,8 @@ def _block_params(L, cin, cout, norms, packed, device, keep):
     pr = kl.ConvBlockParams()
     for i in range(legs):
         g, b = (_norm_vec(t, f"bn{i + 1}.{n}", win[i]) for t, n in zip(norms[i], ("weight", "bias")))
-        cd = _conv_desc(1, 1, 1, win[i], wout[i], 3 if i < 3 else 1, 0, 0)
         pk = packed[i]
-        if pk.numel() != L.kpn_conv2d_packed_floats(ctypes.byref(cd)) or pk.dtype != _f32 or pk.device != device:
+        if pk.numel() != _layer_plan(L, "conv2d", (3 if i < 3 else 1, 0), win[i], wout[i])[5] or pk.dtype != _f32 or pk.device != device:
             raise ValueError(f"packed[{i}] does not belong to this block's convolution {win[i]} -> {wout[i]} (conv2d_pack)")
         keep += [g, b, pk]
         pr.gamma[i], pr.beta[i], pr.packed[i] = g.data_ptr(), b.data_ptr(), pk.data_ptr()

@@ -88,7 +88,6 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv.py needs a GPU: a time measured anywhere else says nothing")
-    import ctypes
     from keypointnerf_amd import lib as kl
     from keypointnerf_amd import ops
     L = kl.get_library()
@@ -110,7 +109,7 @@ def main():
         b = torch.randn(cout, device="cuda", generator=gen) if bias else None
         dy = torch.randn(N, cout, H, W, device="cuda", generator=gen).contiguous(memory_format=cl)
         packed = ops.conv2d_pack(w)
-        ranges = L.kpn_conv2d_wgrad_ranges(ctypes.byref(ops._conv_desc(N, H, W, cin, cout, k, pad, bias)))
+        ranges = L.kpn_conv2d_wgrad_ranges(ops._layer_plan(L, "conv2d", (k, pad), cin, cout, N, H, W, bias)[0])
         bsz = [cout] if bias else None
         cb = lambda mask: torch.ops.aten.convolution_backward(dy, x, w, bsz, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1, mask)
         arms = {
@@ -127,7 +126,7 @@ def main():
         med, med3 = {}, {}
         if args.arith:
             packed3 = ops.conv2d_pack(w, arith=A3)
-            ranges3 = L.kpn_conv2d_ex_wgrad_ranges(ctypes.byref(ops._conv_desc(N, H, W, cin, cout, k, pad, bias)), A3)
+            ranges3 = L.kpn_conv2d_ex_wgrad_ranges(ops._layer_plan(L, "conv2d", (k, pad), cin, cout, N, H, W, bias)[0], A3)
             arms3 = {
                 "fwd": lambda: ops.conv2d_forward(x, packed3, b, cout, k, pad, arith=A3),
                 "dx": lambda: ops.conv2d_backward(None, dy, packed3, cin, k, pad, bias, True, False, False, arith=A3),

@@ -4,10 +4,11 @@ gradients of a network, the outputs of its norm layers and the ReLU margin of it
 tests/layer_cases.py; the bar: tests/parity.py."""
 import copy
 
+import pytest
 import torch
 
 from tests import layer_cases as lc
-from tests.parity import check
+from tests.parity import check, nchw, nhwc
 
 
 def op_run(fam, op_of, name, channels_last=True, need=(True, True, True)):
@@ -68,6 +69,62 @@ def check_op_nchw_bits(fam, op_of, names):
         assert b[0].is_contiguous(memory_format=torch.channels_last)
         if fam.has_dx(op_of(fam.cases[name])[0]):
             assert torch.equal(a[1].grad, b[1].grad) and b[1].grad.is_contiguous()  # the gradient of an NCHW leaf comes back NCHW
+
+
+# ---- keypointnerf_amd.ops under the operators: one cached plan per layer shape ----
+def _ops_of(fam, c):
+    """(pack(w), forward(x, packed, b), backward(x, dy, packed, **want)) of keypointnerf_amd.ops for a case given as its dict"""
+    from keypointnerf_amd import ops
+    if "kind" not in c:
+        return (ops.conv2d_pack, lambda x, p, b: ops.conv2d_forward(x, p, b, c["cout"], c["k"], c["pad"]),
+                lambda x, dy, p, **kw: ops.conv2d_backward(x, dy, p, c["cin"], c["k"], c["pad"], c["bias"], **kw))
+    pack, fwd, bwd = (getattr(ops, fam.prefix[len("kpn_"):] + f) for f in ("pack", "forward", "backward"))
+    return (lambda w: pack(w, c["kind"]), lambda x, p, b: fwd(x, p, b, c["cout"], c["kind"]),
+            lambda x, dy, p, **kw: bwd(x, dy, p, (c["N"], c["cin"], c["H"], c["W"]), c["kind"], c["bias"], **kw))
+
+
+def _ops_run_twice(fam, c):
+    """the packer, then two forward and two backward calls of keypointnerf_amd.ops on the inputs of a case given as its dict: the two
+    pairs give equal bits -> ((misses, hits, plans) the four calls added to the plan cache, (y, dx, dw, db) of the first pair)"""
+    from keypointnerf_amd import ops
+    x, w, b, g = lc.inputs(fam, c)
+    pack, fwd, bwd = _ops_of(fam, c)
+    xd = x.cuda().contiguous() if fam.x_is_nchw(c) else x.cuda().contiguous(memory_format=torch.channels_last)
+    gd, bd = g.cuda().contiguous(memory_format=torch.channels_last), (None if b is None else b.cuda())
+    packed = pack(w.cuda())
+    before = ops._layer_plan.cache_info()
+    runs = [(fwd(xd, packed, bd),) + bwd(xd, gd, packed, want_dx=fam.has_dx(c)) for _ in range(2)]
+    after = ops._layer_plan.cache_info()
+    for first, second in zip(*runs):
+        assert (first is None and second is None) or torch.equal(first.contiguous().view(torch.int32), second.contiguous().view(torch.int32))
+    return (after.misses - before.misses, after.hits - before.hits, after.currsize - before.currsize), runs[0]
+
+
+def check_ops_plan_once_per_shape(fam, L, B, names, stem_name=None):
+    """for each case of `names` (and the stem): four calls of one shape build one plan and look it up three times; the same layer
+    with one image more builds a second one and still gives the bits of the C-ABI driver.  The stem refuses a dx by its message"""
+    from keypointnerf_amd import ops
+    for name in names + ((stem_name,) if stem_name else ()):
+        ops._layer_plan.cache_clear()                                   # the tests before this one have planned these shapes
+        c = fam.cases[name]
+        added, _ = _ops_run_twice(fam, c)
+        assert added == (1, 3, 1), (name, added)
+        c2 = dict(c, N=c["N"] + 1)
+        added, (y, dx, dw, db) = _ops_run_twice(fam, c2)
+        assert added == (1, 3, 1), (name, added)
+        x, w, b, g = lc.inputs(fam, c2)
+        packed = lc.pack(fam, L, B, c2, w.numpy())
+        y_abi = lc.forward(fam, L, B, c2, lc.x_layout(fam, c2, x), packed, None if b is None else b.numpy())
+        abi = lc.backward(fam, L, B, c2, lc.x_layout(fam, c2, x), nhwc(g), packed)
+        assert torch.equal(y.cpu(), torch.from_numpy(nchw(y_abi))) and torch.equal(dw.cpu(), torch.from_numpy(abi["dw"]))
+        assert (dx is None) == (not fam.has_dx(c)) and (dx is None or torch.equal(dx.cpu(), torch.from_numpy(nchw(abi["dx"]))))
+        assert (db is None) == (not c["bias"]) and (db is None or torch.equal(db.cpu(), torch.from_numpy(abi["db"])))
+    if stem_name:
+        c = fam.cases[stem_name]
+        x, w, b, g = lc.inputs(fam, c)
+        pack, _, bwd = _ops_of(fam, c)
+        with pytest.raises(ValueError, match=f"^{fam.prefix[len('kpn_'):-1]}: the stem has no input gradient$"):
+            bwd(x.cuda().contiguous(), g.cuda().contiguous(memory_format=torch.channels_last), pack(w.cuda()), want_dx=True)
 
 
 # ---- networks trained through the operators ----

@@ -124,6 +124,12 @@ def test_op_fake_kernel_shapes_and_refusals():
         torch.ops.kpnerf.conv2d(x, torch.zeros(4, 4, 3, 3, device="cuda"), None, 3)
 
 
+def test_ops_calls_of_one_shape_share_one_plan_and_keep_the_bits_of_the_abi(L, B):
+    """keypointnerf_amd.ops on the smallest case: two forward and two backward calls build one plan (ops._layer_plan) and give
+    equal bits, the layer with one image more builds a second plan and has the bits of the C-ABI driver"""
+    loc.check_ops_plan_once_per_shape(cc.FAMILY, L, B, ("k3_p0",))
+
+
 # ---- install_native_convs ----
 _stack = cc.stand_in_stack
 

@@ -106,6 +106,12 @@ def test_the_stem_op_raises_on_an_input_that_requires_a_gradient():
         torch.ops.kpnerf.conv2d_replicate(torch.zeros(1, 6, 5, 6, device="cuda"), torch.zeros(4, 6, 3, 3, device="cuda"), None)
 
 
+def test_ops_calls_of_one_shape_share_one_plan_and_keep_the_bits_of_the_abi(L, B):
+    """keypointnerf_amd.ops on the smallest case and on a stem: two forward and two backward calls build one plan (ops._layer_plan) and give
+    equal bits, the layer with one image more builds a second plan and has the bits of the C-ABI driver; the stem refuses a dx"""
+    loc.check_ops_plan_once_per_shape(rc.FAMILY, L, B, ("rp3_2x3",), stem_name="rp7stem_3to16")
+
+
 # ---- install_native_tex ----
 NARROW_SEED = 2                             # of the seeds 1, 2, 5, 7, 8, 9 tried on the CPU only 8 misses the margin below
 NARROW_NORMS, NARROW_VALUES = 6, 2112       # the norms in front of a ReLU and their outputs: 2 (4 96 + 8 24 + 16 6 + 2 16 6 + 8 24)

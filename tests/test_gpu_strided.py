@@ -105,6 +105,12 @@ def test_the_stem_op_raises_on_an_input_that_requires_a_gradient():
         torch.ops.kpnerf.conv2d_down2(torch.zeros(1, 4, 5, 6, device="cuda"), torch.zeros(4, 4, 3, 3, device="cuda"), None)
 
 
+def test_ops_calls_of_one_shape_share_one_plan_and_keep_the_bits_of_the_abi(L, B):
+    """keypointnerf_amd.ops on the smallest case and on a stem: two forward and two backward calls build one plan (ops._layer_plan) and give
+    equal bits, the layer with one image more builds a second plan and has the bits of the C-ABI driver; the stem refuses a dx"""
+    loc.check_ops_plan_once_per_shape(sc.FAMILY, L, B, ("s2_2x2",), stem_name="stem_odd")
+
+
 # ---- install_native_strided ----
 def _stack(seed=4):
     net = nn.Sequential(nn.Conv2d(3, 8, 7, stride=2, padding=3), nn.Conv2d(8, 16, 3, stride=2, padding=1),
